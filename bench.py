@@ -12,6 +12,11 @@ resident in HBM, one kernel launch through the C ABI (carma_logdensity_batch_dev
 One process per GPU.  The batch is sharded by rank with no data-path collective (independent
 evaluations -> weak scaling: every rank runs its own 1024-eval batches); RCCL is used only for
 the barrier and the max-over-ranks of the elapsed time.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set-up, warm-up, exactly K timed steps, the
+line.  --full adds every other leg (two batches in flight, the throughput regime, the samplers,
+steady state, per-launch kernel durations, the ladder-sharded leg, cpu_baseline, the Python API
+legs) with their keys on the same line.  --dump-outputs DIR writes the last timed step's output.
 """
 import argparse
 import json
@@ -28,6 +33,7 @@ import torch  # noqa: E402  (import torch BEFORE the HIP library so both share o
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 FP64_VALU_PEAK_TFLOPS = 78.6   # public MI355X FP64 vector peak = 256 CUs x 4 SIMDs x 16 FMA lanes/clk x 2 flop x 2.4 GHz
 MAX_CLOCK_GHZ = 2.4            # MI355X_MICROARCH.md: max clock; a wave64 VALU instruction holds its SIMD's issue port 4 cycles
+SETTLE_S = 0.2                 # plain run: seconds of back-to-back headline steps ahead of the W warm-up steps
 
 
 def main():
@@ -54,7 +60,13 @@ def main():
     ap.add_argument("--no-api", action="store_true", help="skip the legs through the drop-in Python API (the reference's own workloads: "
                     "the notebook's run_mcmc(20000) on OGLE, the README's run_mcmc(50000), choose_order(pmax=7))")
     ap.add_argument("--api-scale", type=float, default=1.0, help="fraction of the API legs' iteration counts (tests use 0.02)")
+    ap.add_argument("--full", action="store_true", help="run the secondary legs too (the --no-* options above pick among them); "
+                    "without it only the headline steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's log-densities to DIR/logdensity.npy "
+                    "(float64, one per evaluation of the batch; DIR/logdensity_rank<r>.npy per rank when N > 1)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu = args.no_mcmc = args.no_pipelined = args.no_steady = args.no_throughput = args.no_ladder = args.no_api = True
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -301,6 +313,24 @@ def main():
         steady = {"metric": "Kalman log-lik evals/sec, the headline step %d times back to back" % NS, "evals_per_s": world * B * NS / ts,
                   "ms_per_step": 1e3 * ts / NS, "launches": NS}
 
+    # A plain run has none of the legs above, which keep the device busy for ~0.1 s before the warm-up (the steady-state leg last:
+    # 1000 launches of this very step).  W warm-up launches alone would start the timed region on a device that has just woken
+    # up (see ORDER OF THE LEGS), so the step first runs back to back for SETTLE_S seconds: with K = 20 the kernel took 23.8-24.8 us
+    # without that, 22.1-22.2 with it, as behind the legs.  The legs also record HIP events before the timed region does; that
+    # region's events must not be the process's first (K = 20, median of 5 runs alternating with a run of every leg: 24.71 us per
+    # step with the first events inside the region, 24.11 with a pair recorded here, 24.28 behind the legs).
+    if not args.full:
+        evw = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        evw[0].record(stream)
+        t_settle = time.perf_counter() + SETTLE_S
+        while time.perf_counter() < t_settle:
+            for i in range(25 * NPOOL):
+                step(i)
+            torch.cuda.synchronize()
+        evw[1].record(stream)
+        torch.cuda.synchronize()
+        evw[0].elapsed_time(evw[1])
+
     for i in range(args.warmup):
         step(i)
     torch.cuda.synchronize()
@@ -348,16 +378,21 @@ def main():
     # sanity: the last step's output is the real thing
     last = out.cpu().numpy()
     n_finite = int(np.isfinite(last).sum())
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "logdensity.npy" if world == 1 else "logdensity_rank%d.npy" % rank), last)
 
     # ---- per-launch kernel duration (HIP events on the launch stream) ------------------------
-    M = max(1, min(args.steps, 256))
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(M)]
-    for i, (a, b) in enumerate(evs):
-        a.record(stream)
-        step(i)
-        b.record(stream)
-    torch.cuda.synchronize()
-    kdur_ms = np.array([a.elapsed_time(b) for a, b in evs])
+    kdur_ms = None
+    if args.full:
+        M = max(1, min(args.steps, 256))
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(M)]
+        for i, (a, b) in enumerate(evs):
+            a.record(stream)
+            step(i)
+            b.record(stream)
+        torch.cuda.synchronize()
+        kdur_ms = np.array([a.elapsed_time(b) for a, b in evs])
     # Average launch duration of the dominant kernel: HIP events around the K back-to-back launches of the timed region
     # (same stream), divided by K -- this is what rocprofv3's per-kernel average agrees with (profiles/).  Bracketing
     # every launch with its own pair of events (kdur_ms) adds the markers' own time (~2 us) to each figure; kept as
@@ -436,8 +471,8 @@ def main():
                 "traffic_source": traffic_src,
                 "kernel": kernel_name,
                 "kernel_avg_us": 1e3 * kernel_ms,
-                "kernel_bracketed_avg_us": 1e3 * float(np.mean(kdur_ms)),
-                "kernel_bracketed_min_us": 1e3 * float(kdur_ms.min()),
+                "kernel_bracketed_avg_us": 1e3 * float(np.mean(kdur_ms)) if kdur_ms is not None else None,
+                "kernel_bracketed_min_us": 1e3 * float(kdur_ms.min()) if kdur_ms is not None else None,
                 "algorithmic_bytes_per_launch": bytes_per_eval * B,
                 "binding_resource": "fp64_valu_issue",
                 "note": "HBM roofline reported as north_star asks; the kernel is bound by the FP64 VALU issue rate of one "

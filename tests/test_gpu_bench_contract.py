@@ -31,7 +31,7 @@ def _json_line(out):
 
 
 def test_single_gpu_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "50", "--warmup", "5", "--mcmc-iters", "200",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "50", "--warmup", "5", "--mcmc-iters", "200",
                         "--cpu-seconds", "1", "--ladder-iters", "20", "--api-scale", "0.02"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _json_line(r.stdout)
@@ -85,10 +85,44 @@ def test_single_gpu_line():
     assert ld["temperatures"] == 8 and ld["replicas"] == 128 and ld["rccl_ranks"] == 1 and ld["iters_per_s"] > 0
 
 
+def test_plain_run_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times exactly K steps and carries none of the secondary legs; --dump-outputs writes the last
+    timed step's log-densities: the same in two runs with the same arguments, and the CPU oracle's on that step's batch."""
+    import numpy as np
+    import oracle as orc
+    from carma_pack_amd.synth import theta_batch
+    from helpers import assert_parity, loglik_truth
+    K = 30
+    dumps = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", "3",
+                            "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = _json_line(r.stdout)
+        assert KEYS <= set(j) and j["steps"] == K and j["warmup"] == 3 and j["n_gpus"] == 1 and j["dtype"] == "f64"
+        assert abs(j["ms_per_step"] * 1e-3 * j["value"] - 1024) < 1e-6 * 1024
+        assert not {"cpu_baseline", "mcmc", "mcmc_large", "steady_state", "pipelined", "throughput", "throughput_1m",
+                    "ladder_sharded", "quickstart_ogle", "readme_run", "choose_order"} & set(j)
+        got = np.load(str(tmp_path / d / "logdensity.npy"))
+        assert got.dtype == np.float64 and got.shape == (1024,) and int(np.isfinite(got).sum()) == j["finite_in_last_batch"]
+        dumps.append(got)
+    assert np.array_equal(dumps[0], dumps[1], equal_nan=True)
+    # bench.py's inputs: eight batches from default_rng(2), step i evaluates batch i % 8
+    g = np.load(os.path.join(ROOT, "tests", "golden", "carma53_readme.npz"))
+    t, y, yerr = g["t"], g["y"], g["yerr"]
+    rng = np.random.default_rng(2)
+    pool = [theta_batch(rng, 1024, 5, 3, t, y, theta_center=g["theta"][0]) for _ in range(8)]
+    max_stdev = 10.0 * np.sqrt(np.mean(y * y) - np.mean(y) ** 2)
+    th = pool[(K - 1) % 8]
+    want = orc.OracleModel(t, y, yerr, 5, 3, max_stdev=max_stdev).logdensity_batch(th)
+    assert np.isfinite(want).sum() > 600
+    assert_parity(dumps[0], want, 1e-10, "bench.py --dump-outputs", arbiter=lambda i: loglik_truth(t, y, yerr, th[i], 5, 3)[0])
+
+
 def test_two_ranks_sharing_the_gpu():
     env = dict(os.environ, CARMA_BENCH_SHARE_GPU="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                        "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
+                        "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full",
                         "--gpus", "2", "--steps", "50", "--warmup", "5", "--mcmc-iters", "200", "--ladder-iters", "6"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -118,7 +152,7 @@ def _native_ladder_ranks(nranks):
            check=True, stdout=sp.PIPE, stderr=sp.STDOUT, timeout=600)
     env = dict(os.environ, CARMA_BENCH_SHARE_GPU="1", CARMA_RCCL_LIB=lib)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nranks),
-                        "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
+                        "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full",
                         "--gpus", str(nranks), "--steps", "50", "--warmup", "5", "--mcmc-iters", "100", "--no-pipelined", "--no-throughput",
                         "--ladder-iters", "6"], capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -150,7 +184,7 @@ def test_ladder_leg_cannot_hold_the_line_back():
     a NON-ZERO status (a wedged exchange is a failed run to the launcher; the line is there to be read on rc != 0)."""
     env = dict(os.environ, CARMA_BENCH_SHARE_GPU="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                        "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
+                        "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full",
                         "--gpus", "2", "--steps", "50", "--warmup", "5", "--no-mcmc", "--no-pipelined", "--no-throughput",
                         "--ladder-iters", "200", "--ladder-timeout", "0.01"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)

@@ -14,13 +14,13 @@ mkdir -p $OUT
 # which build the counters below belong to (bench.py attaches them to a run of the same build only)
 python3 -c "import sys, json; sys.path.insert(0, '$REPO'); from carma_pack_amd._lib import build_ids; json.dump(build_ids(), open('$OUT/ids.json', 'w'))"
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o $TAG -- python3 $REPO/bench.py --no-cpu --no-pipelined --no-mcmc-large --no-api > $OUT/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o $TAG -- python3 $REPO/bench.py --full --no-cpu --no-pipelined --no-mcmc-large --no-api > $OUT/stats.log 2>&1
 echo "stats rc=$?"
 # the same without the cooperative sampler launch (whose process faults at exit under the profiler, after the statistics are written)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_nomcmc -o $TAG -- python3 $REPO/bench.py --no-cpu --no-pipelined --no-mcmc --no-mcmc-large --no-ladder --no-api > $OUT/stats_nomcmc.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_nomcmc -o $TAG -- python3 $REPO/bench.py --full --no-cpu --no-pipelined --no-mcmc --no-mcmc-large --no-ladder --no-api > $OUT/stats_nomcmc.log 2>&1
 echo "stats (no sampler legs) rc=$?"
 # (--no-api: the API legs run the same kernels at other sizes -- their dispatches must not be summed into the sampler leg's)
-PMC_ARGS="--steps 50 --warmup 5 --no-cpu --no-pipelined --no-ladder --no-mcmc-large --no-api --mcmc-iters 200"
+PMC_ARGS="--full --steps 50 --warmup 5 --no-cpu --no-pipelined --no-ladder --no-mcmc-large --no-api --mcmc-iters 200"
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_$c -o $TAG -- python3 $REPO/bench.py $PMC_ARGS > $OUT/pmc_$c.log 2>&1
   echo "pmc $c rc=$?"

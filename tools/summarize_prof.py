@@ -26,7 +26,7 @@ for f in glob.glob(os.path.join(src, "stats", "**", "*kernel_stats.csv"), recurs
     shutil.copy(f, os.path.join(dst, "kernel_stats_%s.csv" % tag))
     print("copied", f)
 NOTES = [
-    "bench.py --steps 50 --warmup 5 --no-cpu --no-pipelined --no-ladder --no-mcmc-large --no-api --mcmc-iters 200 under rocprofv3 --pmc <counters> --kernel-trace, "
+    "bench.py --full --steps 50 --warmup 5 --no-cpu --no-pipelined --no-ladder --no-mcmc-large --no-api --mcmc-iters 200 under rocprofv3 --pmc <counters> --kernel-trace, "
     "one counter set per run (tools/profile_round.sh)",
     "FETCH_SIZE/WRITE_SIZE are KiB; gfx950 FETCH_SIZE may under-count wide coalesced reads by 2x "
     "(MI355X_MICROARCH.md): upper bound on HBM reads = 2*FETCH_SIZE",
