@@ -121,6 +121,20 @@ def _load():
     L.carma_mle_batched.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
                                     C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.carma_mle_batched.restype = C.c_int
+    L.carma_mctx_create.restype = C.c_void_p
+    L.carma_mctx_create.argtypes = [_dp, _dp, _dp, C.POINTER(C.c_long), C.c_int, C.c_int, C.c_int, _dp, C.c_int]
+    L.carma_mctx_destroy.argtypes = [C.c_void_p]
+    L.carma_mctx_destroy.restype = None
+    L.carma_mctx_nseries.argtypes = [C.c_void_p]
+    L.carma_mctx_dim.argtypes = [C.c_void_p]
+    L.carma_mctx_n.argtypes = [C.c_void_p, C.c_int]
+    L.carma_mctx_get_data.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
+    L.carma_mctx_get_prior.argtypes = [C.c_void_p, C.c_int, _dp]
+    L.carma_mlogdensity_batch.argtypes = [C.c_void_p, _dp, _ip, C.c_int, C.c_int, _dp]
+    L.carma_mlogdensity_kernel_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    L.carma_mle_batched_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                       C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]
     L.carma_logprior.argtypes = [C.c_void_p, _dp]
     L.carma_logprior.restype = C.c_double
     L.carma_kfilter_batch_carma.argtypes = [_dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp,
@@ -192,7 +206,9 @@ EXPORTS = [
     "carma_pt_stats", "carma_pt_iterations_done", "carma_comm_unique_id", "carma_comm_create", "carma_comm_destroy",
     "carma_comm_rank", "carma_comm_size", "carma_pt_iterate_sharded", "carma_pt_sample_sharded", "carma_pt_boundary_stats",
     "carma_pt_boundary_check", "carma_pt_sweep", "carma_pt_kernel_in_use", "carma_pt_row_pipeline", "carma_pt_debug_draws", "carma_pt_get_factor",
-    "carma_pt_set_factor", "carma_tune_set",
+    "carma_pt_set_factor", "carma_tune_set", "carma_mctx_create", "carma_mctx_destroy", "carma_mctx_nseries", "carma_mctx_dim",
+    "carma_mctx_n", "carma_mctx_get_data", "carma_mctx_get_prior", "carma_mlogdensity_batch", "carma_mlogdensity_kernel_name",
+    "carma_mle_batched_ms",
 ]
 
 
@@ -579,6 +595,116 @@ def kfilter_carma_batch(time, y, yerr, sigsqr, omega, ma, mu=None, device=None):
     mean = mean.reshape(-1)[:B * m].reshape(B, m)
     var = var.reshape(-1)[:B * m].reshape(B, m)
     return mean, var, sing.astype(bool)
+
+
+class MultiContext:
+    """Owns one carma_mctx: MANY series of one order (p, q) resident in HBM, evaluated in shared launches.
+
+    series: a list of (t, y, yerr); each is prepared as Context prepares one (sort, dedup, prior bounds).  max_stdev: None
+    (10 sqrt(var(y, ddof=1)) per series, as Context), a number for all series, or one value per series."""
+
+    def __init__(self, series, p, q=0, max_stdev=None, device=None):
+        series = list(series)
+        if not series:
+            raise ValueError("MultiContext needs at least one series")
+        ts, ys, es = [], [], []
+        for s, item in enumerate(series):
+            if len(item) != 3:
+                raise ValueError("series %d: expected (t, y, yerr)" % s)
+            t, y, e = (as_f64(a).ravel() for a in item)
+            if not (t.size == y.size == e.size):
+                raise ValueError("series %d: time, y, yerr must have the same length" % s)
+            ts.append(t)
+            ys.append(y)
+            es.append(e)
+        S = len(series)
+        if max_stdev is None:
+            ms = np.array([10.0 * np.sqrt(np.var(y, ddof=1)) if y.size > 1 else 0.0 for y in ys])
+        else:
+            ms = np.broadcast_to(as_f64(max_stdev), (S,)).copy()
+        offsets = np.zeros(S + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([t.size for t in ts])
+        t_all, y_all, e_all = (as_f64(np.concatenate(a)) for a in (ts, ys, es))
+        self.device = default_device() if device is None else int(device)
+        self._h = lib.carma_mctx_create(ptr(t_all), ptr(y_all), ptr(e_all), offsets.ctypes.data_as(C.POINTER(C.c_long)), S,
+                                        int(p), int(q), ptr(ms), self.device)
+        if not self._h:
+            msg = "carma_mctx_create failed: " + last_error()
+            if "no HIP device" in msg:
+                raise CarmaDeviceError(msg)
+            raise ValueError(msg)
+        self.p, self.q = int(p), int(q)
+        self.nseries = lib.carma_mctx_nseries(self._h)
+        self.d = lib.carma_mctx_dim(self._h)
+        self.n = np.array([lib.carma_mctx_n(self._h, s) for s in range(self.nseries)], dtype=np.int64)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.carma_mctx_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def data(self, s):
+        n = int(self.n[s])
+        t, y, e = np.empty(n), np.empty(n), np.empty(n)
+        check(lib.carma_mctx_get_data(self._h, int(s), ptr(t), ptr(y), ptr(e)), "carma_mctx_get_data")
+        return t, y, e
+
+    def prior(self, s):
+        out = np.empty(3)
+        check(lib.carma_mctx_get_prior(self._h, int(s), ptr(out)), "carma_mctx_get_prior")
+        return tuple(out)
+
+    def _which(self, which, B):
+        w = np.ascontiguousarray(np.broadcast_to(np.asarray(which, dtype=np.int64), (B,)))
+        if B and (w.min() < 0 or w.max() >= self.nseries):
+            raise ValueError("series index out of range [0, %d)" % self.nseries)
+        return np.ascontiguousarray(w, dtype=np.int32)
+
+    def logdensity(self, thetas, which, ignore_prior=False):
+        """Log-density of thetas[i] on series which[i] (which: one index per row, or one for all), one launch."""
+        thetas = as_f64(thetas)
+        one = thetas.ndim == 1
+        thetas = thetas.reshape(-1, self.d)
+        B = thetas.shape[0]
+        w = self._which(which, B)
+        out = np.empty(B)
+        check(lib.carma_mlogdensity_batch(self._h, ptr(thetas), w.ctypes.data_as(_ip), B, int(bool(ignore_prior)), ptr(out)),
+              "carma_mlogdensity_batch")
+        return float(out[0]) if one else out
+
+    def kernel_name(self):
+        buf = C.create_string_buffer(128)
+        check(lib.carma_mlogdensity_kernel_name(self._h, buf, 128), "carma_mlogdensity_kernel_name")
+        return buf.value.decode()
+
+    def mle_batched(self, x0, which, lo, hi, maxiter=2000, mem=8, ftol=2.220446049250313e-09, gtol=1e-5, fd_step=1e-6,
+                    ignore_prior=True):
+        """carma_mle_batched_ms: Context.mle_batched with start i on series which[i] and its own box lo[i], hi[i] ([B, d],
+        non-finite = unbounded; or [d] for every start).  Returns (x [B, d], fun [B], nit [B], nfev [B], status [B])."""
+        x0 = np.ascontiguousarray(np.atleast_2d(np.asarray(x0, dtype=np.float64)))
+        B, d = x0.shape
+        if d != self.d:
+            raise ValueError("x0 must be [B, %d]" % self.d)
+        w = self._which(which, B)
+        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.float64), (B, d)))
+        hi = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.float64), (B, d)))
+        x, fun = np.empty((B, d)), np.empty(B)
+        nit, nfev, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        check(lib.carma_mle_batched_ms(self._h, ptr(x0), w.ctypes.data_as(C.c_void_p), B, ptr(lo), ptr(hi), int(maxiter), int(mem),
+                                       float(ftol), float(gtol), float(fd_step), 1 if ignore_prior else 0, ptr(x), ptr(fun),
+                                       nit.ctypes.data_as(C.c_void_p), nfev.ctypes.data_as(C.c_void_p),
+                                       status.ctypes.data_as(C.c_void_p)), "carma_mle_batched_ms")
+        return x, fun, nit, nfev, status
 
 
 def kfilter_car1(time, y, yerr, sigsqr, omega, device=None):

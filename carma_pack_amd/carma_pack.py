@@ -15,7 +15,7 @@ from scipy.optimize import minimize
 
 from . import _carmcmc as carmcmcLib
 
-__all__ = ["CarmaModel", "CarmaSample", "Car1Sample", "MCMCSample", "get_ar_roots", "power_spectrum",
+__all__ = ["CarmaModel", "CarmaModelSet", "CarmaSample", "Car1Sample", "MCMCSample", "get_ar_roots", "power_spectrum",
            "carma_variance", "car1_process", "carma_process", "carma_process_batch", "car1_process_batch"]
 
 
@@ -615,3 +615,121 @@ class CarmaModel(object):
             if a < best_aicc:
                 best, best_aicc, self.p, self.q = mle, a, p, q
         return best, pqlist, AICc
+
+
+# ------------------------------------------------------------------------------------------------
+class CarmaModelSet(object):
+    """Many light curves, each fitted on its own (no counterpart in the reference, which wraps one series per CarmaModel):
+    get_mle / choose_order of every series with all series' starts optimised together in ONE lock-step run on a
+    multi-series context (MultiContext, carma_mle_batched_ms).  series: a list of (time, y, ysig); each becomes a
+    CarmaModel (self.models), so its data are sorted and deduplicated as CarmaModel does."""
+
+    def __init__(self, series, p=1, q=0):
+        series = list(series)
+        if not series:
+            raise ValueError("CarmaModelSet needs at least one series")
+        if not p > q:
+            raise ValueError("Order of AR polynomial, p, must be larger than order of MA polynomial, q.")
+        self.models = []
+        for s, item in enumerate(series):
+            if len(item) != 3:
+                raise ValueError("series %d: expected (time, y, ysig)" % s)
+            t, y, e = (np.asarray(a, dtype=float).ravel() for a in item)
+            if not (t.size == y.size == e.size):
+                raise ValueError("series %d: time, y, ysig must have the same length" % s)
+            if np.unique(t).size < 2:
+                raise ValueError("series %d has fewer than 2 distinct times" % s)
+            self.models.append(CarmaModel(t, y, e, p=p, q=q))
+        self.p, self.q = p, q
+        self.nseries = len(self.models)
+        self._mctx = {}
+        self.timing = {}
+
+    def context(self, p, q):
+        """The MultiContext of order (p, q) over every series (created once; the prior bound max_stdev of the samplers that
+        get_mle's objective carries, carmcmc.cpp:35-40,85-89)."""
+        key = (int(p), int(q))
+        if key not in self._mctx:
+            from ._lib import MultiContext
+            self._mctx[key] = MultiContext([(m.time, m.y, m.ysig) for m in self.models], key[0], key[1],
+                                           max_stdev=[carmcmcLib._pop_max_stdev(m.y) for m in self.models])
+        return self._mctx[key]
+
+    def _which(self, which, B):
+        w = np.broadcast_to(np.asarray(which, dtype=np.int64), (B,))
+        if B and (w.min() < 0 or w.max() >= self.nseries):
+            raise ValueError("series index out of range [0, %d)" % self.nseries)
+        return w
+
+    def loglik(self, theta, which):
+        """-f of get_mle's objective: the log-density with the prior bounds of the MLE (SetMLE(true) for p > 1) of theta[i]
+        on series which[i], every row in one launch."""
+        theta = np.asarray(theta, dtype=float)
+        rows = np.atleast_2d(theta)
+        w = self._which(which, rows.shape[0])
+        out = self.context(self.p, self.q).logdensity(rows, w, ignore_prior=self.p > 1)
+        return float(out[0]) if theta.ndim == 1 else out
+
+    def get_mle(self, p, q, ntrials=100, seed=None, starts=None, return_all=False):
+        """CarmaModel.get_mle of every series.  starts None: each series' starts drawn exactly as CarmaModel.get_mle draws
+        them (a short tempered sampler run per series, same seed), else an array [S, ntrials, d].  All S x ntrials starts
+        are then optimised in ONE lock-step run.  Returns a list of S BatchResult (return_all: S lists of ntrials).
+        self.timing holds the seconds spent drawing starts and optimising."""
+        import time as _time
+        if not p > q:
+            raise ValueError("Order of AR polynomial, p, must be larger than order of MA polynomial, q.")
+        S = self.nseries
+        t0 = _time.perf_counter()
+        if starts is None:
+            starts = np.stack([m._mle_problem(p, q, ntrials, seed)[1] for m in self.models])
+        else:
+            starts = np.asarray(starts, dtype=float)
+            d = 4 if p == 1 else 3 + p + q
+            if starts.ndim != 3 or starts.shape[0] != S or starts.shape[2] != d:
+                raise ValueError("starts must be [%d, ntrials, %d], got %r" % (S, d, starts.shape))
+        t1 = _time.perf_counter()
+        nt, d = starts.shape[1], starts.shape[2]
+        lo, hi = np.empty((S, d)), np.empty((S, d))
+        for s, m in enumerate(self.models):
+            bnds = m._mle_bounds(p, q)
+            lo[s] = [-np.inf if b[0] is None else b[0] for b in bnds]
+            hi[s] = [np.inf if b[1] is None else b[1] for b in bnds]
+        which = np.repeat(np.arange(S), nt)
+        xs, fs, nits, nfevs, sts = self.context(p, q).mle_batched(starts.reshape(S * nt, d), which, lo[which], hi[which],
+                                                                  ignore_prior=p > 1)
+        t2 = _time.perf_counter()
+        self.timing = {"starts_s": t1 - t0, "optimise_s": t2 - t1}
+        out = []
+        for s in range(S):
+            res = [BatchResult(xs[i].copy(), float(fs[i]), int(nits[i]), int(nfevs[i]), int(sts[i]) < 2, STATUS_TEXT[int(sts[i])])
+                   for i in range(s * nt, (s + 1) * nt)]
+            if return_all:
+                out.append(res)
+            else:
+                res = [r for r in res if np.isfinite(r.fun) and r.fun < 1e299] or res
+                out.append(min(res, key=lambda r: r.fun))
+        return out
+
+    def choose_order(self, pmax, qmax=None, pqlist=None, ntrials=100, seed=None):
+        """CarmaModel.choose_order of every series: one get_mle over the whole set per order, AICc with each series' own n.
+        Returns a list of S (best, pqlist, AICc) triples; self.orders holds each series' chosen (p, q)."""
+        if pmax < 1:
+            raise ValueError("Order of AR polynomial must be at least 1.")
+        if qmax is None:
+            qmax = pmax - 1
+        if pqlist is None:
+            pqlist = [(p, q) for p in range(1, pmax + 1) for q in range(min(p, qmax + 1))]
+        MLEs = [self.get_mle(p, q, ntrials=ntrials, seed=seed) for p, q in pqlist]
+        out, self.orders = [], []
+        for s, m in enumerate(self.models):
+            n = m.time.size
+            AICc, best, best_aicc, order = [], MLEs[0][s], 1e300, pqlist[0]
+            for mles, (p, q) in zip(MLEs, pqlist):
+                k = 2 + p + q
+                a = 2.0 * k + 2.0 * mles[s].fun + 2.0 * k * (k + 1.0) / (n - k - 1.0)
+                AICc.append(a)
+                if a < best_aicc:
+                    best, best_aicc, order = mles[s], a, (p, q)
+            out.append((best, pqlist, AICc))
+            self.orders.append(order)
+        return out

@@ -186,6 +186,24 @@ std::vector<double> pack_series(const std::vector<double>& t, const std::vector<
     return s;
 }
 
+// SetPrior (src/include/carpack.hpp:201-207) on a sorted, deduplicated series
+void set_prior_bounds(Prior& pr, const double* t, long n, double max_stdev)
+{
+    pr.max_stdev = max_stdev;
+    double dtmin = std::numeric_limits<double>::infinity();
+    for (long i = 1; i < n; i++) dtmin = std::min(dtmin, t[i] - t[i - 1]);
+    pr.max_freq = 1.0 / dtmin;
+    pr.min_freq = 1.0 / (*std::max_element(t, t + n) - *std::min_element(t, t + n));
+}
+
+// SERIES_REPEATED_DT of packed records (pack_series): >= 25 % of the time steps equal their predecessor
+bool series_repeated_dt(const double* packed, long n)
+{
+    long rep = 0;
+    for (long k = 2; k < n; k++) rep += (packed[4 * (size_t)k] == packed[4 * (size_t)(k - 1)]);
+    return n > 8 && 4 * rep >= n;
+}
+
 // AR roots as the kernels expect them: complex-conjugate pairs adjacent (negative imaginary part first), real roots
 // after them -- the order CARp::ARRoots emits (src/carpack.cpp:137-172).  The result of the filter does not depend on
 // the order of the roots, so roots handed over in another order (carma_pack.py's get_ar_roots puts a real root wherever
@@ -306,11 +324,7 @@ carma_ctx* carma_ctx_create(const double* time, const double* y, const double* y
     c->pr.measerr_dof = 50.0;   // src/include/carpack.hpp:63
     carma_ctx_set_prior(reinterpret_cast<carma_ctx*>(c), max_stdev);
     std::vector<double> s = pack_series(c->t, c->y, c->yerr);
-    {
-        int rep = 0;
-        for (int k = 2; k < c->n; k++) rep += (s[4 * (size_t)k] == s[4 * (size_t)(k - 1)]);
-        c->repeated_dt = c->n > 8 && 4 * rep >= c->n;
-    }
+    c->repeated_dt = series_repeated_dt(s.data(), c->n);
     if (p >= 2) {
         // SERIES_WINDOW_OK (carma_types.h): spans of 16 - p consecutive data against the shortest window the prior admits
         const int ND = 16 - p;
@@ -380,12 +394,7 @@ int carma_ctx_set_prior(carma_ctx* h, double max_stdev)
 {
     if (!h) return CARMA_EINVAL;
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    // SetPrior (src/include/carpack.hpp:201-207)
-    c->pr.max_stdev = max_stdev;
-    double dtmin = std::numeric_limits<double>::infinity();
-    for (int i = 1; i < c->n; i++) dtmin = std::min(dtmin, c->t[i] - c->t[i - 1]);
-    c->pr.max_freq = 1.0 / dtmin;
-    c->pr.min_freq = 1.0 / (*std::max_element(c->t.begin(), c->t.end()) - *std::min_element(c->t.begin(), c->t.end()));
+    set_prior_bounds(c->pr, c->t.data(), c->n, max_stdev);
     return CARMA_OK;
 }
 

@@ -84,6 +84,11 @@ struct Ctx {
 };
 
 void set_error(const char* fmt, ...);
+// series preparation shared by carma_ctx_create and carma_mctx_create (carma_capi.hip)
+void sort_dedup(std::vector<double>& t, std::vector<double>& y, std::vector<double>& e);
+std::vector<double> pack_series(const std::vector<double>& t, const std::vector<double>& y, const std::vector<double>& e);
+void set_prior_bounds(Prior& pr, const double* t, long n, double max_stdev);
+bool series_repeated_dt(const double* packed, long n);
 int hip_fail(hipError_t e, const char* what);
 int select_device(int device);
 void pt_state_free(Ctx* c);

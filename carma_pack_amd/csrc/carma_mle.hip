@@ -28,12 +28,14 @@ constexpr double BIG = 1e300;
 constexpr int LS_K = 8;          // step lengths t, t/2, ... evaluated per line-search launch
 constexpr int PATIENCE = 3;
 
-struct Eval {
+// An evaluator: operator()(pts, owner, npts) sets out[k] = f(pts[k]) = -LogDensity (non-finite -> BIG); owner[k] is the start
+// point k belongs to, filled by the loop only where PER_START is true.
+struct Eval {                    // one series (carma_ctx)
+    static constexpr bool PER_START = false;
     carma_ctx* h;
-    int d, ignore_prior;
+    int ignore_prior;
     std::vector<double> out;
-    // f(pts) = -LogDensity(pts); non-finite -> BIG
-    int operator()(const std::vector<double>& pts, int npts)
+    int operator()(const std::vector<double>& pts, const std::vector<int>&, int npts)
     {
         out.resize((size_t)npts);
         if (npts == 0) return CARMA_OK;
@@ -47,33 +49,46 @@ struct Eval {
     }
 };
 
-}  // namespace
+struct EvalMs {                  // many series (carma_mctx): every point on its start's series
+    static constexpr bool PER_START = true;
+    carma_mctx* h;
+    const int* series;           // [B] series of each start
+    int ignore_prior;
+    std::vector<double> out;
+    std::vector<int> ser;
+    int operator()(const std::vector<double>& pts, const std::vector<int>& owner, int npts)
+    {
+        out.resize((size_t)npts);
+        if (npts == 0) return CARMA_OK;
+        ser.resize((size_t)npts);
+        for (int i = 0; i < npts; i++) ser[i] = series[owner[i]];
+        const int rc = carma_mlogdensity_batch(h, pts.data(), ser.data(), npts, ignore_prior, out.data());
+        if (rc != CARMA_OK) return rc;
+        for (int i = 0; i < npts; i++) {
+            const double f = -out[i];
+            out[i] = std::isfinite(f) ? f : BIG;
+        }
+        return CARMA_OK;
+    }
+};
 
-extern "C" int carma_mle_batched(carma_ctx* h, const double* x0, int B, const double* lo_in, const double* hi_in, int maxiter,
-                                 int mem, double ftol, double gtol, double fd_step, int ignore_prior, double* x_out,
-                                 double* fun_out, int* nit_out, int* nfev_out, int* status_out)
+// The lock-step loop.  lo / hi: the box of start b at lo + b * bstride (bstride = 0: one box for every start; no NULLs,
+// unbounded = +-inf).
+template <class EvalT>
+int mle_loop(EvalT& fun, int d, const double* x0, int B, const double* lo_all, const double* hi_all, size_t bstride, int maxiter,
+             int mem, double ftol, double gtol, double fd_step, double* x_out, double* fun_out, int* nit_out, int* nfev_out,
+             int* status_out)
 {
-    if (!h || !x0 || B < 0 || !x_out || !fun_out || mem < 1 || mem > 64 || maxiter < 0) {
-        set_error("carma_mle_batched: bad argument");
-        return CARMA_EINVAL;
-    }
-    const int d = carma_ctx_dim(h);
     const int m = mem;
-    const double inf = std::numeric_limits<double>::infinity();
-    std::vector<double> lo(d, -inf), hi(d, inf);
-    for (int j = 0; j < d; j++) {
-        if (lo_in && std::isfinite(lo_in[j])) lo[j] = lo_in[j];
-        if (hi_in && std::isfinite(hi_in[j])) hi[j] = hi_in[j];
-    }
-    auto project = [&](double v, int j) { return std::min(std::max(v, lo[j]), hi[j]); };
-    Eval fun{h, d, ignore_prior, {}};
+    auto project = [&](double v, int b, int j) { return std::min(std::max(v, lo_all[b * bstride + j]), hi_all[b * bstride + j]); };
+    std::vector<int> owner;
 
     std::vector<double> x((size_t)B * d), f(B), g((size_t)B * d);
     std::vector<int> nfev(B, 0), nit(B, 0), nhist(B, 0), nsmall(B, 0), status(B, 2);   // 2 = maximum number of iterations
     std::vector<char> active(B, 1), restarted(B, 0);
     std::vector<double> S((size_t)B * m * d, 0.0), Y((size_t)B * m * d, 0.0);
     for (int b = 0; b < B; b++)
-        for (int j = 0; j < d; j++) x[(size_t)b * d + j] = project(x0[(size_t)b * d + j], j);
+        for (int j = 0; j < d; j++) x[(size_t)b * d + j] = project(x0[(size_t)b * d + j], b, j);
 
     // central differences (one-sided at a bound) of the starts listed in `who` at the points xs: fills fo / go
     std::vector<double> pts, up, dn;
@@ -83,7 +98,13 @@ extern "C" int carma_mle_batched(carma_ctx* h, const double* x0, int B, const do
         pts.resize((size_t)n * w * d);
         up.resize((size_t)n * d);
         dn.resize((size_t)n * d);
+        if constexpr (EvalT::PER_START) {
+            owner.resize((size_t)n * w);
+            for (int i = 0; i < n; i++) std::fill(owner.begin() + (size_t)i * w, owner.begin() + (size_t)(i + 1) * w, who[i]);
+        }
         for (int i = 0; i < n; i++) {
+            const double* lo = lo_all + who[i] * bstride;
+            const double* hi = hi_all + who[i] * bstride;
             const double* xi = &xs[(size_t)i * d];
             double* p = &pts[(size_t)i * w * d];
             for (int k = 0; k < w; k++) std::memcpy(p + (size_t)k * d, xi, sizeof(double) * d);
@@ -95,7 +116,7 @@ extern "C" int carma_mle_batched(carma_ctx* h, const double* x0, int B, const do
                 p[(size_t)(1 + d + j) * d + j] = dn[(size_t)i * d + j];
             }
         }
-        const int rc = fun(pts, n * w);
+        const int rc = fun(pts, owner, n * w);
         if (rc != CARMA_OK) return rc;
         fo.resize(n);
         go.resize((size_t)n * d);
@@ -131,6 +152,8 @@ extern "C" int carma_mle_batched(carma_ctx* h, const double* x0, int B, const do
         idx.clear();
         for (int b = 0; b < B; b++) {
             if (!active[b]) continue;
+            const double* lo = lo_all + b * bstride;
+            const double* hi = hi_all + b * bstride;
             double pgmax = 0.0;
             for (int j = 0; j < d; j++) {
                 const double xv = x[(size_t)b * d + j], gv = g[(size_t)b * d + j];
@@ -155,6 +178,8 @@ extern "C" int carma_mle_batched(carma_ctx* h, const double* x0, int B, const do
         std::vector<double> q(d), alpha(m), r(d);
         for (int i = 0; i < na; i++) {
             const int b = idx[i];
+            const double* lo = lo_all + b * bstride;
+            const double* hi = hi_all + b * bstride;
             const double* xb = &x[(size_t)b * d];
             const double* gb = &g[(size_t)b * d];
             double* pgi = &pg[(size_t)i * d];
@@ -230,13 +255,20 @@ extern "C" int carma_mle_batched(carma_ctx* h, const double* x0, int B, const do
             cand.resize((size_t)nn * wl * d);
             up.resize((size_t)nn * KS * d);
             dn.resize((size_t)nn * KS * d);
+            if constexpr (EvalT::PER_START) {
+                owner.resize((size_t)nn * wl);
+                for (int a = 0; a < nn; a++)
+                    std::fill(owner.begin() + (size_t)a * wl, owner.begin() + (size_t)(a + 1) * wl, idx[need[a]]);
+            }
             for (int a = 0; a < nn; a++) {
                 const int i = need[a], b = idx[i];
+                const double* lo = lo_all + b * bstride;
+                const double* hi = hi_all + b * bstride;
                 double* ca = &cand[(size_t)a * wl * d];
                 double tk = tstep[i];
                 for (int k = 0; k < LS_K; k++, tk *= 0.5)
                     for (int j = 0; j < d; j++)
-                        ca[(size_t)k * d + j] = project(x[(size_t)b * d + j] + tk * dir[(size_t)i * d + j], j);
+                        ca[(size_t)k * d + j] = project(x[(size_t)b * d + j] + tk * dir[(size_t)i * d + j], b, j);
                 for (int c = 0; c < KS; c++) {                     // the stencil of f_and_g around candidate c
                     const double* xc = ca + (size_t)c * d;
                     double* st = ca + (size_t)(LS_K + 2 * d * c) * d;
@@ -252,7 +284,7 @@ extern "C" int carma_mle_batched(carma_ctx* h, const double* x0, int B, const do
                     }
                 }
             }
-            const int rc = fun(cand, nn * wl);
+            const int rc = fun(cand, owner, nn * wl);
             if (rc != CARMA_OK) return rc;
             for (int a = 0; a < nn; a++) {
                 const int i = need[a], b = idx[i];
@@ -379,4 +411,56 @@ extern "C" int carma_mle_batched(carma_ctx* h, const double* x0, int B, const do
         if (status_out) status_out[b] = status[b];
     }
     return CARMA_OK;
+}
+
+// box of every start: NULL or non-finite entries = unbounded
+void fill_box(const double* in, size_t count, double dflt, std::vector<double>& out)
+{
+    out.assign(count, dflt);
+    for (size_t k = 0; k < count; k++)
+        if (in && std::isfinite(in[k])) out[k] = in[k];
+}
+
+}  // namespace
+
+extern "C" int carma_mle_batched(carma_ctx* h, const double* x0, int B, const double* lo_in, const double* hi_in, int maxiter,
+                                 int mem, double ftol, double gtol, double fd_step, int ignore_prior, double* x_out,
+                                 double* fun_out, int* nit_out, int* nfev_out, int* status_out)
+{
+    if (!h || !x0 || B < 0 || !x_out || !fun_out || mem < 1 || mem > 64 || maxiter < 0) {
+        set_error("carma_mle_batched: bad argument");
+        return CARMA_EINVAL;
+    }
+    const int d = carma_ctx_dim(h);
+    const double inf = std::numeric_limits<double>::infinity();
+    std::vector<double> lo, hi;
+    fill_box(lo_in, d, -inf, lo);
+    fill_box(hi_in, d, inf, hi);
+    Eval fun{h, ignore_prior, {}};
+    return mle_loop(fun, d, x0, B, lo.data(), hi.data(), 0, maxiter, mem, ftol, gtol, fd_step, x_out, fun_out, nit_out, nfev_out,
+                    status_out);
+}
+
+extern "C" int carma_mle_batched_ms(carma_mctx* h, const double* x0, const int* series, int B, const double* lo_in,
+                                    const double* hi_in, int maxiter, int mem, double ftol, double gtol, double fd_step,
+                                    int ignore_prior, double* x_out, double* fun_out, int* nit_out, int* nfev_out, int* status_out)
+{
+    if (!h || B < 0 || (B > 0 && (!x0 || !series || !x_out || !fun_out)) || mem < 1 || mem > 64 || maxiter < 0) {
+        set_error("carma_mle_batched_ms: bad argument");
+        return CARMA_EINVAL;
+    }
+    const int S = carma_mctx_nseries(h);
+    for (int i = 0; i < B; i++)
+        if (series[i] < 0 || series[i] >= S) {
+            set_error("carma_mle_batched_ms: series[%d] = %d out of range (nseries = %d)", i, series[i], S);
+            return CARMA_EINVAL;
+        }
+    const int d = carma_mctx_dim(h);
+    const double inf = std::numeric_limits<double>::infinity();
+    std::vector<double> lo, hi;
+    fill_box(lo_in, (size_t)B * d, -inf, lo);
+    fill_box(hi_in, (size_t)B * d, inf, hi);
+    EvalMs fun{h, series, ignore_prior, {}, {}};
+    return mle_loop(fun, d, x0, B, lo.data(), hi.data(), (size_t)d, maxiter, mem, ftol, gtol, fd_step, x_out, fun_out, nit_out,
+                    nfev_out, status_out);
 }

@@ -1,0 +1,387 @@
+// carma_mseries.hip -- MANY series in one launch: the one-evaluation-per-lane log-density kernels with the series chosen per
+// wave from a table, the launch plan that builds that table, and the multi-series context of the C ABI (carma_mctx_*).
+//
+// A survey fits thousands of light curves, each on its own; a launch per series leaves most of the chip idle (one series
+// rarely supplies the ~25 000 evaluations the lane kernel needs to fill 256 CUs).  Here all series of a set live in ONE
+// buffer in HBM and a launch carries evaluations of any of them:
+//   - one wave per workgroup, as k_logdens_carma_lane; wave w works on series wave_series[w] -- an index that derives from
+//     blockIdx.x alone, so the series' offset, length and prior bounds are wave-uniform and come in with scalar loads, and so
+//     do the series records in the filter loop, exactly as in the single-series kernel;
+//   - lane l of wave w evaluates parameter vector eval_idx[64 w + l] and writes out[eval_idx[64 w + l]] (the caller's order);
+//     pad lanes (eval_idx = -1) compute a copy of the wave's first evaluation and write nothing;
+//   - the filter is logdensity_lane / logdensity_car1 unchanged, and REPDT is decided per series as carma_ctx_create decides
+//     it: a series gives the same bits as the single-series lane kernel on it.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <numeric>
+#include <vector>
+
+#include "../../include/carma_mi355.h"
+#include "grp_device.h"
+#include "carma_core.h"
+#include "carma_host.h"
+#include "carma_lane.h"
+
+namespace carma {
+
+template <int P, bool REPDT>
+__global__ __launch_bounds__(64) void k_logdens_carma_lane_ms(const double* __restrict__ theta, int d, int q,
+                                                             const double4* __restrict__ records, const long* __restrict__ off,
+                                                             const int* __restrict__ nser, const Prior* __restrict__ prs,
+                                                             const int* __restrict__ wave_series, const int* __restrict__ eval_idx,
+                                                             int ignore_prior, double* __restrict__ out)
+{
+    __shared__ double s_tab[MATH_TAB_N];                     // tables of the table-based exp / sincos (carma_math.h)
+    math_tab_fill(s_tab);
+    __syncthreads();
+    const int s = wave_series[blockIdx.x];                   // wave-uniform: scalar loads of the series' record
+    const double4* series = records + off[s];
+    const int n = nser[s];
+    const Prior pr = prs[s];
+    const int* ew = eval_idx + (long)blockIdx.x * 64;
+    int e = ew[threadIdx.x];
+    const bool live = e >= 0;
+    if (!live) e = ew[0];                                    // (lane 0 of a wave is always live)
+    const double ll = logdensity_lane<P, REPDT>(theta + (long)e * d, q, series, n, pr, ignore_prior, s_tab);
+    if (live) out[e] = ll;
+}
+
+__global__ __launch_bounds__(64) void k_logdens_car1_ms(const double* __restrict__ theta, const double4* __restrict__ records,
+                                                        const long* __restrict__ off, const int* __restrict__ nser,
+                                                        const Prior* __restrict__ prs, const int* __restrict__ wave_series,
+                                                        const int* __restrict__ eval_idx, double* __restrict__ out)
+{
+    const int s = wave_series[blockIdx.x];
+    const double4* series = records + off[s];
+    const int n = nser[s];
+    const Prior pr = prs[s];
+    const int* ew = eval_idx + (long)blockIdx.x * 64;
+    int e = ew[threadIdx.x];
+    const bool live = e >= 0;
+    if (!live) e = ew[0];
+    const double ll = logdensity_car1(theta + 4L * e, series, n, pr);
+    if (live) out[e] = ll;
+}
+
+// nwaves waves of the table (wave_series[nwaves], eval_idx[64 nwaves]) in one launch
+static hipError_t launch_logdens_ms(int p, bool repdt, const double* theta, int d, int q, const double4* records, const long* off,
+                                    const int* nser, const Prior* prs, const int* wave_series, const int* eval_idx, long nwaves,
+                                    int ignore_prior, double* out, hipStream_t st)
+{
+    if (nwaves <= 0) return hipSuccess;
+    const dim3 grid((unsigned)nwaves), block(64);
+    if (p == 1) {
+        hipLaunchKernelGGL(k_logdens_car1_ms, grid, block, 0, st, theta, records, off, nser, prs, wave_series, eval_idx, out);
+        return hipGetLastError();
+    }
+    switch (p) {
+#define CARMA_MS(N)                                                                                                            \
+    case N:                                                                                                                    \
+        if (repdt)                                                                                                             \
+            hipLaunchKernelGGL((k_logdens_carma_lane_ms<N, true>), grid, block, 0, st, theta, d, q, records, off, nser, prs,   \
+                               wave_series, eval_idx, ignore_prior, out);                                                      \
+        else                                                                                                                   \
+            hipLaunchKernelGGL((k_logdens_carma_lane_ms<N, false>), grid, block, 0, st, theta, d, q, records, off, nser, prs,  \
+                               wave_series, eval_idx, ignore_prior, out);                                                      \
+        break;
+        CARMA_MS(2) CARMA_MS(3) CARMA_MS(4) CARMA_MS(5) CARMA_MS(6) CARMA_MS(7)
+#undef CARMA_MS
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// Multi-series context: the series of a set packed one after another in HBM, each as carma_ctx_create packs one
+struct Mctx {
+    int device = 0;
+    int p = 0, q = 0, d = 0, S = 0;
+    std::vector<long> hoff;           // [S + 1] start of series s in t / y / yerr (after sort/dedup)
+    std::vector<double> t, y, yerr;   // all series, sorted and deduplicated, concatenated
+    std::vector<long> off;            // [S] first record of series s in d_rec (a multiple of 2 records: 64-byte aligned)
+    std::vector<int> n;               // [S]
+    std::vector<Prior> pr;            // [S]
+    std::vector<char> repdt;          // [S] SERIES_REPEATED_DT of each series
+    double4* d_rec = nullptr;
+    long* d_off = nullptr;
+    int* d_n = nullptr;
+    Prior* d_pr = nullptr;
+    // per-call buffers, grown on demand: parameter vectors [cap_B][d], results [cap_B], plan [cap_W] + [cap_W][64]
+    double *d_theta = nullptr, *d_out = nullptr;
+    int *d_wser = nullptr, *d_eidx = nullptr;
+    char* h_stage = nullptr;          // pinned: the same four, in this order
+    long cap_B = 0, cap_W = 0;
+    hipStream_t stream = nullptr;
+    std::vector<int> cnt, first, order, wser_tmp;
+
+    size_t stage_bytes(long B, long W) const { return sizeof(double) * (size_t)B * (d + 1) + sizeof(int) * (size_t)W * 65; }
+    int ensure(long B, long W)
+    {
+        if (B <= cap_B && W <= cap_W) return CARMA_OK;
+        const long nB = std::max(std::max(B, cap_B), 1024L), nW = std::max(std::max(W, cap_W), 64L);
+        if (d_theta) (void)dev_free(d_theta);
+        if (d_out) (void)dev_free(d_out);
+        if (d_wser) (void)dev_free(d_wser);
+        if (d_eidx) (void)dev_free(d_eidx);
+        if (h_stage) (void)hipHostFree(h_stage);
+        d_theta = d_out = nullptr;
+        d_wser = d_eidx = nullptr;
+        h_stage = nullptr;
+        cap_B = cap_W = 0;
+        hipError_t e = dev_malloc(&d_theta, sizeof(double) * (size_t)nB * d);
+        if (e == hipSuccess) e = dev_malloc(&d_out, sizeof(double) * (size_t)nB);
+        if (e == hipSuccess) e = dev_malloc(&d_wser, sizeof(int) * (size_t)nW);
+        if (e == hipSuccess) e = dev_malloc(&d_eidx, sizeof(int) * (size_t)nW * 64);
+        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h_stage), stage_bytes(nB, nW), hipHostMallocDefault);
+        if (e != hipSuccess) return hip_fail(e, "carma_mlogdensity_batch: buffers");
+        cap_B = nB;
+        cap_W = nW;
+        return CARMA_OK;
+    }
+};
+
+}  // namespace carma
+
+using namespace carma;
+
+extern "C" {
+
+carma_mctx* carma_mctx_create(const double* time, const double* y, const double* yerr, const long* offsets, int nseries, int p,
+                              int q, const double* max_stdev, int device)
+{
+    if (!time || !y || !yerr || !offsets || nseries < 1) {
+        set_error("carma_mctx_create: need nseries >= 1 and non-null arrays (got nseries=%d)", nseries);
+        return nullptr;
+    }
+    if (p < 1 || p > CARMA_PMAX || q < 0 || (p == 1 && q != 0) || (p > 1 && q >= p)) {
+        set_error("carma_mctx_create: need 1 <= p <= %d and q < p (got p=%d q=%d)", CARMA_PMAX, p, q);
+        return nullptr;
+    }
+    if (offsets[0] != 0) {
+        set_error("carma_mctx_create: offsets[0] must be 0 (got %ld)", offsets[0]);
+        return nullptr;
+    }
+    for (int s = 0; s < nseries; s++) {
+        if (offsets[s + 1] < offsets[s]) {
+            set_error("carma_mctx_create: offsets must be non-decreasing (offsets[%d]=%ld > offsets[%d]=%ld)", s, offsets[s], s + 1,
+                      offsets[s + 1]);
+            return nullptr;
+        }
+        if (offsets[s + 1] - offsets[s] > 0x7fffffffL - P3L_PAD_RECORDS) {
+            set_error("carma_mctx_create: series %d is longer than an int can count", s);
+            return nullptr;
+        }
+    }
+    // every series prepared as carma_ctx_create prepares one (host only: all argument errors come before any device work)
+    Mctx* c = new Mctx();
+    c->device = device;
+    c->p = p;
+    c->q = q;
+    c->d = (p == 1) ? 4 : 3 + p + q;
+    c->S = nseries;
+    c->hoff.assign(nseries + 1, 0);
+    c->off.resize(nseries);
+    c->n.resize(nseries);
+    c->pr.resize(nseries);
+    c->repdt.resize(nseries);
+    std::vector<std::vector<double>> packed(nseries);
+    long rec_total = 0;
+    for (int s = 0; s < nseries; s++) {
+        const long a = offsets[s], b = offsets[s + 1];
+        std::vector<double> ts(time + a, time + b), ys(y + a, y + b), es(yerr + a, yerr + b);
+        sort_dedup(ts, ys, es);
+        const long ns = (long)ts.size();
+        if (ns < 2) {
+            set_error("carma_mctx_create: series %d has fewer than 2 distinct times", s);
+            delete c;
+            return nullptr;
+        }
+        double ms = 0.0;
+        if (max_stdev) {
+            ms = max_stdev[s];
+        } else {                                              // 10 sqrt(var(y, ddof=1)) of the series as given (Context's default)
+            double mean = 0.0, ss = 0.0;
+            for (long k = a; k < b; k++) mean += y[k];
+            mean /= (double)(b - a);
+            for (long k = a; k < b; k++) ss += (y[k] - mean) * (y[k] - mean);
+            ms = 10.0 * std::sqrt(ss / (double)(b - a - 1));
+        }
+        c->pr[s].measerr_dof = 50.0;   // src/include/carpack.hpp:63
+        set_prior_bounds(c->pr[s], ts.data(), ns, ms);
+        packed[s] = pack_series(ts, ys, es);
+        c->repdt[s] = series_repeated_dt(packed[s].data(), ns);
+        c->n[s] = (int)ns;
+        c->off[s] = rec_total;
+        rec_total += (ns + P3L_PAD_RECORDS + 1) / 2 * 2;     // records and pad records, the next series on a 64-byte boundary
+        c->hoff[s + 1] = c->hoff[s] + ns;
+        c->t.insert(c->t.end(), ts.begin(), ts.end());
+        c->y.insert(c->y.end(), ys.begin(), ys.end());
+        c->yerr.insert(c->yerr.end(), es.begin(), es.end());
+    }
+    if (select_device(device) != CARMA_OK) {
+        delete c;
+        return nullptr;
+    }
+    std::vector<double> rec((size_t)rec_total * 4, 0.0);
+    for (int s = 0; s < nseries; s++) {
+        const size_t nr = (size_t)c->n[s] + P3L_PAD_RECORDS;         // the records and pads of pack_series (its tail arrays stay out)
+        std::memcpy(&rec[(size_t)c->off[s] * 4], packed[s].data(), sizeof(double) * 4 * nr);
+        std::vector<double>().swap(packed[s]);
+    }
+    hipError_t e = dev_malloc(&c->d_rec, sizeof(double) * rec.size());
+    if (e == hipSuccess) e = hipMemcpy(c->d_rec, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = dev_malloc(&c->d_off, sizeof(long) * nseries);
+    if (e == hipSuccess) e = hipMemcpy(c->d_off, c->off.data(), sizeof(long) * nseries, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = dev_malloc(&c->d_n, sizeof(int) * nseries);
+    if (e == hipSuccess) e = hipMemcpy(c->d_n, c->n.data(), sizeof(int) * nseries, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = dev_malloc(&c->d_pr, sizeof(Prior) * nseries);
+    if (e == hipSuccess) e = hipMemcpy(c->d_pr, c->pr.data(), sizeof(Prior) * nseries, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+        hip_fail(e, "carma_mctx_create");
+        carma_mctx_destroy(reinterpret_cast<carma_mctx*>(c));
+        return nullptr;
+    }
+    return reinterpret_cast<carma_mctx*>(c);
+}
+
+void carma_mctx_destroy(carma_mctx* h)
+{
+    if (!h) return;
+    Mctx* c = reinterpret_cast<Mctx*>(h);
+    (void)hipSetDevice(c->device);
+    if (c->d_rec) (void)dev_free(c->d_rec);
+    if (c->d_off) (void)dev_free(c->d_off);
+    if (c->d_n) (void)dev_free(c->d_n);
+    if (c->d_pr) (void)dev_free(c->d_pr);
+    if (c->d_theta) (void)dev_free(c->d_theta);
+    if (c->d_out) (void)dev_free(c->d_out);
+    if (c->d_wser) (void)dev_free(c->d_wser);
+    if (c->d_eidx) (void)dev_free(c->d_eidx);
+    if (c->h_stage) (void)hipHostFree(c->h_stage);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+    delete c;
+}
+
+int carma_mctx_nseries(const carma_mctx* h) { return h ? reinterpret_cast<const Mctx*>(h)->S : CARMA_EINVAL; }
+int carma_mctx_dim(const carma_mctx* h) { return h ? reinterpret_cast<const Mctx*>(h)->d : CARMA_EINVAL; }
+
+int carma_mctx_n(const carma_mctx* h, int s)
+{
+    if (!h || s < 0 || s >= reinterpret_cast<const Mctx*>(h)->S) return CARMA_EINVAL;
+    return reinterpret_cast<const Mctx*>(h)->n[s];
+}
+
+int carma_mctx_get_data(const carma_mctx* h, int s, double* time, double* y, double* yerr)
+{
+    if (!h || s < 0 || s >= reinterpret_cast<const Mctx*>(h)->S) return CARMA_EINVAL;
+    const Mctx* c = reinterpret_cast<const Mctx*>(h);
+    const size_t a = (size_t)c->hoff[s], n = (size_t)c->n[s];
+    if (time) std::memcpy(time, c->t.data() + a, sizeof(double) * n);
+    if (y) std::memcpy(y, c->y.data() + a, sizeof(double) * n);
+    if (yerr) std::memcpy(yerr, c->yerr.data() + a, sizeof(double) * n);
+    return CARMA_OK;
+}
+
+int carma_mctx_get_prior(const carma_mctx* h, int s, double* out3)
+{
+    if (!h || !out3 || s < 0 || s >= reinterpret_cast<const Mctx*>(h)->S) return CARMA_EINVAL;
+    const Prior& pr = reinterpret_cast<const Mctx*>(h)->pr[s];
+    out3[0] = pr.max_stdev;
+    out3[1] = pr.max_freq;
+    out3[2] = pr.min_freq;
+    return CARMA_OK;
+}
+
+int carma_mlogdensity_batch(carma_mctx* h, const double* theta, const int* series, int B, int ignore_prior, double* out)
+{
+    if (!h || B < 0 || (B > 0 && (!theta || !series || !out))) {
+        set_error("carma_mlogdensity_batch: bad argument");
+        return CARMA_EINVAL;
+    }
+    if (B == 0) return CARMA_OK;
+    Mctx* c = reinterpret_cast<Mctx*>(h);
+    const int S = c->S, d = c->d;
+    // launch plan (host, O(B + S log S)): counting sort of the evaluations by series, waves of 64 per series, longest
+    // series first, the regular-cadence series (REPDT) in a launch of their own
+    c->cnt.assign(S, 0);
+    for (int i = 0; i < B; i++) {
+        const int s = series[i];
+        if (s < 0 || s >= S) {
+            set_error("carma_mlogdensity_batch: series[%d] = %d out of range (nseries = %d)", i, s, S);
+            return CARMA_EINVAL;
+        }
+        c->cnt[s]++;
+    }
+    c->first.assign(S + 1, 0);
+    for (int s = 0; s < S; s++) c->first[s + 1] = c->first[s] + c->cnt[s];
+    c->order.resize(B);
+    {
+        std::vector<int>& pos = c->wser_tmp;
+        pos.assign(c->first.begin(), c->first.end() - 1);
+        for (int i = 0; i < B; i++) c->order[pos[series[i]]++] = i;
+    }
+    std::vector<int> used;
+    used.reserve(S);
+    long W = 0;
+    for (int s = 0; s < S; s++)
+        if (c->cnt[s]) {
+            used.push_back(s);
+            W += (c->cnt[s] + 63) / 64;
+        }
+    std::stable_sort(used.begin(), used.end(), [&](int a, int b) {
+        if (c->repdt[a] != c->repdt[b]) return c->repdt[a] < c->repdt[b];
+        return c->n[a] > c->n[b];
+    });
+    hipError_t e = hipSetDevice(c->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    int rc = c->ensure(B, W);
+    if (rc != CARMA_OK) return rc;
+    double* h_th = reinterpret_cast<double*>(c->h_stage);
+    double* h_out = h_th + (size_t)c->cap_B * d;
+    int* h_wser = reinterpret_cast<int*>(h_out + c->cap_B);
+    int* h_eidx = h_wser + c->cap_W;
+    std::memcpy(h_th, theta, sizeof(double) * (size_t)B * d);
+    long w = 0, w_plain = 0;                                  // waves of the REPDT = false launch: the first w_plain
+    for (int s : used) {
+        if (!c->repdt[s]) w_plain += (c->cnt[s] + 63) / 64;
+        for (int k = c->first[s]; k < c->first[s + 1]; k += 64, w++) {
+            h_wser[w] = s;
+            int* ew = h_eidx + (size_t)w * 64;
+            const int m = std::min(64, c->first[s + 1] - k);
+            std::memcpy(ew, &c->order[k], sizeof(int) * m);
+            for (int l = m; l < 64; l++) ew[l] = -1;
+        }
+    }
+    hipStream_t st = c->stream;
+    e = hipMemcpyAsync(c->d_theta, h_th, sizeof(double) * (size_t)B * d, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->d_wser, h_wser, sizeof(int) * (size_t)W, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->d_eidx, h_eidx, sizeof(int) * (size_t)W * 64, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return hip_fail(e, "carma_mlogdensity_batch: H2D");
+    (void)hipGetLastError();   // HIP's last-error is sticky: drop anything left by earlier calls
+    const double4* rec = c->d_rec;
+    e = launch_logdens_ms(c->p, false, c->d_theta, d, c->q, rec, c->d_off, c->d_n, c->d_pr, c->d_wser, c->d_eidx, w_plain, ignore_prior,
+                          c->d_out, st);
+    if (e == hipSuccess)
+        e = launch_logdens_ms(c->p, true, c->d_theta, d, c->q, rec, c->d_off, c->d_n, c->d_pr, c->d_wser + w_plain,
+                              c->d_eidx + (size_t)w_plain * 64, W - w_plain, ignore_prior, c->d_out, st);
+    if (e != hipSuccess) return hip_fail(e, "carma_mlogdensity_batch: launch");
+    e = hipMemcpyAsync(h_out, c->d_out, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hip_fail(e, "carma_mlogdensity_batch: D2H");
+    std::memcpy(out, h_out, sizeof(double) * (size_t)B);
+    return CARMA_OK;
+}
+
+int carma_mlogdensity_kernel_name(const carma_mctx* h, char* buf, int len)
+{
+    if (!h || !buf || len < 1) return CARMA_EINVAL;
+    const Mctx* c = reinterpret_cast<const Mctx*>(h);
+    const int r = c->p == 1 ? snprintf(buf, len, "k_logdens_car1_ms") : snprintf(buf, len, "k_logdens_carma_lane_ms<%d>", c->p);
+    return r > 0 ? CARMA_OK : CARMA_EINVAL;
+}
+
+}  // extern "C"

@@ -108,6 +108,40 @@ int carma_logdensity_kernel_name(const carma_ctx* h, int B, char* buf, int len);
  * launch asks; afterwards only this call moves them (process-wide, thread-safe).  CARMA_EINVAL for an unknown name. */
 int carma_tune_set(const char* name, long value);
 
+/*
+ * MANY SERIES per launch (no counterpart in the reference, which fits one light curve per CarmaModel): a survey's light
+ * curves, each fitted on its own, in one context and in one launch.
+ *
+ * carma_mctx_create: series s is time / y / yerr [offsets[s], offsets[s+1]) (offsets[0] = 0, non-decreasing); each series is
+ *   prepared exactly as carma_ctx_create prepares one (sort, dedup, prior bounds, regular-cadence test) and the records of
+ *   all of them are uploaded into one buffer.  max_stdev = [nseries] or NULL for 10 sqrt(var(y_s, ddof=1)) per series.  All
+ *   argument errors (including a series with fewer than 2 distinct times, named by its index) are reported before any
+ *   device work.  Returns NULL on error.  carma_mctx_n / _get_data / _get_prior: as the carma_ctx_ calls, for series s.
+ * carma_mlogdensity_batch: B evaluations, theta = [B][d], evaluation i on series series[i]; out = [B] in the caller's
+ *   order.  One evaluation per lane (k_logdens_carma_lane_ms / k_logdens_car1_ms): series s gets the same bits as the
+ *   single-series lane kernel on a context of that series alone, whatever else the batch holds.  A series index out of
+ *   range is CARMA_EINVAL before any device work.
+ * carma_mle_batched_ms: carma_mle_batched with start i on series series[i] and its own box lo / hi = [B][d] (NULL or
+ *   non-finite entries = unbounded); every start's evaluations go through carma_mlogdensity_batch, all starts advance in
+ *   lock-step in the same launches.
+ */
+typedef struct carma_mctx carma_mctx;
+carma_mctx* carma_mctx_create(const double* time, const double* y, const double* yerr, const long* offsets /* [S+1] */,
+                              int nseries, int p, int q, const double* max_stdev /* [S] or NULL */, int device);
+void carma_mctx_destroy(carma_mctx* h);
+int carma_mctx_nseries(const carma_mctx* h);
+int carma_mctx_dim(const carma_mctx* h);
+int carma_mctx_n(const carma_mctx* h, int s);           /* length of series s after sort/dedup */
+int carma_mctx_get_data(const carma_mctx* h, int s, double* time, double* y, double* yerr);
+int carma_mctx_get_prior(const carma_mctx* h, int s, double* out3 /* max_stdev, max_freq, min_freq */);
+int carma_mlogdensity_batch(carma_mctx* h, const double* theta /* [B][d] */, const int* series /* [B] */, int B,
+                            int ignore_prior, double* out /* [B] */);
+int carma_mlogdensity_kernel_name(const carma_mctx* h, char* buf, int len);
+int carma_mle_batched_ms(carma_mctx* h, const double* x0 /* [B][d] */, const int* series /* [B] */, int B,
+                         const double* lo /* [B][d] */, const double* hi /* [B][d] */, int maxiter, int mem, double ftol,
+                         double gtol, double fd_step, int ignore_prior, double* x, double* fun, int* nit, int* nfev,
+                         int* status);
+
 /* getLogPrior (carpack.hpp:118-126, wrapper :50,58,67); host arithmetic, one vector. */
 double carma_logprior(const carma_ctx* h, const double* theta);
 
