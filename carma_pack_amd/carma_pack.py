@@ -113,13 +113,19 @@ def carma_process(time, sigsqr, ar_roots, ma_coefs=(1.0,), rng=None):
     u = c.copy()
     for k in range(1, time.size):
         rho = np.exp(r * (time[k] - time[k - 1]))
-        x = rho * (x + u * (innov / var))
-        D = np.outer(rho, np.conj(rho)) * (D - np.outer(u, np.conj(u)) / var)
+        if var > 0.0:
+            x = rho * (x + u * (innov / var))
+            D = np.outer(rho, np.conj(rho)) * (D - np.outer(u, np.conj(u)) / var)
+        else:                                        # the previous value was known: no measurement update
+            x = rho * x
+            D = np.outer(rho, np.conj(rho)) * D
         w = D @ np.conj(b)
         u = w + c
-        var = s0 + float(np.real(b @ w))
+        # a repeated time has one-step variance exactly 0 (the value repeats); in doubles it comes out at rounding size,
+        # of either sign (the reference's np.sqrt then yields NaN) -- same rule as the device (carma_simulate.h)
+        var = 0.0 if time[k] == time[k - 1] else s0 + float(np.real(b @ w))
         mean = float(np.real(b @ x))
-        y[k] = rng.normal(mean, np.sqrt(var))
+        y[k] = rng.normal(mean, np.sqrt(max(var, 0.0)))
         innov = y[k] - mean
     return y
 

@@ -293,3 +293,45 @@ def queue_get(q, procs, timeout=600.0):
             dead = [p.exitcode for p in procs if not p.is_alive() and p.exitcode not in (0, None)]
             assert not dead, "worker process exited with code %r" % dead
             assert time.time() - t0 < timeout, "worker timed out"
+
+
+def philox_normals(seed, path, n):
+    """rng_normal(key{seed, path}, i, 0) of carma_rng.h for i < n, restated with numpy (Box-Muller on Philox4x32-10)."""
+    from carma_pack_amd import parallel as par
+    out = np.empty(n)
+    for i in range(n):
+        x = par.philox4x32_10(i & 0xFFFFFFFF, (i >> 32) & 0xFFFFFFFF, path, (3 << 24) | 0, seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+        u1 = ((((x[0] << 32) | x[1]) >> 11) + 0.5) / 9007199254740992.0
+        u2 = ((((x[2] << 32) | x[3]) >> 11) + 0.5) / 9007199254740992.0
+        out[i] = np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
+    return out
+
+
+ROOT_KINDS = ("complex", "real", "mixed")
+
+
+def model_roots(rng, p, kind):
+    """p distinct AR roots (conjugate pairs adjacent, real roots last) on time scales of ~0.2 ... 50 (the series of
+    irregular_series step by 1 ... 3).  kind: "complex" = as many conjugate pairs as p allows (one real root when p is odd),
+    "real" = all real, "mixed" = one pair and p - 2 real roots (p = 2: one pair)."""
+    npair = {"complex": p // 2, "real": 0, "mixed": 1}[kind]
+    out = []
+    for k in range(npair):
+        re = -rng.uniform(0.02, 0.3)
+        im = rng.uniform(0.15, 1.5) * (k + 1) / npair
+        out += [complex(re, -im), complex(re, im)]
+    nr = p - 2 * npair
+    # real roots spread geometrically (well separated: a clustered pair is the ill-conditioned case, tested elsewhere)
+    grid = np.geomspace(0.15, 0.15 * 1.8 ** max(nr - 1, 0), nr) * rng.uniform(0.8, 1.25)
+    out += [complex(-r, 0.0) for r in grid]
+    return np.array(out)
+
+
+def model_ma(rng, p, q):
+    """MA coefficients (lowest order first, ma[0] = 1) of q negative real MA roots, zero padded to p."""
+    ma = np.zeros(p)
+    ma[0] = 1.0
+    if q:
+        c = np.poly(-rng.uniform(0.3, 3.0, q))                   # highest order first
+        ma[:q + 1] = (c / c[-1])[::-1]
+    return ma

@@ -8,6 +8,7 @@ import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 from batched_opt_proto import minimize_batched  # noqa: E402  (numpy prototype of the library's optimiser)
+from helpers import philox_normals as _philox_normals  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -246,18 +247,6 @@ def test_car1_sample_predict_simulate_assess_fit(cm):
     pm, pv = sample.predict(np.sort(ts)[:1], bestfit="map")                           # first time visited: plain conditional
     z = (draws[:, 0].mean() - pm[0]) / np.sqrt(pv[0] / 300)
     assert abs(z) < 4.5 and 0.7 < draws[:, 0].var() / pv[0] < 1.4
-
-
-def _philox_normals(seed, path, n):
-    """rng_normal(key{seed, path}, i, 0) of carma_rng.h for i < n, restated with numpy (Box-Muller on Philox4x32-10)."""
-    from carma_pack_amd import parallel as par
-    out = np.empty(n)
-    for i in range(n):
-        x = par.philox4x32_10(i & 0xFFFFFFFF, (i >> 32) & 0xFFFFFFFF, path, (3 << 24) | 0, seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
-        u1 = ((((x[0] << 32) | x[1]) >> 11) + 0.5) / 9007199254740992.0
-        u2 = ((((x[2] << 32) | x[3]) >> 11) + 0.5) / 9007199254740992.0
-        out[i] = np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
-    return out
 
 
 def test_device_carma_process_is_the_reference_construction(cm, golden_dir):

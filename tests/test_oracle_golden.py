@@ -235,6 +235,53 @@ def test_predict_car1_matches_dense_gp(golden_dir):
     np.testing.assert_allclose(v, pr["car1_dvar"], rtol=1e-8)
 
 
+def test_predict_truth_is_tied_to_the_reference_held_vectors(golden_dir):
+    """The 50-digit predict reference (mp_truth.predict_truth / predict_truth_car1: the dense Gaussian-process conditional)
+    -- the yardstick of tests/test_gpu_model_kernels.py -- against the vectors the REFERENCE's own Python produced
+    (tests/golden/make_golden_predict.py): KalmanFilterDeprecated.predict (*_pmean / *_pvar) to 1e-12, its dense solve in
+    doubles including the backcasts (*_dmean / *_dvar, car1_*) to 1e-11; means relative to the data's scale.  Then against
+    the oracle's Kalman Predict on short series of three orders, all root kinds: 1e-9."""
+    from helpers import irregular_series, model_ma, model_roots
+    from mp_truth import predict_truth, predict_truth_car1
+    g = _load(golden_dir, "carma53_readme.npz")
+    pr = _load(golden_dir, "predict.npz")
+    t, y, yerr = g["t"], g["y"], g["yerr"]
+    times, back = pr["times"], pr["back"]
+    nt = times.size
+    for tag in ("true", "th3", "th17"):
+        mu, scale = float(pr[tag + "_mu"]), float(pr[tag + "_scale"])
+        m, v = predict_truth(t, y - mu, np.sqrt(scale) * yerr, float(pr[tag + "_sigsqr"]), pr[tag + "_omega"],
+                             pr[tag + "_ma"], np.r_[times, back])
+        sc = np.abs(y - mu).max()
+        assert np.max(np.abs(m[:nt] - pr[tag + "_pmean"])) <= 1e-12 * sc, tag
+        assert np.max(np.abs(v[:nt] - pr[tag + "_pvar"]) / v[:nt]) <= 1e-12, tag
+        assert np.max(np.abs(m - pr[tag + "_dmean"])) <= 1e-11 * sc, tag
+        assert np.max(np.abs(v - pr[tag + "_dvar"]) / v) <= 1e-11, tag
+    c = _load(golden_dir, "car1_n100.npz")
+    th = pr["car1_theta"]
+    omega = np.exp(th[3])
+    m, v = predict_truth_car1(c["t"], c["y"] - th[2], np.sqrt(th[1]) * c["yerr"], 2 * th[0] ** 2 * omega, omega,
+                              pr["car1_times"])
+    np.testing.assert_allclose(m, pr["car1_dmean"], rtol=1e-11)
+    np.testing.assert_allclose(v, pr["car1_dvar"], rtol=1e-11)
+    # against the oracle's Kalman Predict (a different algorithm): backcast, datum, midpoint, forecast
+    for p, q in ((2, 1), (4, 0), (7, 6)):
+        ts, ys, es = irregular_series(40, 10 + p)
+        ys = ys - ys.mean()
+        tp = np.r_[ts[0] - 30.0, ts[0], ts[5], 0.5 * (ts[9] + ts[10]), ts[-1], ts[-1] + 4.0, ts[-1] + 300.0]
+        for kind in ("complex", "real", "mixed"):
+            rng = np.random.default_rng(100 * p + q)
+            roots, ma = model_roots(rng, p, kind), model_ma(rng, p, q)
+            sigsqr = np.var(ys) / orc.variance(roots, ma)
+            m, v = predict_truth(ts, ys, es, sigsqr, roots, ma, tp)
+            om, ov = orc.predict_carma(ts, ys, es, sigsqr, roots, ma, tp)
+            assert np.all(np.abs(om - m) <= 1e-9 * np.maximum(np.abs(m), np.sqrt(v))), (p, q, kind, om, m)
+            assert np.all(np.abs(ov - v) <= 1e-9 * v), (p, q, kind, ov, v)
+    m, v = predict_truth_car1(ts, ys, es, 0.2, 0.1, tp)
+    om, ov = orc.predict_car1(ts, ys, es, 0.2, 0.1, tp)
+    assert np.all(np.abs(om - m) <= 1e-9 * np.maximum(np.abs(m), np.sqrt(v))) and np.all(np.abs(ov - v) <= 1e-9 * v)
+
+
 def test_literal_sampler_restatement_car1(golden_dir):
     """The oracle's restatement of RunCar1Sampler recovers the truth of the CAR(1) fixture
     (carma_unit_tests.cpp:1319-1376 criterion: posterior mean within 3 sigma) and keeps the
