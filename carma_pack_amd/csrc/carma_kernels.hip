@@ -232,26 +232,43 @@ __global__ __launch_bounds__(256) void k_logdens_carma_w2(const double* __restri
     // copies -- and everything behind reads theta from the wave's own LDS copy.  (Read where they are used, the parameters were three
     // or four dependent L2 round trips in every wave's prologue, and the tables' copy one more in front of them: a second pass over
     // the same set-up code took 2.3 k cycles where the first took 5.6 k, profiles/r06/w2_stamps_v4.txt.)
+    // The series goes into LDS as well (producers: carma_pipew.h, SLDS): {y, yerr^2}[n], then t[n]; visible behind the producers' first
+    // barrier.  Its first 512 records are requested TOGETHER with theta and the table, so that every wave's prologue waits for one L2
+    // round trip: copied behind the parameters, they were a second one (a third for the wave that takes records 256 .. n - 1).
     const double* th;
+    double2* lds_yz = ring + Geo::SER_OFF;
+    double* lds_t = reinterpret_cast<double*>(lds_yz + n + (n & 1));
     {
         double* s_th = reinterpret_cast<double*>(ring + Geo::TH_OFF) + (tid >> 6) * 64 + (lane64 & ~15);
         const int l16 = lane64 & 15;
         const double thv = l16 < d ? theta[e * d + l16] : 0.0;
         double* tab = reinterpret_cast<double*>(ring + Geo::TAB_OFF);
         const double tv = tid < MATH_TAB_N ? c_math_tab[tid] : 0.0;
+        double4 r0 = {}, r1 = {};
+        if constexpr (SL) {
+            if (tid < n) r0 = series[tid];
+            if (tid + 256 < n) r1 = series[tid + 256];
+        }
         s_th[l16] = thv;
         if (tid < MATH_TAB_N) tab[tid] = tv;
         static_assert(MATH_TAB_N <= 256, "one table element per thread");
+        if constexpr (SL) {
+            if (tid < n) {
+                lds_yz[tid] = make_double2(r0.y, r0.z);
+                lds_t[tid] = r0.w;
+            }
+            if (tid + 256 < n) {
+                lds_yz[tid + 256] = make_double2(r1.y, r1.z);
+                lds_t[tid + 256] = r1.w;
+            }
+        }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         th = s_th;
     }
-    // the series into LDS (producers: carma_pipew.h, SLDS): {y, yerr^2}[n], then t[n]; visible behind the producers' first barrier
-    double2* lds_yz = ring + Geo::SER_OFF;
-    double* lds_t = reinterpret_cast<double*>(lds_yz + n + (n & 1));
     if constexpr (SL) {
-        for (int i = tid; i < n; i += 256) {
+        for (int i = tid + 512; i < n; i += 256) {
             const double4 r = series[i];
             lds_yz[i] = make_double2(r.y, r.z);
             lds_t[i] = r.w;
