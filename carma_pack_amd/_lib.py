@@ -132,6 +132,8 @@ def _load():
     L.carma_mctx_get_prior.argtypes = [C.c_void_p, C.c_int, _dp]
     L.carma_mlogdensity_batch.argtypes = [C.c_void_p, _dp, _ip, C.c_int, C.c_int, _dp]
     L.carma_mlogdensity_kernel_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    L.carma_mkfilter.argtypes = [C.c_void_p, _ip, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_long), _ip]
+    L.carma_mpredict.argtypes = [C.c_void_p, _ip, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, C.POINTER(C.c_long), _dp, _dp, _ip]
     L.carma_mle_batched_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                        C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]
@@ -208,7 +210,7 @@ EXPORTS = [
     "carma_pt_boundary_check", "carma_pt_sweep", "carma_pt_kernel_in_use", "carma_pt_row_pipeline", "carma_pt_debug_draws", "carma_pt_get_factor",
     "carma_pt_set_factor", "carma_tune_set", "carma_mctx_create", "carma_mctx_destroy", "carma_mctx_nseries", "carma_mctx_dim",
     "carma_mctx_n", "carma_mctx_get_data", "carma_mctx_get_prior", "carma_mlogdensity_batch", "carma_mlogdensity_kernel_name",
-    "carma_mle_batched_ms",
+    "carma_mle_batched_ms", "carma_mkfilter", "carma_mpredict",
 ]
 
 
@@ -686,6 +688,71 @@ class MultiContext:
         buf = C.create_string_buffer(128)
         check(lib.carma_mlogdensity_kernel_name(self._h, buf, 128), "carma_mlogdensity_kernel_name")
         return buf.value.decode()
+
+    def _items(self, which, sigsqr, roots, ma, mu, who):
+        """The (series, model) items of kfilter / predict as the library takes them; every shape error is raised here."""
+        sig = as_f64(np.atleast_1d(sigsqr)).ravel()
+        M = sig.size
+        if M < 1:
+            raise ValueError("%s: need at least one item" % who)
+        w = self._which(which, M)
+        roots = np.asarray(roots, dtype=complex)
+        if self.p == 1:
+            roots = roots.reshape(-1)
+            if roots.size != M:
+                raise ValueError("%s: roots must hold one root (-omega) per item for a CAR(1) context" % who)
+            ma_, nma = np.ones((M, 1)), 1
+        else:
+            roots = np.atleast_2d(roots)
+            if roots.shape != (M, self.p):
+                raise ValueError("%s: roots must be [%d, %d] (one row of p roots per item)" % (who, M, self.p))
+            ma_ = as_f64(np.atleast_2d(ma))
+            if ma_.ndim != 2 or ma_.shape[0] != M or not (1 <= ma_.shape[1] <= self.p):
+                raise ValueError("%s: ma must be [%d, nma] with 1 <= nma <= %d" % (who, M, self.p))
+            nma = ma_.shape[1]
+        om = as_f64(np.stack([roots.real, roots.imag], axis=-1))
+        mu_ = None if mu is None else as_f64(np.atleast_1d(mu)).ravel()
+        if mu_ is not None and mu_.size != M:
+            raise ValueError("%s: mu must have one entry per item" % who)
+        return M, w, sig, om, ma_, nma, mu_
+
+    def kfilter(self, which, sigsqr, roots, ma, mu=None):
+        """Filter() of M items in one launch (carma_mkfilter): item i is the model (sigsqr[i], roots[i], ma[i]) on series
+        which[i].  sigsqr [M], roots [M][p] complex (p = 1: [M], the root -omega), ma [M][nma] (ignored for p = 1), mu [M] or
+        None -- subtracted from y inside and added back to the mean.  Returns (means, vars, singular): lists of M arrays, item
+        i's of length n[which[i]], and a bool array."""
+        M, w, sig, om, ma_, nma, mu_ = self._items(which, sigsqr, roots, ma, mu, "MultiContext.kfilter")
+        off = np.zeros(M + 1, dtype=np.int64)
+        off[1:] = np.cumsum(self.n[w])
+        mean, var = np.empty(off[-1]), np.empty(off[-1])
+        sing = np.zeros(M, dtype=np.int32)
+        check(lib.carma_mkfilter(self._h, w.ctypes.data_as(_ip), M, ptr(sig), ptr(om), ptr(ma_), nma,
+                                 ptr(mu_) if mu_ is not None else None, ptr(mean), ptr(var), None, sing.ctypes.data_as(_ip)),
+              "carma_mkfilter")
+        return ([mean[off[i]:off[i + 1]] for i in range(M)], [var[off[i]:off[i + 1]] for i in range(M)], sing.astype(bool))
+
+    def predict(self, which, sigsqr, roots, ma, times, mu=None, return_singular=False):
+        """Predict of M items in one launch (carma_mpredict): item i (as in kfilter) at times[i], a list of M arrays (any of
+        them may be empty).  Returns (means, vars): lists of M arrays shaped as times[i].  An item with a repeated AR root
+        raises CarmaError, as KalmanHandle.predict does -- or, with return_singular, is flagged in a third return value."""
+        M, w, sig, om, ma_, nma, mu_ = self._items(which, sigsqr, roots, ma, mu, "MultiContext.predict")
+        times = [as_f64(np.atleast_1d(t)).ravel() for t in times]
+        if len(times) != M:
+            raise ValueError("MultiContext.predict: times must hold one array per item (%d), got %d" % (M, len(times)))
+        toff = np.zeros(M + 1, dtype=np.int64)
+        toff[1:] = np.cumsum([t.size for t in times])
+        tp = as_f64(np.concatenate(times)) if toff[-1] else np.zeros(1)
+        pm, pv = np.empty(max(int(toff[-1]), 1)), np.empty(max(int(toff[-1]), 1))
+        sing = np.zeros(M, dtype=np.int32)
+        check(lib.carma_mpredict(self._h, w.ctypes.data_as(_ip), M, ptr(sig), ptr(om), ptr(ma_), nma,
+                                 ptr(mu_) if mu_ is not None else None, ptr(tp), toff.ctypes.data_as(C.POINTER(C.c_long)), ptr(pm),
+                                 ptr(pv), sing.ctypes.data_as(_ip)), "carma_mpredict")
+        if return_singular:
+            return ([pm[toff[i]:toff[i + 1]] for i in range(M)], [pv[toff[i]:toff[i + 1]] for i in range(M)], sing.astype(bool))
+        if sing.any():
+            raise CarmaError("KalmanFilterp: singular eigenvector matrix (solve failed) for item(s) %s"
+                             % np.flatnonzero(sing)[:8].tolist())
+        return [pm[toff[i]:toff[i + 1]] for i in range(M)], [pv[toff[i]:toff[i + 1]] for i in range(M)]
 
     def mle_batched(self, x0, which, lo, hi, maxiter=2000, mem=8, ftol=2.220446049250313e-09, gtol=1e-5, fd_step=1e-6,
                     ignore_prior=True):

@@ -16,7 +16,7 @@ from scipy.optimize import minimize
 from . import _carmcmc as carmcmcLib
 
 __all__ = ["CarmaModel", "CarmaModelSet", "CarmaSample", "Car1Sample", "MCMCSample", "get_ar_roots", "power_spectrum",
-           "carma_variance", "car1_process", "carma_process", "carma_process_batch", "car1_process_batch"]
+           "carma_variance", "car1_process", "carma_process", "carma_process_batch", "car1_process_batch", "mle_to_model"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -234,6 +234,36 @@ def _poly_from_roots(roots):
     for i in range(m):
         coefs[:, 1:i + 2] = coefs[:, 1:i + 2] - roots[:, i:i + 1] * coefs[:, 0:i + 1]
     return coefs
+
+
+def mle_to_model(x, p, q=0):
+    """An MLE parameter vector x of order (p, q) -> (sigsqr, ar_roots, ma_coefs, mu): the model of the Kalman filter, derived
+    exactly as CarmaSample.add_mle derives it -- var = x[0]^2, roots and MA coefficients from the log quadratic factors,
+    sigsqr = var / carma_variance(1, roots, ma); CAR(1): omega = exp(x[3]), sigsqr = 2 omega var, the one root -omega."""
+    x = np.asarray(x, dtype=float).ravel()
+    p, q = int(p), int(q)
+    d = 4 if p == 1 else 3 + p + q
+    if p < 1 or q < 0 or q >= p or x.size != d:
+        raise ValueError("mle_to_model: a CARMA(%d,%d) parameter vector has %d entries, got %d" % (p, q, d, x.size))
+    var, mu = x[0] ** 2, float(x[2])
+    if p == 1:
+        omega = np.exp(x[3])
+        return float(2.0 * omega * var), np.array([-omega + 0j]), np.ones(1), mu
+    roots = _roots_from_log_quads(x[None, 3:p + 3])[0]
+    if q == 0:
+        ma = np.ones(1)
+    else:
+        c = np.poly(_roots_from_log_quads(x[None, 3 + p:])[0])
+        ma = np.real(c / c[q])[::-1]
+    return float(var / carma_variance(1.0, roots, ma)), roots, ma, mu
+
+
+def group_by_order(orders):
+    """[(p, q)] per series -> {(p, q): [series indices]}, orders in order of first appearance."""
+    groups = {}
+    for s, (p, q) in enumerate(orders):
+        groups.setdefault((int(p), int(q)), []).append(s)
+    return groups
 
 
 class CarmaSample(MCMCSample):
@@ -738,4 +768,74 @@ class CarmaModelSet(object):
                     best, best_aicc, order = mles[s], a, (p, q)
             out.append((best, pqlist, AICc))
             self.orders.append(order)
+        return out
+
+    def _fit_items(self, fits, orders):
+        """Per-order work lists of predict / assess_fit: {(p, q): (series indices, sigsqr, roots, ma, mu)}.  fits: S results
+        (anything with .x, or the vectors themselves); orders: None (self.orders of choose_order, else (self.p, self.q) for all),
+        one (p, q), or one per series.  Everything is checked here, before any library call."""
+        fits = list(fits)
+        if len(fits) != self.nseries:
+            raise ValueError("fits must hold one result per series (%d), got %d" % (self.nseries, len(fits)))
+        if orders is None:
+            orders = getattr(self, "orders", None) or [(self.p, self.q)] * self.nseries
+        orders = [tuple(o) for o in np.asarray(orders, dtype=int).reshape(-1, 2)]
+        if len(orders) == 1:
+            orders = orders * self.nseries
+        if len(orders) != self.nseries:
+            raise ValueError("orders must hold one (p, q) per series (%d), got %d" % (self.nseries, len(orders)))
+        items = {}
+        for (p, q), idx in group_by_order(orders).items():
+            if not p > q >= 0:
+                raise ValueError("Order of AR polynomial, p, must be larger than order of MA polynomial, q.")
+            mods = []
+            for s in idx:
+                try:
+                    mods.append(mle_to_model(getattr(fits[s], "x", fits[s]), p, q))
+                except ValueError as err:
+                    raise ValueError("series %d: %s" % (s, err))
+            ma = np.zeros((len(idx), max(q + 1, 1)))
+            for k, m in enumerate(mods):
+                ma[k, :m[2].size] = m[2]
+            items[(p, q)] = (np.array(idx), np.array([m[0] for m in mods]), np.array([m[1] for m in mods]), ma,
+                             np.array([m[3] for m in mods]))
+        return items
+
+    def predict(self, times, fits, orders=None):
+        """CarmaSample.predict of every series at its fitted model: expected value and variance at `times` -- one array for
+        every series, or a list of S arrays -- given the series' data.  fits: S results as get_mle returns them (or the best of
+        each choose_order triple); orders: see _fit_items.  The series are grouped by order, one launch per order present.
+        Returns two lists of S arrays."""
+        if isinstance(times, (list, tuple)) and len(times) and not np.isscalar(times[0]):
+            tlist = [np.atleast_1d(np.asarray(t, dtype=float)).ravel() for t in times]
+            if len(tlist) != self.nseries:
+                raise ValueError("times must be one array, or one per series (%d), got %d" % (self.nseries, len(tlist)))
+        else:
+            tlist = [np.atleast_1d(np.asarray(times, dtype=float)).ravel()] * self.nseries
+        mean, var = [None] * self.nseries, [None] * self.nseries
+        for (p, q), (idx, sig, roots, ma, mu) in self._fit_items(fits, orders).items():
+            pm, pv = self.context(p, q).predict(idx, sig, roots, ma, [tlist[s] for s in idx], mu=mu)
+            for k, s in enumerate(idx):
+                mean[s], var[s] = pm[k], pv[k]
+        return mean, var
+
+    def assess_fit(self, fits, orders=None, nplot=256):
+        """CarmaSample.assess_fit of every series at its fitted model: a list of S dicts with the interpolated path on `nplot`
+        times (time, mean, var), the standardised residuals of the one-step predictions (std_resid) and their autocorrelation
+        function (resid_acf).  One filter launch and one predict launch per order present."""
+        out = [None] * self.nseries
+        for (p, q), (idx, sig, roots, ma, mu) in self._fit_items(fits, orders).items():
+            ctx = self.context(p, q)
+            kmean, kvar, sing = ctx.kfilter(idx, sig, roots, ma, mu=mu)
+            if sing.any():
+                raise carmcmcLib._lib.CarmaError("KalmanFilterp: singular eigenvector matrix (solve failed) for series %s"
+                                            % idx[sing][:8].tolist())
+            grids = [np.linspace(self.models[s].time.min(), self.models[s].time.max(), nplot) for s in idx]
+            pm, pv = ctx.predict(idx, sig, roots, ma, grids, mu=mu)
+            for k, s in enumerate(idx):
+                resid = (self.models[s].y - kmean[k]) / np.sqrt(kvar[k])
+                r0 = resid - resid.mean()
+                acf = np.correlate(r0, r0, mode="full")[r0.size - 1:]
+                acf = acf / acf[0]                            # (by its own lag 0, not np.sum(r0 * r0): resid_acf[0] is exactly 1)
+                out[s] = dict(time=grids[k], mean=pm[k], var=pv[k], std_resid=resid, resid_acf=acf)
         return out

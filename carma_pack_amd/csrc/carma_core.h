@@ -746,9 +746,11 @@ CARMA_DEV double logdensity_carma(const GrpT& g, const double* theta, int q, con
 
 // ---------------------------------------------------------------------------------------------
 // CAR(1): one LANE per evaluation (kfilter.cpp:19-48, carpack.hpp:265,273-275, carpack.cpp:116-130)
+// write_mv: mean_k (+ mu when mv_mu is set: the callers with centred data pass mu = 0 and keep their bits) and var_k of every
+// datum to mean_out[k * mv_stride], var_out[k * mv_stride]
 CARMA_DEV double car1_filter(double sigsqr, double omega, double mu, double scale,
                              const double4* __restrict__ series, int n, bool write_mv, double* mean_out,
-                             double* var_out)
+                             double* var_out, long mv_stride = 1, bool mv_mu = false)
 {
     double4 rec = series[0];
     double e2 = rec.z * scale;
@@ -759,7 +761,7 @@ CARMA_DEV double car1_filter(double sigsqr, double omega, double mu, double scal
     acc.init();
     acc.add_var(var);
     if (write_mv) {
-        mean_out[0] = mean;
+        mean_out[0] = mv_mu ? mean + mu : mean;
         var_out[0] = var;
     }
     // (round 4: one reciprocal of var per step instead of two IEEE divisions, the short exponential of carma_math.h instead of
@@ -783,8 +785,8 @@ CARMA_DEV double car1_filter(double sigsqr, double omega, double mu, double scal
         yc = rec.y - mu;
         acc.add_var(var);
         if (write_mv) {
-            mean_out[k] = mean;
-            var_out[k] = var;
+            mean_out[k * mv_stride] = mv_mu ? mean + mu : mean;
+            var_out[k * mv_stride] = var;
         }
     }
     double innov = yc - mean;

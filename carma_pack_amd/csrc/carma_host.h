@@ -89,6 +89,8 @@ void sort_dedup(std::vector<double>& t, std::vector<double>& y, std::vector<doub
 std::vector<double> pack_series(const std::vector<double>& t, const std::vector<double>& y, const std::vector<double>& e);
 void set_prior_bounds(Prior& pr, const double* t, long n, double max_stdev);
 bool series_repeated_dt(const double* packed, long n);
+// AR roots in the order the KalmanFilterp-type kernels expect (carma_normalize_roots); CARMA_EINVAL unless closed under conjugation
+int normalize_roots(int p, const double* om, double* out);
 int hip_fail(hipError_t e, const char* what);
 int select_device(int device);
 void pt_state_free(Ctx* c);

@@ -31,11 +31,6 @@
 
 namespace carma {
 
-template <int P>
-struct GroupOf {
-    static constexpr int value = P <= 2 ? 2 : (P <= 4 ? 4 : 8);
-};
-
 template <int P, int G, int WAVES, bool DTC = false>
 __global__ __launch_bounds__(64 * WAVES) void k_logdens_carma(const double* __restrict__ theta, int B, int d, int q,
                                                              const double4* __restrict__ series, int n, Prior pr,

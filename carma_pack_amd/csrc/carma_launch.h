@@ -6,6 +6,13 @@
 
 namespace carma {
 
+// lanes of the group that holds one evaluation in the lane-group kernels (a row of the state per lane)
+constexpr int group_of(int p) { return p <= 2 ? 2 : (p <= 4 ? 4 : 8); }
+template <int P>
+struct GroupOf {
+    static constexpr int value = group_of(P);
+};
+
 // compute units of the current device (cached per device)
 int device_cus();
 

@@ -11,6 +11,16 @@
 //     pad lanes (eval_idx = -1) compute a copy of the wave's first evaluation and write nothing;
 //   - the filter is logdensity_lane / logdensity_car1 unchanged, and REPDT is decided per series as carma_ctx_create decides
 //     it: a series gives the same bits as the single-series lane kernel on it.
+//
+// Filter() and Predict of MANY (series, model) items in one launch (carma_mkfilter, carma_mpredict):
+//   - filter: one ITEM per lane -- kfilter_lane / car1_filter with a series pointer and a length of the lane's own.  The loop over
+//     the data is a divergent one (a lane that has finished is masked off by the compiler's exec handling; nothing inside
+//     lane_filter with in-line factors talks across lanes), the records come in with per-lane vector loads, and the host plan
+//     sorts the items by length so that a wave's lanes finish together.  A wave writes into a tile of its own, [2 nmax_w][lanes]
+//     (row k: mean_k of every lane; row n_l + k: var_k of lane l), so that the stores of a step are contiguous wherever the
+//     lanes' lengths agree; k_mtranspose_mv then moves the tiles into the caller's ragged layout, 32 data of an item at a time;
+//   - predict: one lane GROUP per (item, time) with predict_run; its group exchange needs one trip count per wave, so a wave
+//     takes ONE series (wave table indexed by blockIdx.x) and its 64 / G groups take (item, time) pairs on that series.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,6 +35,7 @@
 #include "carma_core.h"
 #include "carma_host.h"
 #include "carma_lane.h"
+#include "carma_predict.h"
 
 namespace carma {
 
@@ -95,6 +106,162 @@ static hipError_t launch_logdens_ms(int p, bool repdt, const double* theta, int 
     return hipGetLastError();
 }
 
+
+// Filter() of M items, one per lane.  par: per slot [M][3 P + 2] as k_kfilter_carma_lane takes it, slots in the plan's order (longest
+// series first); slot_series[M]; tile_off[waves]: start of the wave's tile in mv.  Lanes past M leave after the barrier.
+template <int P>
+__global__ __launch_bounds__(64) void k_mkfilter_carma_lane(const double* __restrict__ par, int M, const double4* __restrict__ records,
+                                                           const long* __restrict__ off, const int* __restrict__ nser,
+                                                           const int* __restrict__ slot_series, const long* __restrict__ tile_off,
+                                                           double* __restrict__ mv, int* __restrict__ singular)
+{
+    __shared__ double s_tab[MATH_TAB_N];
+    math_tab_fill(s_tab);
+    __syncthreads();
+    const long slot = (long)blockIdx.x * 64 + threadIdx.x;
+    if (slot >= M) return;
+    const long ld = min(64L, (long)M - (long)blockIdx.x * 64);            // lanes of this wave that hold an item
+    const int s = slot_series[slot];
+    const double* pm = par + slot * (3 * P + 2);
+    const bool sing = kfilter_lane<P>(pm, pm + 2 * P, pm[3 * P], pm[3 * P + 1], records + off[s], nser[s], s_tab,
+                                      mv + tile_off[blockIdx.x] + threadIdx.x, ld);
+    singular[slot] = sing ? 1 : 0;
+}
+
+// CAR(1): par = [M][3] (sigsqr, omega, mu), the same tiles
+__global__ __launch_bounds__(64) void k_mkfilter_car1(const double* __restrict__ par, int M, const double4* __restrict__ records,
+                                                      const long* __restrict__ off, const int* __restrict__ nser,
+                                                      const int* __restrict__ slot_series, const long* __restrict__ tile_off,
+                                                      double* __restrict__ mv)
+{
+    const long slot = (long)blockIdx.x * 64 + threadIdx.x;
+    if (slot >= M) return;
+    const long ld = min(64L, (long)M - (long)blockIdx.x * 64);
+    const int s = slot_series[slot];
+    const int n = nser[s];
+    const double* pm = par + slot * 3;
+    double* t = mv + tile_off[blockIdx.x] + threadIdx.x;
+    (void)car1_filter(pm[0], pm[1], pm[2], 1.0, records + off[s], n, true, t, t + (long)n * ld, ld, true);
+}
+
+// The tiles of the filter kernels -> the caller's ragged arrays: the item in lane l of wave blockIdx.x has slot_n data, its
+// means go to mean[slot_out + k], its variances to var[slot_out + k].  32 rows of a tile at a time through LDS: the reads
+// follow the tile's rows, the writes put 32 consecutive data of one item side by side; nothing is written at or past k = n_l.
+__global__ __launch_bounds__(256) void k_mtranspose_mv(const double* __restrict__ mv, const long* __restrict__ tile_off, int M,
+                                                       const int* __restrict__ slot_n, const long* __restrict__ slot_out,
+                                                       double* __restrict__ mean, double* __restrict__ var)
+{
+    __shared__ double s_m[32][65], s_v[32][65];
+    __shared__ int s_n[64];
+    __shared__ long s_o[64];
+    const long slot0 = (long)blockIdx.x * 64;
+    const int ld = (int)min(64L, (long)M - slot0);
+    if (threadIdx.x < 64) {
+        const bool live = (int)threadIdx.x < ld;
+        s_n[threadIdx.x] = live ? slot_n[slot0 + threadIdx.x] : 0;
+        s_o[threadIdx.x] = live ? slot_out[slot0 + threadIdx.x] : 0;
+    }
+    __syncthreads();
+    const int nmax = s_n[0];                                  // the plan sorts by length: lane 0 holds the wave's longest
+    const double* tile = mv + tile_off[blockIdx.x];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;   // reading: 64 lanes x 4 rows
+    const int kx = threadIdx.x & 31, ly = threadIdx.x >> 5;   // writing: 32 data x 8 items
+    for (int k0 = blockIdx.y * 32; k0 < nmax; k0 += gridDim.y * 32) {
+        const int ntx = s_n[tx];
+        for (int j = ty; j < 32; j += 4) {
+            const int k = k0 + j;
+            if (k < ntx) {
+                s_m[j][tx] = tile[(long)k * ld + tx];
+                s_v[j][tx] = tile[((long)ntx + k) * ld + tx];
+            }
+        }
+        __syncthreads();
+        const int k = k0 + kx;
+        for (int l = ly; l < ld; l += 8) {
+            if (k < s_n[l]) {
+                mean[s_o[l] + k] = s_m[kx][l];
+                var[s_o[l] + k] = s_v[kx][l];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// Predict of (item, time) pairs: wave blockIdx.x works on series wave_series[blockIdx.x], its 64 / G groups on the pairs
+// pair_out[64 / G * blockIdx.x + group] (index into tpred / pmean / pvar; -1: an idle group, which repeats the wave's first
+// pair and writes nothing) of item pair_item[.].  par = [items][3 P + 2] in the caller's order.
+template <int P, int G>
+__global__ __launch_bounds__(64) void k_mpredict_carma(const double* __restrict__ par, const double4* __restrict__ records,
+                                                      const long* __restrict__ off, const int* __restrict__ nser,
+                                                      const int* __restrict__ wave_series, const int* __restrict__ pair_item,
+                                                      const long* __restrict__ pair_out, const double* __restrict__ tpred,
+                                                      double* __restrict__ pmean, double* __restrict__ pvar, int* __restrict__ singular)
+{
+    __shared__ double4 xch[64];
+    __shared__ double2 xch2[64];
+    const int tid = threadIdx.x;
+    Grp<G> g{xch, tid & 63, xch2};
+    const int s = wave_series[blockIdx.x];                    // wave-uniform: one trip count for every group (predict_run's exchange)
+    const double4* series = records + off[s];
+    const int n = nser[s];
+    long e = (long)blockIdx.x * (64 / G) + tid / G;
+    const bool live = pair_out[e] >= 0;
+    if (!live) e = (long)blockIdx.x * (64 / G);               // (group 0 of a wave is always live)
+    const int item = pair_item[e];
+    const long o = pair_out[e];
+    const double* pm = par + (long)item * (3 * P + 2);
+    Model<P> m;
+    model_from_roots<P, G>(g, pm, pm + 2 * P, pm[3 * P], m);
+    double mean, var;
+    bool sing;
+    predict_run<P, G>(g, m, series, n, tpred[o], &mean, &var, &sing, pm[3 * P + 1]);
+    if (live && g.lane() == 0) {
+        pmean[o] = mean;
+        pvar[o] = var;
+        if (sing) singular[item] = 1;
+    }
+}
+
+// CAR(1): one lane per (item, time) pair, pairs in the caller's order; par = [items][3] (sigsqr, omega, mu)
+__global__ __launch_bounds__(64) void k_mpredict_car1(const double* __restrict__ par, const double4* __restrict__ records,
+                                                      const long* __restrict__ off, const int* __restrict__ nser,
+                                                      const int* __restrict__ item_series, const int* __restrict__ pair_item,
+                                                      long npairs, const double* __restrict__ tpred, double* __restrict__ pmean,
+                                                      double* __restrict__ pvar)
+{
+    const long e = (long)blockIdx.x * 64 + threadIdx.x;
+    if (e >= npairs) return;
+    const int item = pair_item[e];
+    const int s = item_series[item];
+    const double* pm = par + 3L * item;
+    predict_car1(pm[0], pm[1], records + off[s], nser[s], tpred[e], pmean + e, pvar + e, pm[2]);
+}
+
+// A device buffer of the context that grows on demand
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    hipError_t need(size_t bytes)
+    {
+        if (bytes <= cap) return hipSuccess;
+        if (p) (void)dev_free(p);
+        p = nullptr;
+        cap = 0;
+        const size_t nb = std::max(bytes + bytes / 4, (size_t)4096);
+        const hipError_t e = carma_dev_malloc(&p, nb);
+        if (e == hipSuccess) cap = nb;
+        return e;
+    }
+    void release()
+    {
+        if (p) (void)dev_free(p);
+        p = nullptr;
+        cap = 0;
+    }
+    template <class T>
+    T* as() const { return static_cast<T*>(p); }
+};
+
 // Multi-series context: the series of a set packed one after another in HBM, each as carma_ctx_create packs one
 struct Mctx {
     int device = 0;
@@ -116,6 +283,8 @@ struct Mctx {
     long cap_B = 0, cap_W = 0;
     hipStream_t stream = nullptr;
     std::vector<int> cnt, first, order, wser_tmp;
+    // carma_mkfilter / carma_mpredict: parameters and times (doubles), plan tables (ints, longs), tiles, results, flags
+    DevBuf k_par, k_int, k_long, k_tile, k_res, k_sing;
 
     size_t stage_bytes(long B, long W) const { return sizeof(double) * (size_t)B * (d + 1) + sizeof(int) * (size_t)W * 65; }
     int ensure(long B, long W)
@@ -142,6 +311,53 @@ struct Mctx {
         return CARMA_OK;
     }
 };
+
+// The items of carma_mkfilter / carma_mpredict -> par [M][3 p + 2] (p = 1: [M][3]: sigsqr, omega, mu) in the caller's order, as
+// the kernels read them.  Host only; an argument error names its item.
+static int pack_items(const Mctx* c, const char* who, const int* series, int M, const double* sigsqr, const double* om,
+                      const double* ma, int nma, const double* mu, std::vector<double>& par)
+{
+    const int p = c->p;
+    if (M < 1 || !series || !sigsqr || !om || (p > 1 && (!ma || nma < 1 || nma > p))) {
+        set_error("%s: bad argument (M >= 1, non-null arrays, 1 <= nma <= p; got M=%d nma=%d p=%d)", who, M, nma, p);
+        return CARMA_EINVAL;
+    }
+    const int PW = p == 1 ? 3 : 3 * p + 2;
+    par.assign((size_t)M * PW, 0.0);
+    for (int i = 0; i < M; i++) {
+        if (series[i] < 0 || series[i] >= c->S) {
+            set_error("%s: item %d: series index %d out of range (nseries = %d)", who, i, series[i], c->S);
+            return CARMA_EINVAL;
+        }
+        double* pb = par.data() + (size_t)i * PW;
+        if (p == 1) {
+            if (om[2 * (size_t)i + 1] != 0.0) {
+                set_error("%s: item %d: the root of a CAR(1) model must be real", who, i);
+                return CARMA_EINVAL;
+            }
+            pb[0] = sigsqr[i];
+            pb[1] = -om[2 * (size_t)i];
+            pb[2] = mu ? mu[i] : 0.0;
+            continue;
+        }
+        if (normalize_roots(p, om + (size_t)i * 2 * p, pb) != CARMA_OK) {
+            set_error("%s: item %d: the AR roots must be real or come in complex-conjugate pairs", who, i);
+            return CARMA_EINVAL;
+        }
+        for (int k = 0; k < nma; k++) pb[2 * p + k] = ma[(size_t)i * nma + k];       // zero padded to p (kfilter.hpp:318-320)
+        pb[3 * p] = sigsqr[i];
+        pb[3 * p + 1] = mu ? mu[i] : 0.0;
+    }
+    return CARMA_OK;
+}
+
+template <class T>
+static hipError_t upload(DevBuf& b, const std::vector<T>& v, hipStream_t st)
+{
+    hipError_t e = b.need(sizeof(T) * v.size());
+    if (e == hipSuccess) e = hipMemcpyAsync(b.p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, st);
+    return e;
+}
 
 }  // namespace carma
 
@@ -262,6 +478,7 @@ void carma_mctx_destroy(carma_mctx* h)
     if (c->d_wser) (void)dev_free(c->d_wser);
     if (c->d_eidx) (void)dev_free(c->d_eidx);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
+    for (DevBuf* b : {&c->k_par, &c->k_int, &c->k_long, &c->k_tile, &c->k_res, &c->k_sing}) b->release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -373,6 +590,221 @@ int carma_mlogdensity_batch(carma_mctx* h, const double* theta, const int* serie
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return hip_fail(e, "carma_mlogdensity_batch: D2H");
     std::memcpy(out, h_out, sizeof(double) * (size_t)B);
+    return CARMA_OK;
+}
+
+int carma_mkfilter(carma_mctx* h, const int* series, int M, const double* sigsqr, const double* omega_re_im, const double* ma,
+                   int nma, const double* mu, double* mean, double* var, long* out_offsets, int* singular)
+{
+    if (!h || !mean || !var) {
+        set_error("carma_mkfilter: bad argument (null context or output)");
+        return CARMA_EINVAL;
+    }
+    Mctx* c = reinterpret_cast<Mctx*>(h);
+    const int p = c->p, PW = p == 1 ? 3 : 3 * p + 2;
+    std::vector<double> par;
+    int rc = pack_items(c, "carma_mkfilter", series, M, sigsqr, omega_re_im, ma, nma, mu, par);
+    if (rc != CARMA_OK) return rc;
+    // launch plan (host): the items sorted by length, longest first -- slot j is lane j % 64 of wave j / 64, and the lanes of
+    // a wave run to the wave's longest series
+    std::vector<long> offs((size_t)M + 1, 0);
+    for (int i = 0; i < M; i++) offs[i + 1] = offs[i] + c->n[series[i]];
+    const long total = offs[M];
+    std::vector<int>& order = c->order;
+    order.resize(M);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return c->n[series[a]] > c->n[series[b]]; });
+    const long W = ((long)M + 63) / 64;
+    std::vector<double> spar((size_t)M * PW);
+    std::vector<int> tint((size_t)2 * M);                     // slot_series [M], slot_n [M]
+    std::vector<long> tlong((size_t)W + M);                   // tile_off [W], slot_out [M]
+    size_t tile_total = 0;
+    for (long j = 0; j < M; j++) {
+        const int i = order[j], sidx = series[i];
+        std::memcpy(&spar[(size_t)j * PW], &par[(size_t)i * PW], sizeof(double) * PW);
+        tint[j] = sidx;
+        tint[(size_t)M + j] = c->n[sidx];
+        tlong[(size_t)W + j] = offs[i];
+        if (j % 64 == 0) {
+            tlong[j / 64] = (long)tile_total;
+            tile_total += (size_t)2 * c->n[sidx] * (size_t)std::min(64L, (long)M - j);
+        }
+    }
+    hipError_t e = hipSetDevice(c->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    hipStream_t st = c->stream;
+    std::vector<int> sing((size_t)M, 0);
+    e = upload(c->k_par, spar, st);
+    if (e == hipSuccess) e = upload(c->k_int, tint, st);
+    if (e == hipSuccess) e = upload(c->k_long, tlong, st);
+    if (e == hipSuccess) e = c->k_tile.need(sizeof(double) * tile_total);
+    if (e == hipSuccess) e = c->k_res.need(sizeof(double) * 2 * (size_t)total);
+    if (e == hipSuccess) e = c->k_sing.need(sizeof(int) * (size_t)M);
+    if (e == hipSuccess) {
+        (void)hipGetLastError();   // HIP's last-error is sticky: drop anything left by earlier calls
+        const double* d_par = c->k_par.as<double>();
+        const int *d_sser = c->k_int.as<int>(), *d_sn = d_sser + M;
+        const long *d_toff = c->k_long.as<long>(), *d_sout = d_toff + W;
+        double *d_mv = c->k_tile.as<double>(), *d_mean = c->k_res.as<double>(), *d_var = d_mean + total;
+        const dim3 grid((unsigned)W), block(64);
+        switch (p) {
+            case 1:
+                hipLaunchKernelGGL(k_mkfilter_car1, grid, block, 0, st, d_par, M, c->d_rec, c->d_off, c->d_n, d_sser, d_toff, d_mv);
+                break;
+#define CARMA_MKF(N)                                                                                                              \
+    case N:                                                                                                                       \
+        hipLaunchKernelGGL((k_mkfilter_carma_lane<N>), grid, block, 0, st, d_par, M, c->d_rec, c->d_off, c->d_n, d_sser, d_toff,  \
+                           d_mv, c->k_sing.as<int>());                                                                            \
+        break;
+                CARMA_MKF(2) CARMA_MKF(3) CARMA_MKF(4) CARMA_MKF(5) CARMA_MKF(6) CARMA_MKF(7)
+#undef CARMA_MKF
+            default: return CARMA_EINVAL;
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess) {
+            const long nmax = c->n[series[order[0]]];
+            const dim3 tgrid((unsigned)W, (unsigned)std::min((nmax + 31) / 32, 1024L));
+            hipLaunchKernelGGL(k_mtranspose_mv, tgrid, dim3(256), 0, st, d_mv, d_toff, M, d_sn, d_sout, d_mean, d_var);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(mean, d_mean, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(var, d_var, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && p > 1)
+            e = hipMemcpyAsync(sing.data(), c->k_sing.p, sizeof(int) * (size_t)M, hipMemcpyDeviceToHost, st);
+    }
+    const hipError_t es = hipStreamSynchronize(st);           // (also after a failure: enqueued copies read and write this frame's vectors)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return hip_fail(e, "carma_mkfilter");
+    if (out_offsets) std::memcpy(out_offsets, offs.data(), sizeof(long) * ((size_t)M + 1));
+    if (singular)
+        for (long j = 0; j < M; j++) singular[order[j]] = sing[j];
+    return CARMA_OK;
+}
+
+int carma_mpredict(carma_mctx* h, const int* series, int M, const double* sigsqr, const double* omega_re_im, const double* ma,
+                   int nma, const double* mu, const double* tpred, const long* toff, double* pmean, double* pvar, int* singular)
+{
+    if (!h || !toff) {
+        set_error("carma_mpredict: bad argument (null context or toff)");
+        return CARMA_EINVAL;
+    }
+    Mctx* c = reinterpret_cast<Mctx*>(h);
+    const int p = c->p;
+    std::vector<double> par;
+    int rc = pack_items(c, "carma_mpredict", series, M, sigsqr, omega_re_im, ma, nma, mu, par);
+    if (rc != CARMA_OK) return rc;
+    if (toff[0] < 0) {
+        set_error("carma_mpredict: toff[0] = %ld is negative", toff[0]);
+        return CARMA_EINVAL;
+    }
+    for (int i = 0; i < M; i++)
+        if (toff[i + 1] < toff[i]) {
+            set_error("carma_mpredict: item %d: toff must be non-decreasing (toff[%d]=%ld > toff[%d]=%ld)", i, i, toff[i], i + 1,
+                      toff[i + 1]);
+            return CARMA_EINVAL;
+        }
+    const long t0 = toff[0], T = toff[M] - t0;
+    if (T > 0 && (!tpred || !pmean || !pvar)) {
+        set_error("carma_mpredict: bad argument (null tpred, pmean or pvar)");
+        return CARMA_EINVAL;
+    }
+    if (singular) std::fill(singular, singular + M, 0);
+    if (T == 0) return CARMA_OK;
+    // launch plan (host).  p = 1: a lane per (item, time) pair in the caller's order.  p >= 2: the pairs grouped by series
+    // (counting sort of the items), 64 / G of them per wave, a wave on one series, the longest series first.
+    std::vector<int> tint;
+    std::vector<long> tlong;
+    long W = 0;
+    const int E = p == 1 ? 64 : 64 / group_of(p);
+    if (p == 1) {
+        tint.resize((size_t)M + T);                           // item_series [M], pair_item [T]
+        for (int i = 0; i < M; i++) {
+            tint[i] = series[i];
+            std::fill(tint.begin() + M + (toff[i] - t0), tint.begin() + M + (toff[i + 1] - t0), i);
+        }
+        W = (T + 63) / 64;
+    } else {
+        const int S = c->S;
+        std::vector<long> npair((size_t)S, 0);
+        c->cnt.assign(S, 0);
+        for (int i = 0; i < M; i++) {
+            c->cnt[series[i]]++;
+            npair[series[i]] += toff[i + 1] - toff[i];
+        }
+        c->first.assign(S + 1, 0);
+        for (int s = 0; s < S; s++) c->first[s + 1] = c->first[s] + c->cnt[s];
+        c->order.resize(M);
+        {
+            std::vector<int>& pos = c->wser_tmp;
+            pos.assign(c->first.begin(), c->first.end() - 1);
+            for (int i = 0; i < M; i++) c->order[pos[series[i]]++] = i;
+        }
+        std::vector<int> used;
+        for (int s = 0; s < S; s++)
+            if (npair[s]) {
+                used.push_back(s);
+                W += (npair[s] + E - 1) / E;
+            }
+        std::stable_sort(used.begin(), used.end(), [&](int a, int b) { return c->n[a] > c->n[b]; });
+        tint.assign((size_t)W + (size_t)W * E, 0);            // wave_series [W], pair_item [W E]
+        tlong.assign((size_t)W * E, -1L);                     // pair_out [W E]
+        long w = 0;
+        for (int s : used) {
+            long g = w * E;                                   // next group of this series
+            for (int k = c->first[s]; k < c->first[s + 1]; k++) {
+                const int i = c->order[k];
+                for (long o = toff[i] - t0; o < toff[i + 1] - t0; o++, g++) {
+                    tint[(size_t)W + g] = i;
+                    tlong[g] = o;
+                }
+            }
+            const long w1 = w + (npair[s] + E - 1) / E;
+            for (; w < w1; w++) tint[w] = s;
+        }
+    }
+    hipError_t e = hipSetDevice(c->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    hipStream_t st = c->stream;
+    std::vector<int> sing((size_t)M, 0);
+    const size_t npar = par.size();
+    e = c->k_par.need(sizeof(double) * (npar + (size_t)T));
+    if (e == hipSuccess) e = hipMemcpyAsync(c->k_par.p, par.data(), sizeof(double) * npar, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(c->k_par.as<double>() + npar, tpred + t0, sizeof(double) * (size_t)T, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = upload(c->k_int, tint, st);
+    if (e == hipSuccess && p > 1) e = upload(c->k_long, tlong, st);
+    if (e == hipSuccess) e = c->k_res.need(sizeof(double) * 2 * (size_t)T);
+    if (e == hipSuccess) e = c->k_sing.need(sizeof(int) * (size_t)M);
+    if (e == hipSuccess) e = hipMemsetAsync(c->k_sing.p, 0, sizeof(int) * (size_t)M, st);
+    if (e == hipSuccess) {
+        (void)hipGetLastError();
+        const double *d_par = c->k_par.as<double>(), *d_tp = d_par + npar;
+        double *d_pm = c->k_res.as<double>(), *d_pv = d_pm + T;
+        const int* d_int = c->k_int.as<int>();
+        const dim3 grid((unsigned)W), block(64);
+        switch (p) {
+            case 1:
+                hipLaunchKernelGGL(k_mpredict_car1, grid, block, 0, st, d_par, c->d_rec, c->d_off, c->d_n, d_int, d_int + M, T, d_tp,
+                                   d_pm, d_pv);
+                break;
+#define CARMA_MPR(N)                                                                                                              \
+    case N:                                                                                                                       \
+        hipLaunchKernelGGL((k_mpredict_carma<N, GroupOf<N>::value>), grid, block, 0, st, d_par, c->d_rec, c->d_off, c->d_n, d_int, \
+                           d_int + W, c->k_long.as<long>(), d_tp, d_pm, d_pv, c->k_sing.as<int>());                               \
+        break;
+                CARMA_MPR(2) CARMA_MPR(3) CARMA_MPR(4) CARMA_MPR(5) CARMA_MPR(6) CARMA_MPR(7)
+#undef CARMA_MPR
+            default: return CARMA_EINVAL;
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(pmean + t0, d_pm, sizeof(double) * (size_t)T, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(pvar + t0, d_pv, sizeof(double) * (size_t)T, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(sing.data(), c->k_sing.p, sizeof(int) * (size_t)M, hipMemcpyDeviceToHost, st);
+    }
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return hip_fail(e, "carma_mpredict");
+    if (singular) std::memcpy(singular, sing.data(), sizeof(int) * (size_t)M);
     return CARMA_OK;
 }
 

@@ -18,10 +18,23 @@
 
 namespace carma {
 
-// y must already be centred and yerr^2 scaled: series records are used as they are.
+// The returned mean of a prediction on uncentred data: pm + mu as an addition of its own.  Contraction is off here: fused with
+// the product that forms pm (fma(ypm, 1 / yprec, mu)) the mean would be rounded once instead of twice and differ in the last
+// bit from the single-series call on centred data plus mu.  (Not pm + 0.0 either: that would turn a mean of -0.0 into +0.0.)
+CARMA_DEV double add_back_mu(double pm, double mu)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    return mu != 0.0 ? pm + mu : pm;
+}
+
+// yerr^2 must already be scaled: series records are used as they are, but for mu -- subtracted from a record's y where it is
+// read and added back to the returned mean (the multi-series contexts keep y uncentred; y - 0.0 is exact, so callers with
+// centred data, mu = 0, keep their bits).
 template <int P, int G, class GrpT>
 CARMA_DEV void predict_run(const GrpT& g, const Model<P>& m, const double4* __restrict__ series, int n, double time,
-                           double* pmean, double* pvar, bool* singular)
+                           double* pmean, double* pvar, bool* singular, double mu = 0.0)
 {
     FilterConsts<P> fc;
     filter_reset<P, G>(g, m, fc);
@@ -50,7 +63,7 @@ CARMA_DEV void predict_run(const GrpT& g, const Model<P>& m, const double4* __re
     } else {
         const double4 r0 = series[0];
         den = s0 + r0.z;                 // var(0)  (:180-182)
-        resid = r0.y;                    // innovation (:184)
+        resid = r0.y - mu;               // innovation (:184)
         t_a = r0.w;
     }
     for (int i = 1; i <= n; i++) {
@@ -101,11 +114,11 @@ CARMA_DEV void predict_run(const GrpT& g, const Model<P>& m, const double4* __re
             amean = ypm * yprec;
         } else if (i < ip) {                                  // ordinary filter step (:207-213)
             den = s0 + Sw + rb.z;
-            resid = rb.y - Sx;
+            resid = (rb.y - mu) - Sx;
         } else {                                              // linear-filter coefficients (:309-313, :332-336)
             const double var_b = s0 + Sw + rb.z;
             yslope = Ss;
-            resid = rb.y - Sc;
+            resid = (rb.y - mu) - Sc;
             den = var_b;
             yprec += yslope * yslope / var_b;                 // :272-273, :277-278
             amean += yslope * resid / var_b;
@@ -114,13 +127,15 @@ CARMA_DEV void predict_run(const GrpT& g, const Model<P>& m, const double4* __re
     }
     const bool forecast = (ip == n);                          // :257-261
     *pvar = forecast ? ypv : 1.0 / yprec;                     // :281-282
-    *pmean = forecast ? ypm : amean / yprec;
+    const double pm = forecast ? ypm : amean / yprec;
+    *pmean = add_back_mu(pm, mu);
     *singular = fc.sing;
 }
 
 // CAR(1): one LANE per prediction time (kfilter.cpp:72-135, 51-69).
+// mu: as in predict_run.
 CARMA_DEV void predict_car1(double sigsqr, double omega, const double4* __restrict__ series, int n, double time,
-                            double* pmean, double* pvar)
+                            double* pmean, double* pvar, double mu = 0.0)
 {
     int ip = 0;
     while (ip < n && time > series[ip].w) ip++;
@@ -131,7 +146,7 @@ CARMA_DEV void predict_car1(double sigsqr, double omega, const double4* __restri
         const double rho = exp(-1.0 * omega * (bb.w - a.w));
         const double previous_var = var - a.z;
         const double var_ratio = previous_var / var;
-        mean = rho * mean + rho * var_ratio * (a.y - mean);
+        mean = rho * mean + rho * var_ratio * ((a.y - mu) - mean);
         var = sv * (1.0 - rho * rho) + rho * rho * previous_var * (1.0 - var_ratio) + bb.z;
     }
     double ypm, ypv;
@@ -143,11 +158,11 @@ CARMA_DEV void predict_car1(double sigsqr, double omega, const double4* __restri
         const double rho = exp(-(time - a.w) * omega);
         const double previous_var = var - a.z;
         const double var_ratio = previous_var / var;
-        ypm = rho * mean + rho * var_ratio * (a.y - mean);
+        ypm = rho * mean + rho * var_ratio * ((a.y - mu) - mean);
         ypv = sv * (1.0 - rho * rho) + rho * rho * previous_var * (1.0 - var_ratio);
     }
     if (ip == n) {
-        *pmean = ypm;
+        *pmean = add_back_mu(ypm, mu);
         *pvar = ypv;
         return;
     }
@@ -158,21 +173,22 @@ CARMA_DEV void predict_car1(double sigsqr, double omega, const double4* __restri
     double yslope = exp(-fabs(cur.w - time) * omega);
     var = sv * (1.0 - yslope * yslope) + cur.z;
     yprec += yslope * yslope / var;
-    ypm += yslope * (cur.y - yconst) / var;
+    ypm += yslope * ((cur.y - mu) - yconst) / var;
     for (int k = ip + 1; k < n; k++) {
         const double4 nx = series[k];
         const double rho = exp(-1.0 * (nx.w - cur.w) * omega);
         const double previous_var = var - cur.z;
         const double var_ratio = previous_var / var;
         yslope *= rho * (1.0 - var_ratio);
-        yconst = yconst * rho * (1.0 - var_ratio) + rho * var_ratio * cur.y;
+        yconst = yconst * rho * (1.0 - var_ratio) + rho * var_ratio * (cur.y - mu);
         var = sv * (1.0 - rho * rho) + rho * rho * previous_var * (1.0 - var_ratio) + nx.z;
         yprec += yslope * yslope / var;
-        ypm += yslope * (nx.y - yconst) / var;
+        ypm += yslope * ((nx.y - mu) - yconst) / var;
         cur = nx;
     }
     *pvar = 1.0 / yprec;
-    *pmean = ypm * (1.0 / yprec);
+    const double pm = ypm * (1.0 / yprec);
+    *pmean = add_back_mu(pm, mu);
 }
 
 }  // namespace carma

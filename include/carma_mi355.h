@@ -124,6 +124,23 @@ int carma_tune_set(const char* name, long value);
  * carma_mle_batched_ms: carma_mle_batched with start i on series series[i] and its own box lo / hi = [B][d] (NULL or
  *   non-finite entries = unbounded); every start's evaluations go through carma_mlogdensity_batch, all starts advance in
  *   lock-step in the same launches.
+ * carma_mkfilter: KalmanFilterp::Filter / KalmanFilter1::Filter of M ITEMS in one launch; item i is the model (sigsqr[i],
+ *   omega_re_im[i], ma[i]) on series series[i] of the context, whose order p the models share.  Several items may name one
+ *   series, a series may have none.  omega_re_im = [M][p][2], roots in any order but closed under conjugation; ma = [M][nma],
+ *   1 <= nma <= p, zero padded to p inside; mu = [M] or NULL (0): subtracted from y and added back to the mean; yerr is used
+ *   as given.  p = 1: omega_re_im = [M][2] holds the root (-omega, 0) and ma / nma are ignored.  The output is ragged: item
+ *   i has n_i = carma_mctx_n(h, series[i]) means and variances at mean / var [off[i], off[i] + n_i), off[0] = 0, off[i+1] =
+ *   off[i] + n_i, items in the caller's order (the caller allocates the sum of the n_i); out_offsets = [M+1] or NULL
+ *   receives off.  singular = [M] or NULL: 1 where an item has a repeated AR root (its rows are then not meaningful); the
+ *   other items are not affected.  One item per lane (kfilter_lane, car1_filter): an item's rows have the bits
+ *   carma_kfilter_batch_carma gives for that model on that series alone, whatever else the call holds.
+ * carma_mpredict: Predict of the same kind of items, item i at the times tpred[toff[i] .. toff[i+1]) (toff = [M+1],
+ *   non-decreasing; an item without times is legal); pmean / pvar are indexed as tpred.  One lane group per (item, time)
+ *   (CAR(1): one lane): the bits of carma_predict_carma / carma_predict_car1 on the series centred by mu, plus mu.
+ *   singular as above, set by an item's predictions (an item without times reports 0).
+ *   Both: a series index out of range, roots not closed under conjugation, nma outside 1..p, M < 1 and a decreasing toff are
+ *   CARMA_EINVAL before any device work, with the item's index in carma_last_error(); the context stays usable.  The
+ *   per-call device buffers belong to the context and grow on demand.
  */
 typedef struct carma_mctx carma_mctx;
 carma_mctx* carma_mctx_create(const double* time, const double* y, const double* yerr, const long* offsets /* [S+1] */,
@@ -137,6 +154,14 @@ int carma_mctx_get_prior(const carma_mctx* h, int s, double* out3 /* max_stdev, 
 int carma_mlogdensity_batch(carma_mctx* h, const double* theta /* [B][d] */, const int* series /* [B] */, int B,
                             int ignore_prior, double* out /* [B] */);
 int carma_mlogdensity_kernel_name(const carma_mctx* h, char* buf, int len);
+int carma_mkfilter(carma_mctx* h, const int* series /* [M] */, int M, const double* sigsqr /* [M] */,
+                   const double* omega_re_im /* [M][p][2] */, const double* ma /* [M][nma] */, int nma,
+                   const double* mu /* [M] or NULL */, double* mean, double* var, long* out_offsets /* [M+1] or NULL */,
+                   int* singular /* [M] or NULL */);
+int carma_mpredict(carma_mctx* h, const int* series /* [M] */, int M, const double* sigsqr /* [M] */,
+                   const double* omega_re_im /* [M][p][2] */, const double* ma /* [M][nma] */, int nma,
+                   const double* mu /* [M] or NULL */, const double* tpred, const long* toff /* [M+1] */, double* pmean,
+                   double* pvar, int* singular /* [M] or NULL */);
 int carma_mle_batched_ms(carma_mctx* h, const double* x0 /* [B][d] */, const int* series /* [B] */, int B,
                          const double* lo /* [B][d] */, const double* hi /* [B][d] */, int maxiter, int mem, double ftol,
                          double gtol, double fd_step, int ignore_prior, double* x, double* fun, int* nit, int* nfev,
