@@ -295,3 +295,51 @@ extern "C" void emu_predict_car1(double sigsqr, double omega, const double* seri
 }
 
 
+// ---------------------------------------------------------------------------------------------
+// The lane-group primitives of grp_emu.h on their own (tests/test_devprim_cpu.py holds the numpy restatements of
+// tests/devprim_ref.py to them; the device header is held to the same restatements on the GPU).
+// v: [G] one value per lane;  sum_out: [G] Grp<G>::sum in every lane
+template <int G>
+static void grp_sum_one(const double* v, double* sum_out)
+{
+    run_group<G>([&](const Grp<G>& g) { sum_out[g.lane()] = g.sum(v[g.lane()]); });
+}
+
+extern "C" int emu_grp_sum(int G, const double* v, double* sum_out)
+{
+    switch (G) {
+        case 2: grp_sum_one<2>(v, sum_out); break;
+        case 4: grp_sum_one<4>(v, sum_out); break;
+        case 8: grp_sum_one<8>(v, sum_out); break;
+        case 16: grp_sum_one<16>(v, sum_out); break;
+        default: return -1;
+    }
+    return 0;
+}
+
+// c, s: [16];  D, mm: [16][P] -- Grp<16>::row_colmix in the 16 lanes of one row
+template <int P>
+static void row_colmix_one(const double* c, const double* s, const double* D, double* mm)
+{
+    run_group<16>([&](const Grp<16>& g) {
+        const int r = g.lane();
+        double d[P], m[P];
+        for (int j = 0; j < P; j++) d[j] = D[r * P + j];
+        g.template row_colmix<P>(m, c[r], s[r], d);
+        for (int j = 0; j < P; j++) mm[r * P + j] = m[j];
+    });
+}
+
+extern "C" int emu_row_colmix(int P, const double* c, const double* s, const double* D, double* mm)
+{
+    switch (P) {
+        case 2: row_colmix_one<2>(c, s, D, mm); break;
+        case 3: row_colmix_one<3>(c, s, D, mm); break;
+        case 4: row_colmix_one<4>(c, s, D, mm); break;
+        case 5: row_colmix_one<5>(c, s, D, mm); break;
+        case 6: row_colmix_one<6>(c, s, D, mm); break;
+        case 7: row_colmix_one<7>(c, s, D, mm); break;
+        default: return -1;
+    }
+    return 0;
+}

@@ -199,3 +199,92 @@ def test_sample_dictionary_of_a_device_run_sampler(cpa, readme):
     idx = (np.arange(57) * (400 / 57)).astype(int)
     want = orc.post.psd_band(s.get_samples("ar_coefs")[idx], s.get_samples("ma_coefs")[idx], want_sig[idx], f, [2.5, 50.0, 97.5])
     np.testing.assert_allclose(np.c_[lo2, med2, hi2], want, rtol=1e-8)
+
+
+PSD_NS = 257
+
+
+def _psd_master_freq():
+    return np.r_[0.0, np.exp(np.linspace(np.log(1e-4), np.log(10.0), 16))]
+
+
+def _psd_truth(ar, ma, sig, freq):
+    """sigma^2 |delta(2 pi i f)|^2 / |alpha(2 pi i f)|^2 in mpmath (50 digits) and the Horner condition number
+    cond = sum |a_k w^k| / |alpha| + sum |b_k w^k| / |delta|; [nf, ns] each.  ar highest order first, ma lowest first."""
+    import mpmath
+    ctx = mpmath.mp.clone()
+    ctx.dps = 50
+    val, cond = np.empty((freq.size, ar.shape[0])), np.empty((freq.size, ar.shape[0]))
+
+    def poly(coefs, w):                                      # lowest order first; z = i w: even powers real, odd imaginary
+        re = im = mag = ctx.mpf(0)
+        wk = ctx.mpf(1)
+        for k, c in enumerate(coefs):
+            t = ctx.mpf(float(c)) * wk
+            sgn = -1 if (k // 2) % 2 else 1
+            if k % 2:
+                im += sgn * t
+            else:
+                re += sgn * t
+            mag += abs(t)
+            wk *= w
+        return re * re + im * im, mag
+
+    for i, f in enumerate(freq):
+        w = 2 * ctx.pi * ctx.mpf(float(f))
+        for s in range(ar.shape[0]):
+            a2, amag = poly(ar[s, ::-1], w)
+            d2, dmag = poly(ma[s], w)
+            val[i, s] = float(ctx.mpf(float(sig[s])) ** 2 * d2 / a2)
+            cond[i, s] = float(amag / ctx.sqrt(a2) + dmag / ctx.sqrt(d2))
+    return val, cond
+
+
+@pytest.mark.parametrize("nar", [2, 3, 4, 5, 6, 7, 8])
+def test_psd_grid_every_order_around_the_frequency_tile(cpa, readme, nar):
+    """k_psd_grid at every (nar, nma) the C entry admits below nar (nar AR coefficients, nma MA coefficients), 257 samples,
+    and 1, 7, 8, 9, 16, 17 frequencies -- either side of its tile of 8 frequencies per lane -- out of 0 and 16 log-spaced
+    frequencies from 1e-4 to 10.  Against mpmath within 4 (nar + nma) 2^-53 cond, cond = sum |a_k w^k| / |alpha| +
+    sum |b_k w^k| / |delta|, the forward-error bound of Horner's rule (twice, for the squared moduli); where cond < 100 also
+    within 1e-12 of the numpy restatement.  Every row holds ns finite-or-inf values, and a request of nf rows leaves the row
+    behind them alone."""
+    import ctypes as C
+    from carma_pack_amd import _lib, carma_pack as cp
+    from helpers import prior_like_theta
+    t, y = readme["t"], readme["y"]
+    master = _psd_master_freq()
+    p = nar - 1
+    for nma in range(1, nar):
+        q = nma - 1
+        rng = np.random.default_rng(100 * nar + nma)
+        if p == 1:
+            ar = np.c_[np.ones(PSD_NS), np.exp(rng.normal(-3.0, 1.0, PSD_NS))]
+            ma, var = np.ones((PSD_NS, 1)), rng.uniform(0.5, 3.0, PSD_NS) ** 2
+            sig = np.sqrt(2.0 * ar[:, 1] * var)
+        else:
+            th = np.array([prior_like_theta(rng, p, q, t, y) for _ in range(PSD_NS)])
+            roots, ar, ma = _derived(cp, th, p, q)
+            sig = orc.post.sigma_noise(roots, ma, th[:, 0] ** 2)
+            sig[~np.isfinite(sig)] = 1.0
+        assert ar.shape == (PSD_NS, nar) and ma.shape == (PSD_NS, nma)
+        truth, cond = _psd_truth(ar, ma, sig, master)
+        for nf in (1, 7, 8, 9, 16, 17):
+            idx = np.round(np.linspace(0, 16, nf)).astype(int)
+            freq = master[idx]
+            band, grid = _lib.psd_band(ar, ma, sig, freq, [50.0], return_samples=True)
+            assert grid.shape == (nf, PSD_NS) and not np.isnan(grid).any()
+            want, cnd = truth[idx], cond[idx]
+            err = np.abs(grid - want) / want
+            bound = 4 * (nar + nma) * 2.0 ** -53 * cnd
+            assert (err <= bound).all(), (nar, nma, nf, float((err / bound).max()))
+            easy = cnd < 100.0
+            np.testing.assert_allclose(grid[easy], orc.post.psd_samples(ar, ma, sig, freq)[easy], rtol=1e-12)
+            # the same request into a buffer with one more row: the sentinel row stays
+            buf = np.full((nf + 1, PSD_NS), -777.0)
+            bnd = np.empty((nf, 1))
+            args = [_lib.as_f64(x) for x in (ar, ma, sig, freq, np.array([50.0]))]
+            rc = _lib.lib.carma_psd_band(nar, nma, _lib.ptr(args[0]), _lib.ptr(args[1]), _lib.ptr(args[2]), PSD_NS, _lib.ptr(args[3]),
+                                         nf, _lib.ptr(args[4]), 1, _lib.ptr(bnd), buf.ctypes.data_as(C.POINTER(C.c_double)),
+                                         _lib.default_device())
+            assert rc == 0
+            assert (buf[nf] == -777.0).all() and np.array_equal(buf[:nf], grid)
