@@ -185,6 +185,49 @@ def run_mcmc_carma(sample_size, burnin, time, y, yerr, p, q, nwalkers, do_zcarma
     return obj
 
 
+class SetRunSampler(object):
+    """One run of a multi-series sampler call (MultiContext.pt_run) seen as the sampler object CarmaSample / Car1Sample wrap:
+    the coldest chain of the run's first replica, like the objects run_mcmc_car1 / run_mcmc_carma return.  loglik: the
+    log-densities of that trace with the prior bounds ignored, when the caller has evaluated them for all runs in one launch
+    (CarmaModelSet.run_mcmc) -- getLogDensityBatch hands them out instead of launching again."""
+
+    def __init__(self, mctx, series, samples, logposts, loglik=None, accept_rate=None, swap_rate=None):
+        self._mctx, self._series = mctx, int(series)
+        self.p, self.q = mctx.p, mctx.q
+        self._all_samples, self._all_logposts = samples, logposts          # [R][S][d], [R][S]
+        self._samples, self._logposts = samples[0], logposts[0]
+        self._loglik = loglik
+        self._ignore_prior = False
+        self.accept_rate, self.swap_rate = accept_rate, swap_rate
+
+    def getSamples(self):
+        return vecvecD(vecD(row) for row in self._samples.tolist())
+
+    def GetLogLikes(self):
+        return vecD(self._logposts.tolist())
+
+    def getAllSamples(self):
+        return self._all_samples, self._all_logposts
+
+    def SetMLE(self, ignore_prior):
+        self._ignore_prior = bool(ignore_prior)
+
+    def getLogPrior(self, theta):
+        # carpack.hpp:118-126 with measerr_dof = 50 (carpack.hpp:63): host arithmetic
+        s = float(_arr(theta)[1])
+        return -0.5 * 50.0 / s - (1.0 + 50.0 / 2.0) * np.log(s)
+
+    def getLogDensity(self, theta):
+        return float(self.getLogDensityBatch(_arr(theta).reshape(1, -1))[0])
+
+    def getLogDensityBatch(self, thetas):
+        thetas = np.asarray(thetas, dtype=float).reshape(-1, self._mctx.d)
+        if (self._loglik is not None and self._ignore_prior and thetas.shape == self._samples.shape
+                and np.array_equal(thetas, self._samples)):
+            return self._loglik
+        return self._mctx.logdensity(thetas, self._series, ignore_prior=self._ignore_prior)
+
+
 class _KalmanBase(object):
     def __init__(self, time, y, yerr):
         self._t, self._y, self._e = _arr(time), _arr(y), _arr(yerr)

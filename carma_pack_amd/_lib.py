@@ -137,6 +137,20 @@ def _load():
     L.carma_mle_batched_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                        C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]
+    L.carma_mpt_create.argtypes = [C.c_void_p, _ip, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_uint64]
+    L.carma_mpt_start.argtypes = [C.c_void_p, _dp]
+    L.carma_mpt_set_chains.argtypes = [C.c_void_p, _dp, _dp]
+    L.carma_mpt_get_chains.argtypes = [C.c_void_p, _dp, _dp]
+    L.carma_mpt_get_factor.argtypes = [C.c_void_p, _dp]
+    L.carma_mpt_set_factor.argtypes = [C.c_void_p, _dp]
+    L.carma_mpt_iterate.argtypes = [C.c_void_p, C.c_long, C.c_int]
+    L.carma_mpt_sample.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp]
+    L.carma_mpt_stats.argtypes = [C.c_void_p, _dp, _dp, C.c_int]
+    L.carma_mpt_iterations_done.argtypes = [C.c_void_p]
+    L.carma_mpt_iterations_done.restype = C.c_long
+    L.carma_mpt_logdensity.argtypes = [C.c_void_p, _dp, _dp]
+    L.carma_mpt_kernel_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    L.carma_mpt_run.argtypes = [C.c_void_p, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_uint64, _dp, _dp]
     L.carma_logprior.argtypes = [C.c_void_p, _dp]
     L.carma_logprior.restype = C.c_double
     L.carma_kfilter_batch_carma.argtypes = [_dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp,
@@ -210,7 +224,9 @@ EXPORTS = [
     "carma_pt_boundary_check", "carma_pt_sweep", "carma_pt_kernel_in_use", "carma_pt_row_pipeline", "carma_pt_debug_draws", "carma_pt_get_factor",
     "carma_pt_set_factor", "carma_tune_set", "carma_mctx_create", "carma_mctx_destroy", "carma_mctx_nseries", "carma_mctx_dim",
     "carma_mctx_n", "carma_mctx_get_data", "carma_mctx_get_prior", "carma_mlogdensity_batch", "carma_mlogdensity_kernel_name",
-    "carma_mle_batched_ms", "carma_mkfilter", "carma_mpredict",
+    "carma_mle_batched_ms", "carma_mkfilter", "carma_mpredict", "carma_mpt_create", "carma_mpt_start", "carma_mpt_set_chains",
+    "carma_mpt_get_chains", "carma_mpt_get_factor", "carma_mpt_set_factor", "carma_mpt_iterate", "carma_mpt_sample",
+    "carma_mpt_stats", "carma_mpt_iterations_done", "carma_mpt_logdensity", "carma_mpt_kernel_name", "carma_mpt_run",
 ]
 
 
@@ -772,6 +788,114 @@ class MultiContext:
                                        nit.ctypes.data_as(C.c_void_p), nfev.ctypes.data_as(C.c_void_p),
                                        status.ctypes.data_as(C.c_void_p)), "carma_mle_batched_ms")
         return x, fun, nit, nfev, status
+
+    # ---- parallel-tempering sampler over many series (carma_mpt_*) -------------------------------
+    def _runs(self, series):
+        w = np.asarray(series, dtype=np.int64).ravel()
+        if w.size < 1:
+            raise ValueError("need at least one run")
+        return np.ascontiguousarray(w, dtype=np.int32)
+
+    def _init_rows(self, init, M):
+        if init is None:
+            return None
+        a = as_f64(init)
+        if a.shape != (M, self.d):
+            raise ValueError("init must be [%d, %d] (one row per run), got %r" % (M, self.d, a.shape))
+        return a
+
+    def pt_create(self, series, ntemps, nreplicas, adapt_iters, seed=0, temperatures=None):
+        """One sampler run (nreplicas ladders of ntemps chains) per entry of `series` (indices into this context, any order,
+        repeats allowed), all advancing in the same launches (carma_mpt_create)."""
+        w = self._runs(series)
+        tt = as_f64(temperatures) if temperatures is not None else None
+        if tt is not None and tt.size != int(ntemps):
+            raise ValueError("temperatures must hold ntemps = %d values" % int(ntemps))
+        check(lib.carma_mpt_create(self._h, w.ctypes.data_as(_ip), w.size, int(ntemps), int(nreplicas),
+                                   ptr(tt) if tt is not None else None, int(adapt_iters), C.c_uint64(int(seed) & (2 ** 64 - 1))),
+              "carma_mpt_create")
+        self._mpt_shape = (int(w.size), int(nreplicas), int(ntemps))
+        self._mpt_series = w
+
+    def _mpt(self):
+        if getattr(self, "_mpt_shape", None) is None:
+            raise ValueError("call pt_create first")
+        return self._mpt_shape
+
+    def pt_start(self, init=None):
+        """Starting values (carma_mpt_start); init: None or [M, d], row j for every chain of run j where it is finite."""
+        M = self._mpt()[0]
+        a = self._init_rows(init, M)
+        check(lib.carma_mpt_start(self._h, ptr(a) if a is not None else None), "carma_mpt_start")
+
+    def pt_set_chains(self, theta, logpost=None):
+        M, R, T = self._mpt()
+        theta = as_f64(theta).reshape(M, R, T, self.d)
+        lp = as_f64(logpost).reshape(M, R, T) if logpost is not None else None
+        check(lib.carma_mpt_set_chains(self._h, ptr(theta), ptr(lp) if lp is not None else None), "carma_mpt_set_chains")
+
+    def pt_get_chains(self):
+        M, R, T = self._mpt()
+        theta, lp = np.empty((M, R, T, self.d)), np.empty((M, R, T))
+        check(lib.carma_mpt_get_chains(self._h, ptr(theta), ptr(lp)), "carma_mpt_get_chains")
+        return theta, lp
+
+    def pt_get_factor(self):
+        """The proposal factor of every chain, [M][R][T][d][d] (upper triangular)."""
+        M, R, T = self._mpt()
+        chol = np.empty((M, R, T, self.d, self.d))
+        check(lib.carma_mpt_get_factor(self._h, ptr(chol)), "carma_mpt_get_factor")
+        return chol
+
+    def pt_set_factor(self, chol):
+        M, R, T = self._mpt()
+        chol = as_f64(chol).reshape(M, R, T, self.d, self.d)
+        check(lib.carma_mpt_set_factor(self._h, ptr(chol)), "carma_mpt_set_factor")
+
+    def pt_iterate(self, niter, do_exchange=True):
+        check(lib.carma_mpt_iterate(self._h, int(niter), int(bool(do_exchange))), "carma_mpt_iterate")
+
+    def pt_sample(self, nsamples, thin=1):
+        """(samples [M][R][nsamples][d], logposts [M][R][nsamples]) of the coldest chains."""
+        M, R, T = self._mpt()
+        samples, logposts = np.empty((M, R, int(nsamples), self.d)), np.empty((M, R, int(nsamples)))
+        check(lib.carma_mpt_sample(self._h, int(nsamples), int(thin), ptr(samples), ptr(logposts)), "carma_mpt_sample")
+        return samples, logposts
+
+    def pt_stats(self, reset=False):
+        M, R, T = self._mpt()
+        acc, swp = np.empty((M, R, T)), np.empty((M, R, T))
+        check(lib.carma_mpt_stats(self._h, ptr(acc), ptr(swp), int(bool(reset))), "carma_mpt_stats")
+        return acc, swp
+
+    def pt_iterations_done(self):
+        return lib.carma_mpt_iterations_done(self._h)
+
+    def pt_logdensity(self, theta):
+        """Log-densities of chain states [M][R][T][d], each on its run's series, through the sampler's own log-density kernel."""
+        M, R, T = self._mpt()
+        theta = as_f64(theta).reshape(M, R, T, self.d)
+        out = np.empty((M, R, T))
+        check(lib.carma_mpt_logdensity(self._h, ptr(theta), ptr(out)), "carma_mpt_logdensity")
+        return out
+
+    def pt_kernel_name(self):
+        buf = C.create_string_buffer(128)
+        check(lib.carma_mpt_kernel_name(self._h, buf, 128), "carma_mpt_kernel_name")
+        return buf.value.decode()
+
+    def pt_run(self, series, ntemps, nreplicas, sample_size, burnin, thin=1, init=None, seed=0):
+        """Whole Sampler::Run of every run: (samples [M][R][S][d], logposts [M][R][S]) of the coldest chains (carma_mpt_run)."""
+        w = self._runs(series)
+        a = self._init_rows(init, w.size)
+        samples = np.empty((w.size, int(nreplicas), int(sample_size), self.d))
+        logposts = np.empty((w.size, int(nreplicas), int(sample_size)))
+        check(lib.carma_mpt_run(self._h, w.ctypes.data_as(_ip), w.size, int(ntemps), int(nreplicas), int(sample_size), int(burnin),
+                                int(thin), ptr(a) if a is not None else None, C.c_uint64(int(seed) & (2 ** 64 - 1)), ptr(samples),
+                                ptr(logposts)), "carma_mpt_run")
+        self._mpt_shape = (int(w.size), int(nreplicas), int(ntemps))
+        self._mpt_series = w
+        return samples, logposts
 
 
 def kfilter_car1(time, y, yerr, sigsqr, omega, device=None):

@@ -680,6 +680,7 @@ class CarmaModelSet(object):
         self.nseries = len(self.models)
         self._mctx = {}
         self.timing = {}
+        self.mcmc_samples = None
 
     def context(self, p, q):
         """The MultiContext of order (p, q) over every series (created once; the prior bound max_stdev of the samplers that
@@ -706,18 +707,89 @@ class CarmaModelSet(object):
         out = self.context(self.p, self.q).logdensity(rows, w, ignore_prior=self.p > 1)
         return float(out[0]) if theta.ndim == 1 else out
 
+    def run_mcmc(self, nsamples, nburnin=None, ntemperatures=None, nthin=1, init=None, nreplicas=1, seed=None):
+        """CarmaModel.run_mcmc of EVERY series in one sampler run (MultiContext.pt_run): all series' ladders advance in the
+        same launches, one chain per lane.  Defaults as CarmaModel.run_mcmc: ntemperatures = max(10, p + q) (p = 1: one
+        chain at temperature 1), nburnin = nsamples / 2.  init: None or [S, d], row s for series s.  Returns a list of S
+        CarmaSample (p = 1: Car1Sample) in the caller's order, also kept as self.mcmc_samples and models[s].mcmc_sample."""
+        p, q, S = self.p, self.q, self.nseries
+        d = 4 if p == 1 else 3 + p + q
+        if int(nsamples) < 1:
+            raise ValueError("nsamples must be at least 1")
+        if int(nthin) < 1:
+            raise ValueError("nthin must be at least 1")
+        if int(nreplicas) < 1:
+            raise ValueError("nreplicas must be at least 1")
+        if ntemperatures is None:
+            ntemperatures = max(10, p + q)
+        if not 1 <= int(ntemperatures) <= 64:
+            raise ValueError("ntemperatures must be 1 ... 64 (a ladder is the lanes of one wave), got %d" % int(ntemperatures))
+        if p == 1:
+            ntemperatures = 1
+        if nburnin is None:
+            nburnin = int(nsamples) // 2
+        if int(nburnin) < 0:
+            raise ValueError("nburnin must not be negative")
+        if init is not None:
+            init = np.asarray(init, dtype=float)
+            if init.shape != (S, d):
+                raise ValueError("init must be [%d, %d] (one row per series), got %r" % (S, d, init.shape))
+        mc = self.context(p, q)
+        # longest series first: the ladders that share a wave then have similar lengths
+        order = np.argsort(-np.asarray(mc.n), kind="stable")
+        samples, logposts = mc.pt_run(order, int(ntemperatures), int(nreplicas), int(nsamples), int(nburnin), int(nthin),
+                                      init=None if init is None else init[order], seed=carmcmcLib._seed(seed))
+        acc, swp = mc.pt_stats()
+        # the "loglik" column (prior bounds ignored) of all series' traces: one launch
+        loglik = None
+        if p > 1:
+            ns = samples.shape[2]
+            loglik = mc.logdensity(samples[:, 0].reshape(-1, d), np.repeat(order, ns), ignore_prior=True).reshape(S, ns)
+        out = [None] * S
+        for j, s in enumerate(order):
+            m = self.models[s]
+            run = carmcmcLib.SetRunSampler(mc, s, samples[j], logposts[j], None if loglik is None else loglik[j], acc[j], swp[j])
+            out[s] = Car1Sample(m.time, m.y, m.ysig, run) if p == 1 else CarmaSample(m.time, m.y, m.ysig, run, q=q)
+            m.mcmc_sample = out[s]
+        self.mcmc_samples = out
+        return out
+
+    def _set_starts(self, p, q, ntrials, seed):
+        """The starts of get_mle(starts="set"): CarmaModel._mle_problem's short tempered run (25 adapting iterations, one
+        sample, 10 temperatures -- 1 for p = 1 -- ntrials replicas) of ALL series as one multi-series run, then the same
+        post-processing per series."""
+        mc = self.context(p, q)
+        order = np.argsort(-np.asarray(mc.n), kind="stable")
+        samples, _ = mc.pt_run(order, 1 if p == 1 else 10, int(ntrials), 1, 25, 1, seed=carmcmcLib._seed(seed))
+        starts = np.empty((self.nseries, int(ntrials), mc.d))
+        starts[order] = samples[:, :, 0, :]
+        for s, m in enumerate(self.models):
+            rng = np.random.default_rng(seed)
+            starts[s, :, 1] = 1.0                            # initial guess for the error scale
+            for j, (lo, hi) in enumerate(m._mle_bounds(p, q)):
+                if lo is not None:
+                    out = (starts[s, :, j] < lo) | (starts[s, :, j] > hi)
+                    starts[s, out, j] = rng.uniform(lo, hi, int(out.sum()))
+        return starts
+
     def get_mle(self, p, q, ntrials=100, seed=None, starts=None, return_all=False):
         """CarmaModel.get_mle of every series.  starts None: each series' starts drawn exactly as CarmaModel.get_mle draws
-        them (a short tempered sampler run per series, same seed), else an array [S, ntrials, d].  All S x ntrials starts
-        are then optimised in ONE lock-step run.  Returns a list of S BatchResult (return_all: S lists of ntrials).
-        self.timing holds the seconds spent drawing starts and optimising."""
+        them (a short tempered sampler run per series, same seed); "set": all series' starts from ONE multi-series sampler
+        run with the same arguments (other draws than None gives -- the chains' random streams are keyed by their place in
+        the set's ensemble); else an array [S, ntrials, d].  All S x ntrials starts are then optimised in ONE lock-step run.
+        Returns a list of S BatchResult (return_all: S lists of ntrials).  self.timing holds the seconds spent drawing
+        starts and optimising."""
         import time as _time
         if not p > q:
             raise ValueError("Order of AR polynomial, p, must be larger than order of MA polynomial, q.")
+        if isinstance(starts, str) and starts != "set":
+            raise ValueError("starts must be None, 'set' or an array [S, ntrials, d], got %r" % starts)
         S = self.nseries
         t0 = _time.perf_counter()
         if starts is None:
             starts = np.stack([m._mle_problem(p, q, ntrials, seed)[1] for m in self.models])
+        elif isinstance(starts, str):
+            starts = self._set_starts(p, q, ntrials, seed)
         else:
             starts = np.asarray(starts, dtype=float)
             d = 4 if p == 1 else 3 + p + q

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <random>
 #include <vector>
 
 #include "carma_launch.h"
@@ -91,6 +92,10 @@ void set_prior_bounds(Prior& pr, const double* t, long n, double max_stdev);
 bool series_repeated_dt(const double* packed, long n);
 // AR roots in the order the KalmanFilterp-type kernels expect (carma_normalize_roots); CARMA_EINVAL unless closed under conjugation
 int normalize_roots(int p, const double* om, double* out);
+// starting values of the samplers (carma_pt_host.hip): one draw from the reference's starting-value distribution for a series
+// (sorted, distinct times), and the generator of a chain's draws -- keyed by the chain's global slot and the attempt
+void draw_start(const double* t, const double* y, int n, const Prior& pr, int p, int q, std::mt19937_64& rng, double* theta);
+std::mt19937_64 start_rng(uint64_t seed, uint64_t gslot, int round);
 int hip_fail(hipError_t e, const char* what);
 int select_device(int device);
 void pt_state_free(Ctx* c);

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <functional>
+
 #include "carma_types.h"
 
 namespace carma {
@@ -75,6 +77,12 @@ size_t pt_lane_scratch_doubles(int d, long nchain);
 hipError_t launch_pt_lane(int p, const PtLaunch& L, double* scratch, const double4* series, const Prior& pr,
                           const double* temps, double* theta, double* logpost, double* chol, unsigned* naccept,
                           unsigned* nswap, double* samples, double* sample_lp, int series_flags, bool load_factor, hipStream_t st);
+// the same loop with the log-density step ("K1") supplied by the caller: k1(thn [nc][d], nc, ll [nc], st) enqueues the
+// log-densities of the nc = R * T proposals (chain-major, chain = ladder * T + temperature) on st
+using PtLaneK1 = std::function<hipError_t(const double* thn, long nc, double* ll, hipStream_t st)>;
+hipError_t launch_pt_lane_k1(int p, const PtLaunch& L, double* scratch, const PtLaneK1& k1, const double* temps, double* theta,
+                             double* logpost, double* chol, unsigned* naccept, unsigned* nswap, double* samples, double* sample_lp,
+                             bool load_factor, hipStream_t st);
 // the lane sampler keeps the proposal factors in its chain-minor working state between calls; this writes them to the chain-major
 // array the other entry points read (carma_pt_get_factor, the shard packers): enqueued on st
 hipError_t pt_lane_store_factor(int d, int T, int R, double* scratch, double* chol, hipStream_t st);

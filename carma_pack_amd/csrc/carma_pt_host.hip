@@ -56,14 +56,14 @@ static double pop_var(const std::vector<double>& y)
     return sq / y.size() - mean * mean;
 }
 
-static double sample_var(const std::vector<double>& y)   // arma::var
+static double sample_var(const double* y, int n)   // arma::var
 {
     double mean = 0;
-    for (double v : y) mean += v;
-    mean /= y.size();
+    for (int i = 0; i < n; i++) mean += y[i];
+    mean /= (size_t)n;
     double s = 0;
-    for (double v : y) s += (v - mean) * (v - mean);
-    return s / (y.size() - 1);
+    for (int i = 0; i < n; i++) s += (y[i] - mean) * (y[i] - mean);
+    return s / ((size_t)n - 1);
 }
 
 static int chunk_iters(const Ctx* c)
@@ -83,10 +83,9 @@ static int chunk_iters(const Ctx* c)
     return (int)std::max(1.0, std::min(4096.0, 250000.0 / est_us));
 }
 
-// One draw from the reference's starting-value distribution.
-static void draw_start(const Ctx* c, std::mt19937_64& rng, double* theta)
+// One draw from the reference's starting-value distribution for the series (t, y)[n] (sorted, distinct times) with prior pr.
+void draw_start(const double* t, const double* y, int n, const Prior& pr, int p, int q, std::mt19937_64& rng, double* theta)
 {
-    const int n = c->n, p = c->p, q = c->q;
     std::normal_distribution<double> norm(0.0, 1.0);
     std::uniform_real_distribution<double> unif(0.0, 1.0);
     auto scaled_inv_chisq = [&](int dof, double ssqr) {       // src/random.cpp:180-186
@@ -94,11 +93,11 @@ static void draw_start(const Ctx* c, std::mt19937_64& rng, double* theta)
         return ssqr / chi(rng) * (double)dof;
     };
     double ymean = 0;
-    for (double v : c->y) ymean += v;
+    for (int i = 0; i < n; i++) ymean += y[i];
     ymean /= n;
-    const double yvar = scaled_inv_chisq(n - 1, sample_var(c->y));
+    const double yvar = scaled_inv_chisq(n - 1, sample_var(y, n));
     const double mu = ymean + std::sqrt(yvar) / n * norm(rng);
-    double scale = scaled_inv_chisq((int)c->pr.measerr_dof, 1.0);
+    double scale = scaled_inv_chisq((int)pr.measerr_dof, 1.0);
     scale = std::max(std::min(scale, 1.99), 0.51);
     theta[0] = std::sqrt(yvar);
     theta[1] = scale;
@@ -106,16 +105,16 @@ static void draw_start(const Ctx* c, std::mt19937_64& rng, double* theta)
     if (p == 1) {
         // CAR1::StartingValue (src/carpack.cpp:38-81)
         std::vector<double> dt(n - 1);
-        for (int i = 1; i < n; i++) dt[i - 1] = c->t[i] - c->t[i - 1];
+        for (int i = 1; i < n; i++) dt[i - 1] = t[i] - t[i - 1];
         std::sort(dt.begin(), dt.end());
         const double med = (dt.size() % 2) ? dt[dt.size() / 2] : 0.5 * (dt[dt.size() / 2 - 1] + dt[dt.size() / 2]);
         double lw = -1.0 * std::log(med * (1.0 + 49.0 * unif(rng)));
-        lw = std::min(lw, c->pr.max_freq);     // sic (carpack.cpp:56)
+        lw = std::min(lw, pr.max_freq);     // sic (carpack.cpp:56)
         theta[3] = lw;
         return;
     }
     // CARp::StartingAR (src/carpack.cpp:268-311)
-    const double min_freq = c->pr.min_freq, max_freq = c->pr.max_freq;
+    const double min_freq = pr.min_freq, max_freq = pr.max_freq;
     const int nc = (p + 1) / 2;
     std::vector<double> cent(nc), width(nc);
     for (int i = 0; i < nc; i++) cent[i] = std::exp(std::log(max_freq / min_freq) * unif(rng) + std::log(min_freq));
@@ -134,6 +133,16 @@ static void draw_start(const Ctx* c, std::mt19937_64& rng, double* theta)
     if (p % 2 == 1) theta[3 + p - 1] = std::log(2.0 * M_PI * width[p / 2]);
     // CARMA::StartingMA (src/carpack.cpp:515-519)
     for (int i = 0; i < q; i++) theta[3 + p + i] = std::fabs(norm(rng));
+}
+
+// The generator of a chain's starting-value draws: keyed by (seed, the chain's GLOBAL slot, attempt)
+std::mt19937_64 start_rng(uint64_t seed, uint64_t gslot, int round)
+{
+    uint64_t z = seed * 0x9E3779B97F4A7C15ull + 0x1234567ull;
+    z ^= (gslot + 1) * 0xBF58476D1CE4E5B9ull;
+    z ^= ((uint64_t)round + 1) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return std::mt19937_64(z * 0xD6E8FEB86659FD93ull + 0x2545F4914F6CDD1Dull);
 }
 
 static PtLaunch pt_launch_args(const Ctx* c, long ch, int do_exchange, int thin, long save_offset)
@@ -557,11 +566,7 @@ int carma_pt_start(carma_ctx* h, const double* init, int ninit)
     // exactly as the single-process run does.
     auto chain_rng = [&](size_t k, int round) {
         const uint64_t gslot = ((uint64_t)s->replica0 + k / (size_t)s->T) * (uint64_t)s->T_global + s->slot0 + k % (size_t)s->T;
-        uint64_t z = s->seed * 0x9E3779B97F4A7C15ull + 0x1234567ull;
-        z ^= (gslot + 1) * 0xBF58476D1CE4E5B9ull;
-        z ^= ((uint64_t)round + 1) * 0x94D049BB133111EBull;
-        z ^= z >> 31;
-        return std::mt19937_64(z * 0xD6E8FEB86659FD93ull + 0x2545F4914F6CDD1Dull);
+        return start_rng(s->seed, gslot, round);
     };
     for (int round = 0; round < 4000; round++) {
         std::vector<size_t> todo;
@@ -571,7 +576,7 @@ int carma_pt_start(carma_ctx* h, const double* init, int ninit)
         std::vector<double> cand(todo.size() * d), out(todo.size());
         for (size_t i = 0; i < todo.size(); i++) {
             std::mt19937_64 rng = chain_rng(todo[i], round);
-            draw_start(c, rng, &cand[i * d]);
+            draw_start(c->t.data(), c->y.data(), c->n, c->pr, c->p, c->q, rng, &cand[i * d]);
         }
         int rc = logdensity_of_chain_states(h, cand.data(), todo.size(), d, out.data());
         if (rc != CARMA_OK) return rc;

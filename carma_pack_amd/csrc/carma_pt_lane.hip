@@ -350,9 +350,12 @@ static hipError_t ram_launch_d(int d, F&& f)
 // either end.  The iterations, the save slots and the Philox keys are those of launch_pt for the same PtLaunch.
 // load_factor: the chain-minor factors are not current (first call, or the chain-major copy was written): take them from chol.  The
 // chain-major copy is NOT written back here -- pt_lane_store_factor does that for whoever wants to read it.
-hipError_t launch_pt_lane(int p, const PtLaunch& L, double* scratch, const double4* series, const Prior& pr,
-                          const double* temps, double* theta, double* logpost, double* chol, unsigned* naccept,
-                          unsigned* nswap, double* samples, double* sample_lp, int series_flags, bool load_factor, hipStream_t st)
+// K1 is the caller's: k1(thn [nc][d], nc, ll [nc], st) enqueues the log-densities of the nc proposals.  The bookkeeping kernels never
+// touch a series, so whoever supplies K1 decides what a chain is evaluated on (launch_pt_lane below: one series for all chains;
+// carma_mseries.hip: every ladder on a series of its own).
+hipError_t launch_pt_lane_k1(int p, const PtLaunch& L, double* scratch, const PtLaneK1& k1, const double* temps, double* theta,
+                             double* logpost, double* chol, unsigned* naccept, unsigned* nswap, double* samples, double* sample_lp,
+                             bool load_factor, hipStream_t st)
 {
     (void)hipGetLastError();
     if (p < 1 || L.T < 1 || L.T > 64 || L.d < 4 || L.d > RAM_DMAX || (p == 1) != (L.d == 4)) return hipErrorInvalidValue;
@@ -379,9 +382,7 @@ hipError_t launch_pt_lane(int p, const PtLaunch& L, double* scratch, const doubl
             e = ram_launch_d(L.d, [&](auto dc) {
                 hipLaunchKernelGGL((k_ram_propose<decltype(dc)::value>), dim3(grid), dim3(256), 0, st, Li, S);
             });
-        if (e == hipSuccess)
-            e = p == 1 ? launch_logdens_car1(S.thn, (int)nc, series, L.n, pr, S.ll, st)
-                       : launch_logdens_carma(p, S.thn, (int)nc, L.d, L.q, series, L.n, pr, 0, S.ll, st, series_flags);
+        if (e == hipSuccess) e = k1(S.thn, nc, S.ll, st);
         if (e == hipSuccess) {
             const bool next = fused && it + 1 < L.niter;
             e = ram_launch_d(L.d, [&](auto dc) {
@@ -399,6 +400,18 @@ hipError_t launch_pt_lane(int p, const PtLaunch& L, double* scratch, const doubl
         e = hipGetLastError();
     }
     return e;
+}
+
+// ... with the batched log-density launch of ONE series as K1: the single-series sampler
+hipError_t launch_pt_lane(int p, const PtLaunch& L, double* scratch, const double4* series, const Prior& pr,
+                          const double* temps, double* theta, double* logpost, double* chol, unsigned* naccept,
+                          unsigned* nswap, double* samples, double* sample_lp, int series_flags, bool load_factor, hipStream_t st)
+{
+    const PtLaneK1 k1 = [&](const double* thn, long nc, double* ll, hipStream_t s) {
+        return p == 1 ? launch_logdens_car1(thn, (int)nc, series, L.n, pr, ll, s)
+                      : launch_logdens_carma(p, thn, (int)nc, L.d, L.q, series, L.n, pr, 0, ll, s, series_flags);
+    };
+    return launch_pt_lane_k1(p, L, scratch, k1, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, load_factor, st);
 }
 
 // the chain-minor factors -> the chain-major array chol [R][T][d][d] (enqueued on st)

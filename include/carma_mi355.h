@@ -167,6 +167,48 @@ int carma_mle_batched_ms(carma_mctx* h, const double* x0 /* [B][d] */, const int
                          double gtol, double fd_step, int ignore_prior, double* x, double* fun, int* nit, int* nfev,
                          int* status);
 
+/*
+ * The parallel-tempering sampler over MANY SERIES (the carma_pt_* set on a carma_mctx).  A RUN is one sampler -- nreplicas
+ * independent ladders of ntemps chains -- on one series of the context; a call takes M runs, series = [M] (an index may repeat,
+ * any order).  All runs advance in the same launches: one chain per lane, the bookkeeping kernels of the large-ensemble sampler
+ * (carma_pt_lane.hip) and a log-density kernel in which every chain is evaluated on its own series
+ * (k_logdens_carma_chains_ms / k_logdens_car1_chains_ms).  Run j owns ladders j R .. j R + R - 1 of ONE ensemble of M R ladders,
+ * and a chain's random streams (Philox and starting values) are keyed by its position ladder * T + temperature in that ensemble:
+ * run j walks, bit for bit, the trajectory of the block replica0 = j R (carma_pt_shard) of a single-series lane-sampler ensemble
+ * on its series, whatever its neighbours are.
+ *
+ * carma_mpt_create: temperatures = [ntemps] or NULL (100^(i / (ntemps - 1))), shared by all runs; the initial proposal factor of
+ *   a run comes from its own series as in carma_pt_create.  CARMA_EINVAL, before any device work and with a message, for M < 1,
+ *   ntemps outside 1 ... 64, a series index out of range, or more chains (M * nreplicas * ntemps) than a launch can index.
+ * carma_mpt_start: starting values drawn per chain from its series' starting-value distribution, non-finite candidates retried in
+ *   rounds (the pending candidates of all runs in one launch); init = [M][d] or NULL: row j is given to every chain of run j when
+ *   its log-density on that run's series is finite, else run j draws.
+ * carma_mpt_set_chains / _get_chains: theta = [M][R][T][d], logpost = [M][R][T] (NULL on set: computed).
+ * carma_mpt_get_factor / _set_factor: [M][R][T][d*d] as carma_pt_get_factor.
+ * carma_mpt_iterate / _sample / _stats / _iterations_done: as the carma_pt_ calls; samples = [M][R][nsamples][d], logposts =
+ *   [M][R][nsamples], rates = [M][R][T].  The sample buffer is one device allocation; CARMA_ENOMEM names the bytes asked for.
+ *   Every call but carma_mpt_create is CARMA_EINVAL before carma_mpt_create, iterate / sample also before the chains have
+ *   starting values.
+ * carma_mpt_logdensity: the log-densities of chain states theta = [M][R][T][d], each on its run's series, through the sampler's
+ *   log-density kernel (the bits of carma_mlogdensity_batch); out = [M][R][T].  carma_mpt_kernel_name: that kernel's name.
+ * carma_mpt_run: create, start, burn-in (adapting), sample -- as carma_pt_run.
+ */
+int carma_mpt_create(carma_mctx* h, const int* series /* [M] */, int M, int ntemps, int nreplicas,
+                     const double* temperatures /* [ntemps] or NULL */, int adapt_iters, uint64_t seed);
+int carma_mpt_start(carma_mctx* h, const double* init /* [M][d] or NULL */);
+int carma_mpt_set_chains(carma_mctx* h, const double* theta /* [M][R][T][d] */, const double* logpost /* [M][R][T] or NULL */);
+int carma_mpt_get_chains(carma_mctx* h, double* theta, double* logpost);
+int carma_mpt_get_factor(carma_mctx* h, double* chol);
+int carma_mpt_set_factor(carma_mctx* h, const double* chol);
+int carma_mpt_iterate(carma_mctx* h, long niter, int do_exchange);
+int carma_mpt_sample(carma_mctx* h, int nsamples, int thin, double* samples /* [M][R][nsamples][d] */, double* logposts);
+int carma_mpt_stats(carma_mctx* h, double* accept_rate, double* swap_rate, int reset);
+long carma_mpt_iterations_done(const carma_mctx* h);
+int carma_mpt_logdensity(carma_mctx* h, const double* theta /* [M][R][T][d] */, double* out /* [M][R][T] */);
+int carma_mpt_kernel_name(const carma_mctx* h, char* buf, int len);
+int carma_mpt_run(carma_mctx* h, const int* series /* [M] */, int M, int ntemps, int nreplicas, int sample_size, int burnin,
+                  int thin, const double* init /* [M][d] or NULL */, uint64_t seed, double* samples, double* logposts);
+
 /* getLogPrior (carpack.hpp:118-126, wrapper :50,58,67); host arithmetic, one vector. */
 double carma_logprior(const carma_ctx* h, const double* theta);
 
