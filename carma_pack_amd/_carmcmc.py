@@ -146,6 +146,8 @@ class CARMA(CARp):
 # samples, carma_pack.py:513-546, 596-623); carma_pack.py calls these through this module like every other compute call
 sigma_noise_batch = _lib.sigma_noise_batch
 psd_band = _lib.psd_band
+simulate_cond_carma = _lib.simulate_cond_carma
+simulate_cond_car1 = _lib.simulate_cond_car1
 
 
 def _pop_max_stdev(y):
@@ -271,6 +273,15 @@ class _KalmanBase(object):
         m, _ = self._predict(self._t, self._y - y_tilde, self._e, times)
         return vecD((f_new + m).tolist())
 
+    def SimulateBatch(self, times, npaths, seed=None):
+        """Extension: `npaths` conditional draws of this object's model at `times` in two launches for all of them
+        (carma_simulate_cond_*: Simulate's construction with the measurement noise from the device generator, so that
+        a seed reproduces the paths) -> [npaths][len(times)] in the order of `times`.  seed None: drawn from numpy's
+        global stream, as Simulate draws its own."""
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 62))
+        return self._simulate_cond(_arr(times), int(npaths), int(seed))
+
 
 class KalmanFilter1(_KalmanBase):
     """KalmanFilter1(time, y, yerr[, sigsqr, omega]) (wrapper :83-90; kfilter.hpp:222-245)."""
@@ -298,6 +309,12 @@ class KalmanFilter1(_KalmanBase):
 
     def _simulate(self, times, seed):
         return _lib.simulate_car1(times, self._sigsqr, self._omega, 1, seed)[0]
+
+    def _simulate_cond(self, times, npaths, seed):
+        if self._sigsqr is None or self._omega is None:
+            raise RuntimeError("KalmanFilter1: sigsqr and omega are not set")
+        return _lib.simulate_cond_car1(self._t, self._y, self._e, np.full(npaths, float(self._sigsqr)),
+                                       np.full(npaths, float(self._omega)), None, times, seed=seed)
 
 
 class KalmanFilterp(_KalmanBase):
@@ -329,3 +346,10 @@ class KalmanFilterp(_KalmanBase):
 
     def _simulate(self, times, seed):
         return _lib.simulate_carma(times, self._sigsqr, self._omega, self._ma, 1, seed)[0]
+
+    def _simulate_cond(self, times, npaths, seed):
+        if self._sigsqr is None or self._omega is None or self._ma is None:
+            raise RuntimeError("KalmanFilterp: sigsqr, omega and ma_coefs are not set")
+        return _lib.simulate_cond_carma(self._t, self._y, self._e, np.full(npaths, float(self._sigsqr)),
+                                        np.tile(self._omega, (npaths, 1)), np.tile(self._ma, (npaths, 1)), None, times,
+                                        seed=seed)

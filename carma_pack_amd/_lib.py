@@ -174,6 +174,10 @@ def _load():
     L.carma_kf_predict.argtypes = [C.c_void_p, _dp, C.c_int, _dp, _dp]
     L.carma_simulate_carma.argtypes = [_dp, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_int, C.c_int, C.c_uint64, _dp, C.c_int]
     L.carma_simulate_car1.argtypes = [_dp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_uint64, _dp, C.c_int]
+    L.carma_simulate_cond_carma.argtypes = [_dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, C.c_int,
+                                            C.c_uint64, C.c_uint, _dp, _dp, _dp, _ip, _ip, C.c_int]
+    L.carma_simulate_cond_car1.argtypes = [_dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_uint64, C.c_uint,
+                                           _dp, _dp, _dp, _ip, _ip, C.c_int]
     L.carma_sigma_noise_batch.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int]
     L.carma_psd_band.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int]
     L.carma_pt_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_uint64,
@@ -217,7 +221,7 @@ EXPORTS = [
     "carma_ctx_n", "carma_ctx_dim", "carma_ctx_get_data", "carma_ctx_get_prior", "carma_ctx_set_prior",
     "carma_logdensity_batch", "carma_logdensity_batch_dev", "carma_logdensity_kernel_name", "carma_logprior", "carma_mle_batched", "carma_kfilter_carma", "carma_kfilter_batch_carma",
     "carma_kfilter_car1", "carma_predict_carma", "carma_predict_car1", "carma_normalize_roots", "carma_kf_create_carma", "carma_kf_create_car1",
-    "carma_kf_destroy", "carma_kf_n", "carma_kf_filter", "carma_kf_predict", "carma_simulate_carma", "carma_simulate_car1", "carma_sigma_noise_batch", "carma_psd_band", "carma_pt_run", "carma_pt_create", "carma_pt_shard", "carma_pt_bind_state",
+    "carma_kf_destroy", "carma_kf_n", "carma_kf_filter", "carma_kf_predict", "carma_simulate_carma", "carma_simulate_car1", "carma_simulate_cond_carma", "carma_simulate_cond_car1", "carma_sigma_noise_batch", "carma_psd_band", "carma_pt_run", "carma_pt_create", "carma_pt_shard", "carma_pt_bind_state",
     "carma_pt_start", "carma_pt_set_chains", "carma_pt_get_chains", "carma_pt_iterate", "carma_pt_sample",
     "carma_pt_stats", "carma_pt_iterations_done", "carma_comm_unique_id", "carma_comm_create", "carma_comm_destroy",
     "carma_comm_rank", "carma_comm_size", "carma_pt_iterate_sharded", "carma_pt_sample_sharded", "carma_pt_boundary_stats",
@@ -231,14 +235,15 @@ EXPORTS = [
 
 
 def tune_set(name, value):
-    """Move a launch-shape switch ("WIN_ROWS", "WIN2_EVALS", "PT_ROW_WIN": carma_tune_set; measurements and parity tests).
+    """Move a launch-shape switch ("WIN_ROWS", "WIN2_EVALS", "PT_ROW_WIN", "CSIM_CHUNK_PATHS": carma_tune_set; measurements and
+    parity tests).
     value None: back to the library's default."""
     check(lib.carma_tune_set(str(name).encode(), -2 ** 63 if value is None else int(value)), "carma_tune_set")
 
 
 def tune_reset():
     """Every switch back to what the environment said when the library read it (CARMA_TUNE_<name>), or to the default."""
-    for name in ("WIN_ROWS", "WIN2_EVALS", "PT_ROW_WIN"):
+    for name in ("WIN_ROWS", "WIN2_EVALS", "PT_ROW_WIN", "CSIM_CHUNK_PATHS"):
         e = os.environ.get("CARMA_TUNE_" + name)
         tune_set(name, None if e is None else int(e))
 
@@ -957,6 +962,86 @@ def simulate_car1(time, sigsqr, omega, npaths=1, seed=0, device=None):
                                   C.c_uint64(int(seed) & (2 ** 64 - 1)), ptr(out), default_device() if device is None else device),
           "carma_simulate_car1")
     return out
+
+
+def merged_times(time, tsim):
+    """The grid the conditional simulation draws its unconditional paths on: the series' distinct times (sorted) followed by
+    the sorted `tsim`, in a stable ascending sort -- a requested time equal to a datum comes behind it.
+    -> (grid [n + M], position of every datum [n], position of every tsim entry in the caller's order [M])."""
+    ts = np.sort(as_f64(np.ravel(time)), kind="stable")
+    ts = ts[np.r_[True, np.diff(ts) != 0]]
+    tsim = as_f64(np.atleast_1d(tsim))
+    perm = np.argsort(tsim, kind="stable")
+    cat = np.concatenate([ts, tsim[perm]])
+    order = np.argsort(cat, kind="stable")
+    inv = np.empty(order.size, dtype=int)
+    inv[order] = np.arange(order.size)
+    spos = np.empty(tsim.size, dtype=int)
+    spos[perm] = inv[ts.size:]
+    return cat[order], inv[:ts.size], spos
+
+
+def _simulate_cond(call, what, time, y, yerr, K, model_args, mu, tsim, seed, path0, return_parts, return_singular, device):
+    time, y, yerr = as_f64(time), as_f64(y), as_f64(yerr)
+    tp = as_f64(np.atleast_1d(tsim))
+    mu_ = None if mu is None else as_f64(np.atleast_1d(mu))
+    if mu_ is not None and mu_.size != K:
+        raise ValueError("%s: mu must have one entry per path" % what)
+    n, M = time.size, tp.size
+    out = np.empty((K, max(M, 1)))
+    unc = np.empty((K, n + M)) if return_parts else None
+    noi = np.empty((K, n)) if return_parts else None
+    sing = np.zeros(K, dtype=np.int32)
+    nout = C.c_int(0)
+    rc = call(ptr(time), ptr(y), ptr(yerr), n, *model_args, ptr(mu_) if mu_ is not None else None, ptr(tp), M,
+              C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint(int(path0) & 0xffffffff), ptr(out),
+              ptr(unc) if return_parts else None, ptr(noi) if return_parts else None, sing.ctypes.data_as(_ip),
+              C.byref(nout), default_device() if device is None else device)
+    check(rc, what)
+    sing = sing.astype(bool)
+    if sing.any() and not return_singular:
+        raise CarmaError("%s: repeated AR root (singular eigenvector matrix) in path %d" % (what, int(np.argmax(sing))))
+    res = (out,)
+    if return_parts:
+        m = nout.value
+        # (the library writes rows of n_out + M and of n_out values back to back)
+        res += (unc.reshape(-1)[:K * (m + M)].reshape(K, m + M), noi.reshape(-1)[:K * m].reshape(K, m),
+                merged_times(time, tp)[0])
+    if return_singular:
+        res += (sing,)
+    return res[0] if len(res) == 1 else res
+
+
+def simulate_cond_carma(time, y, yerr, sigsqr, omega, ma, mu, tsim, seed=0, path0=0, return_parts=False,
+                        return_singular=False, device=None):
+    """K paths of the process at `tsim` CONDITIONAL on the series, path k under its own model (sigsqr[k], omega[k] complex [p],
+    ma[k], mu[k]; mu None: 0) and with the generator key (seed, path0 + k), in two launches (carma_simulate_cond_carma)
+    -> out [K][M] in the order of tsim.  return_parts: also (uncond [K][n + M], noise [K][n], merged_times [n + M]) -- the
+    unconditional paths on the merged grid and the unit normals of the measurement noise, from which simulate_carma and
+    predict_carma rebuild every path.  return_singular: also the flags [K] of paths with a repeated AR root (otherwise such
+    a path raises)."""
+    omega = np.atleast_2d(np.asarray(omega, dtype=complex))
+    K, p = omega.shape
+    om = as_f64(np.stack([omega.real, omega.imag], axis=-1))
+    ma = as_f64(np.atleast_2d(ma))
+    sig = as_f64(np.atleast_1d(sigsqr))
+    if ma.shape[0] != K or sig.size != K:
+        raise ValueError("simulate_cond_carma: sigsqr, omega and ma must describe the same number of paths")
+    return _simulate_cond(lib.carma_simulate_cond_carma, "carma_simulate_cond_carma", time, y, yerr, K,
+                          (p, K, ptr(sig), ptr(om), ptr(ma), ma.shape[1]), mu, tsim, seed, path0, return_parts,
+                          return_singular, device)
+
+
+def simulate_cond_car1(time, y, yerr, sigsqr, omega, mu, tsim, seed=0, path0=0, return_parts=False, return_singular=False,
+                       device=None):
+    """simulate_cond_carma for CAR(1) models: sigsqr [K], omega [K] = 1 / tau (carma_simulate_cond_car1)."""
+    sig = as_f64(np.atleast_1d(sigsqr))
+    om = as_f64(np.atleast_1d(omega))
+    K = sig.size
+    if om.size != K:
+        raise ValueError("simulate_cond_car1: sigsqr and omega must describe the same number of paths")
+    return _simulate_cond(lib.carma_simulate_cond_car1, "carma_simulate_cond_car1", time, y, yerr, K,
+                          (K, ptr(sig), ptr(om)), mu, tsim, seed, path0, return_parts, return_singular, device)
 
 
 def sigma_noise_batch(ar_roots, ma_coefs, var, device=None):

@@ -410,9 +410,9 @@ class CarmaSample(MCMCSample):
         ci = self._psd_credint(percentile, nsamples, frequencies)
         return ci[:, 0], ci[:, 2], ci[:, 1], frequencies
 
-    def makeKalmanFilter(self, bestfit):
-        """KalmanFilterp for a point estimate ('map', 'median', 'mean' or a sample index),
-        reference :650-685."""
+    def _point_params(self, bestfit):
+        """(sigsqr, mu, ar_roots, ma_coefs) of a point estimate: 'map', 'median', 'mean', a sample index, or -- any other
+        string, 'random' by convention -- one sample drawn from numpy's global stream (reference :650-676)."""
         if bestfit == "map":
             i = int(np.argmax(self._samples["logpost"]))
             pick = lambda a: a[i]  # noqa: E731
@@ -420,16 +420,57 @@ class CarmaSample(MCMCSample):
             pick = lambda a: np.median(a, axis=0)  # noqa: E731
         elif bestfit == "mean":
             pick = lambda a: np.mean(a, axis=0)  # noqa: E731
+        elif isinstance(bestfit, str):
+            i = int(np.random.randint(0, self._samples["sigma"].shape[0]))    # a random draw from the posterior (:670-676)
+            pick = lambda a: a[i]  # noqa: E731
         else:
             pick = lambda a: a[int(bestfit)]  # noqa: E731
         sigsqr = float(np.ravel(pick(self._samples["sigma"]))[0]) ** 2
         mu = float(np.ravel(pick(self._samples["mu"]))[0])
         roots = np.atleast_1d(pick(self._samples["ar_roots"]))
         ma = np.atleast_1d(pick(self._samples["ma_coefs"]))
+        return sigsqr, mu, roots, ma
+
+    def makeKalmanFilter(self, bestfit):
+        """KalmanFilterp for a point estimate ('map', 'median', 'mean' or a sample index) or, for any other string
+        ('random'), for one random draw from the posterior; reference :650-685."""
+        sigsqr, mu, roots, ma = self._point_params(bestfit)
         omega = carmcmcLib.vecC(roots.tolist())
         kf = carmcmcLib.KalmanFilterp(carmcmcLib.vecD(self.time), carmcmcLib.vecD(self.y - mu),
                                       carmcmcLib.vecD(self.ysig), sigsqr, omega, carmcmcLib.vecD(ma.tolist()))
         return kf, mu
+
+    def _path_models(self, index):
+        """Model arrays of the samples `index` as the conditional simulation takes them: (sigsqr, mu, (ar_roots, ma_coefs))."""
+        sig = np.ravel(self._samples["sigma"])[index]
+        return sig ** 2, np.ravel(self._samples["mu"])[index], (self._samples["ar_roots"][index], self._samples["ma_coefs"][index])
+
+    def _point_models(self, bestfit, npaths):
+        sigsqr, mu, roots, ma = self._point_params(bestfit)
+        return np.full(npaths, sigsqr), np.full(npaths, mu), (np.tile(roots, (npaths, 1)), np.tile(ma, (npaths, 1)))
+
+    def _simulate_cond(self, sigsqr, mu, rest, time, seed):
+        return carmcmcLib.simulate_cond_carma(self.time, self.y, self.ysig, sigsqr, rest[0], rest[1], mu, time, seed=seed)
+
+    def simulate_paths(self, time, npaths=1, bestfit="random", seed=None, return_index=False):
+        """`npaths` draws of the process at `time` conditional on the data -> [npaths][len(time)]: the ensemble the reference
+        builds with `for i in range(nsim): ysim[i] = sample.simulate(time, bestfit='random')`, in two launches for all paths.
+        bestfit 'random': every path under its own posterior sample; 'map', 'median', 'mean' or a sample index: that one
+        model for all paths.  seed: the sample indices come from np.random.RandomState(seed) and the device generator is
+        keyed by (seed, path), so a seed reproduces the ensemble; None: indices and a seed from numpy's global stream.
+        return_index: also the sample index of every path (None unless bestfit is 'random')."""
+        time = np.atleast_1d(np.asarray(time, dtype=float))
+        npaths = int(npaths)
+        rs = np.random if seed is None else np.random.RandomState(seed)
+        index = None
+        if bestfit == "random":
+            index = rs.randint(0, self._samples["sigma"].shape[0], size=npaths)
+            sigsqr, mu, rest = self._path_models(index)
+        else:
+            sigsqr, mu, rest = self._point_models(bestfit, npaths)
+        dev_seed = int(np.random.randint(0, 2 ** 62)) if seed is None else int(seed)
+        paths = self._simulate_cond(sigsqr, mu, rest, time, dev_seed)
+        return (paths, index) if return_index else paths
 
     def predict(self, time, bestfit="map"):
         """Expected value and variance of the series at `time` given the data and a point estimate of
@@ -488,8 +529,8 @@ class Car1Sample(CarmaSample):
         self._samples["ma_coefs"] = np.ones((trace.shape[0], 1))
         self._samples["sigma"] = np.sqrt(2.0 * omega * trace[:, 0] ** 2)
 
-    def makeKalmanFilter(self, bestfit):
-        """KalmanFilter1 for a point estimate (reference :925-948): 'map', 'median', anything else = posterior mean
+    def _point_params(self, bestfit):
+        """(sigsqr, mu, log omega) of a point estimate (reference :925-948): 'map', 'median', anything else = posterior mean
         (of sigma^2, mu and log omega -- as the reference does); an integer picks one sample (as CarmaSample)."""
         sig, mu_s, lw = (np.ravel(self._samples[k]) for k in ("sigma", "mu", "log_omega"))
         if bestfit == "map":
@@ -502,9 +543,26 @@ class Car1Sample(CarmaSample):
             sigsqr, mu, log_omega = sig[i] ** 2, mu_s[i], lw[i]
         else:
             sigsqr, mu, log_omega = np.mean(sig ** 2), np.mean(mu_s), np.mean(lw)
+        return float(sigsqr), float(mu), float(log_omega)
+
+    def makeKalmanFilter(self, bestfit):
+        """KalmanFilter1 for a point estimate (_point_params; reference :925-948)."""
+        sigsqr, mu, log_omega = self._point_params(bestfit)
         kf = carmcmcLib.KalmanFilter1(carmcmcLib.vecD(self.time), carmcmcLib.vecD(self.y - mu),
-                                      carmcmcLib.vecD(self.ysig), float(sigsqr), float(np.exp(log_omega)))
-        return kf, float(mu)
+                                      carmcmcLib.vecD(self.ysig), sigsqr, float(np.exp(log_omega)))
+        return kf, mu
+
+    # simulate_paths is CarmaSample's, through this class's own parameter pick
+    def _path_models(self, index):
+        sig = np.ravel(self._samples["sigma"])[index]
+        return sig ** 2, np.ravel(self._samples["mu"])[index], np.exp(np.ravel(self._samples["log_omega"])[index])
+
+    def _point_models(self, bestfit, npaths):
+        sigsqr, mu, log_omega = self._point_params(bestfit)
+        return np.full(npaths, sigsqr), np.full(npaths, mu), np.full(npaths, float(np.exp(log_omega)))
+
+    def _simulate_cond(self, sigsqr, mu, omega, time, seed):
+        return carmcmcLib.simulate_cond_car1(self.time, self.y, self.ysig, sigsqr, omega, mu, time, seed=seed)
 
     # (the spectrum sigma^2 / (omega^2 + (2 pi f)^2) of the reference (:1004-1013) is the general formula with
     # alpha(s) = s + omega, delta = 1 -- the arrays generate_from_trace stores -- so CarmaSample's device path serves it)

@@ -703,7 +703,8 @@ static long p3l_max_rows()
 // Launch shape for B evaluations of order P (one table for the launcher and for carma_logdensity_kernel_name)
 enum class LdShape { P3L, PC1, PC2, PLAIN1, PLAIN4, LANE, LPC, WIN, WIN2 };
 // The launch-shape switches (carma_launch.h): environment read once, atomics afterwards.
-static const char* const TUNE_NAMES[TUNE_COUNT] = {"CARMA_TUNE_WIN_ROWS", "CARMA_TUNE_WIN2_EVALS", "CARMA_TUNE_PT_ROW_WIN"};
+static const char* const TUNE_NAMES[TUNE_COUNT] = {"CARMA_TUNE_WIN_ROWS", "CARMA_TUNE_WIN2_EVALS", "CARMA_TUNE_PT_ROW_WIN",
+                                                    "CARMA_TUNE_CSIM_CHUNK_PATHS"};
 static std::atomic<long> g_tune[TUNE_COUNT];
 static std::atomic<int> g_tune_init{0};
 static void tune_init()

@@ -105,7 +105,8 @@ int carma_logdensity_kernel_name(const carma_ctx* h, int B, char* buf, int len);
 
 /* Launch-shape switches for measurements and the parity tests (no counterpart in the reference): "WIN_ROWS", "WIN2_EVALS",
  * "PT_ROW_WIN" -- the CARMA_TUNE_* environment variables of the same names give their initial values, read once when the first
- * launch asks; afterwards only this call moves them (process-wide, thread-safe).  CARMA_EINVAL for an unknown name. */
+ * launch asks; afterwards only this call moves them (process-wide, thread-safe).  CARMA_EINVAL for an unknown name.
+ * "CSIM_CHUNK_PATHS": paths per chunk of carma_simulate_cond_* (0: as many as its scratch cap holds; results do not depend on it). */
 int carma_tune_set(const char* name, long value);
 
 /*
@@ -288,6 +289,39 @@ int carma_simulate_carma(const double* time, int n, int p, double sigsqr, const 
                          const double* ma, int nma, int npaths, uint64_t seed, double* out, int device);
 int carma_simulate_car1(const double* time, int n, double sigsqr, double omega, int npaths, uint64_t seed,
                         double* out, int device);
+
+/*
+ * CONDITIONAL simulation of npaths paths on ONE series, path k with a model of its own (sigsqr[k], omega_re_im[k], ma[k],
+ * mu[k]): what `for i in range(nsim): ysim[i] = sample.simulate(tsim, bestfit='random')` (src/carmcmc/carma_pack.py:807-837
+ * over kfilter.hpp:135-184, one re-filter per time and path) draws, in two launches for all paths.
+ * Construction (Matheron's rule):  out_k = f~_k(tsim) + E[f(tsim) | y - mu_k - y~_k] + mu_k,  where
+ *   - the series is sorted and deduplicated as carma_kf_create_* does (n_out data remain; fewer than 2: CARMA_EINVAL);
+ *   - the merged grid is the stable ascending sort of (the n_out data times, then tsim sorted): n_out + M times, a tsim equal to a
+ *     datum behind it; f~_k is carma_simulate_* 's path on that grid (repeated times repeat the value);
+ *   - y~_kj = f~_k(t_j) + yerr_j z_kj, and the residual datum is (y_j - mu_k) - y~_kj with yerr_j as given;
+ *   - E[.|.] is carma_predict_* of the residual series under model k; the three sums above are rounded one by one, the last
+ *     (+ mu_k) is skipped for mu_k = 0.
+ * Keys of the counter-based generator: path k uses (seed, path0 + k); its unconditional path takes the normals
+ * (step i of the merged grid, idx 0) -- the draws of path path0 + k of carma_simulate_*(merged grid, model k, seed) -- and
+ * z_kj is (datum j, idx 1).  A path therefore depends neither on the other paths of the call nor on how the call is cut into
+ * chunks (the scratch, 32 n_out + 8 (n_out + M) bytes a path, is capped; "CSIM_CHUNK_PATHS" of carma_tune_set forces a chunk size).
+ * omega_re_im = [npaths][p][2], roots in any order but closed under conjugation; ma = [npaths][nma], 1 <= nma <= p, zero padded
+ * inside; mu = [npaths] or NULL (0).  out = [npaths][M] in the CALLER's order of tsim.  Optional outputs (NULL to skip), from
+ * which every path can be rebuilt with the single-model entry points: uncond = [npaths][n_out + M] (f~ on the merged grid),
+ * noise = [npaths][n_out] (z).  singular = [npaths] or NULL: 1 where a path has a repeated AR root (its rows are then not
+ * meaningful; other paths are not affected); returns 1 if any path is singular and singular is NULL.  CARMA_EINVAL, before any
+ * device work and with the offending path in carma_last_error() where one is at fault: npaths < 1, M < 1, nma outside 1..p,
+ * roots not closed under conjugation, sigsqr (omega) not positive, a tsim that is not finite, fewer than 2 distinct data times.
+ * CAR(1): omega[k] = 1 / tau_k.
+ */
+int carma_simulate_cond_carma(const double* time, const double* y, const double* yerr, int n, int p, int npaths,
+                              const double* sigsqr, const double* omega_re_im, const double* ma, int nma, const double* mu,
+                              const double* tsim, int M, uint64_t seed, unsigned path0, double* out, double* uncond,
+                              double* noise, int* singular, int* n_out, int device);
+int carma_simulate_cond_car1(const double* time, const double* y, const double* yerr, int n, int npaths,
+                             const double* sigsqr, const double* omega, const double* mu, const double* tsim, int M,
+                             uint64_t seed, unsigned path0, double* out, double* uncond, double* noise, int* singular,
+                             int* n_out, int device);
 
 /*
  * CarmaSample post-processing (src/carmcmc/carma_pack.py), one launch per quantity instead of a
