@@ -160,7 +160,7 @@ class BatchResult(object):
 
 # status codes of carma_mle_batched (include/carma_mi355.h) in words
 STATUS_TEXT = ("converged: projected gradient <= gtol", "converged: relative reduction of f <= ftol",
-               "maximum number of iterations reached", "line search failed")
+               "maximum number of iterations reached", "line search failed", "no finite value at the start")
 
 
 class MCMCSample(object):

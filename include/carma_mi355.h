@@ -93,7 +93,9 @@ int carma_logdensity_batch_dev(carma_ctx* h, const double* d_theta, int B, int i
  * x0 = [B][d] starts; lo / hi = [d] box (NULL or non-finite entries = unbounded); maxiter per start; fd_step = relative
  * finite-difference step; ignore_prior as carma_logdensity_batch (SetMLE(true), carma_pack.py:242).
  * Outputs: x = [B][d], fun = [B] (-LogDensity at x), and optionally nit / nfev / status = [B]
- * (0 converged on the gradient, 1 converged on f, 2 maxiter reached, 3 line search failed).
+ * (0 converged on the gradient, 1 converged on f, 2 maxiter reached, 3 line search failed, 4 no finite value at the
+ * start: the objective is non-finite at the projected x0; such a start ends at once with nit 0, fun 1e300 and x the
+ * projected x0).  0 and 1 are successes.
  */
 int carma_mle_batched(carma_ctx* h, const double* x0, int B, const double* lo, const double* hi, int maxiter, int mem,
                       double ftol, double gtol, double fd_step, int ignore_prior, double* x, double* fun, int* nit,
@@ -124,7 +126,7 @@ int carma_tune_set(const char* name, long value);
  *   range is CARMA_EINVAL before any device work.
  * carma_mle_batched_ms: carma_mle_batched with start i on series series[i] and its own box lo / hi = [B][d] (NULL or
  *   non-finite entries = unbounded); every start's evaluations go through carma_mlogdensity_batch, all starts advance in
- *   lock-step in the same launches.
+ *   lock-step in the same launches.  status as carma_mle_batched (0 ... 4; 4 = no finite value at the start).
  * carma_mkfilter: KalmanFilterp::Filter / KalmanFilter1::Filter of M ITEMS in one launch; item i is the model (sigsqr[i],
  *   omega_re_im[i], ma[i]) on series series[i] of the context, whose order p the models share.  Several items may name one
  *   series, a series may have none.  omega_re_im = [M][p][2], roots in any order but closed under conjugation; ma = [M][nma],

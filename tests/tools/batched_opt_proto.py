@@ -21,6 +21,16 @@ def _project(x, lo, hi):
     return np.minimum(np.maximum(x, lo), hi)
 
 
+def _dot(a, b):
+    """sum_j a[..., j] b[..., j], accumulated from j = 0 upwards as the library's loop does (a library reduction may pair the
+    terms otherwise; over some tens of quasi-Newton iterations a last-bit difference in a dot product grows to 1e-8 in x)."""
+    a, b = np.broadcast_arrays(a, b)
+    acc = np.zeros(a.shape[:-1])
+    for j in range(a.shape[-1]):
+        acc = acc + a[..., j] * b[..., j]
+    return acc
+
+
 def minimize_batched(fun_batch, x0, bounds, maxiter=2000, m=8, ftol=2.220446049250313e-09, gtol=1e-5, fd_step=1e-6):
     """Minimise f independently from every row of x0.
 
@@ -55,16 +65,17 @@ def minimize_batched(fun_batch, x0, bounds, maxiter=2000, m=8, ftol=2.2204460492
         return f[:, 0], g
 
     f, g = f_and_g(x, np.arange(B))
+    infeasible = f >= BIG                                   # no finite value at the start: ends at once (status 4)
     S = np.zeros((B, m, d))
     Y = np.zeros((B, m, d))
     rho = np.zeros((B, m))
     nhist = np.zeros(B, dtype=int)
-    active = np.ones(B, dtype=bool)
+    active = ~infeasible
     nit = np.zeros(B, dtype=int)
     nsmall = np.zeros(B, dtype=int)
     restarted = np.zeros(B, dtype=bool)
     patience = 3
-    msg = ["maximum number of iterations reached"] * B
+    msg = [STATUS_TEXT[4] if infeasible[i] else STATUS_TEXT[2] for i in range(B)]
     for _ in range(maxiter):
         idx = np.flatnonzero(active)
         if idx.size == 0:
@@ -87,23 +98,23 @@ def minimize_batched(fun_batch, x0, bounds, maxiter=2000, m=8, ftol=2.2204460492
         Sa, Ya, ra = S[idx], Y[idx], rho[idx]               # one gather per iteration
         alpha = np.zeros((idx.size, m))
         for k in range(int(nh.max()) - 1, -1, -1):
-            a = np.where(k < nh, ra[:, k] * np.einsum("ij,ij->i", Sa[:, k], q), 0.0)
+            a = np.where(k < nh, ra[:, k] * _dot(Sa[:, k], q), 0.0)
             alpha[:, k] = a
             q -= a[:, None] * Ya[:, k]
         last = np.maximum(nh - 1, 0)
         ar = np.arange(idx.size)
-        ys = np.einsum("ij,ij->i", Sa[ar, last], Ya[ar, last])
-        yy = np.einsum("ij,ij->i", Ya[ar, last], Ya[ar, last])
-        gamma = np.where((nh > 0) & (yy > 0), ys / np.maximum(yy, 1e-300), 1.0 / np.maximum(np.linalg.norm(pg, axis=1), 1e-12))
+        ys = _dot(Sa[ar, last], Ya[ar, last])
+        yy = _dot(Ya[ar, last], Ya[ar, last])
+        gamma = np.where((nh > 0) & (yy > 0), ys / np.maximum(yy, 1e-300), 1.0 / np.maximum(np.sqrt(_dot(pg, pg)), 1e-12))
         r = gamma[:, None] * q
         for k in range(int(nh.max())):
-            b = ra[:, k] * np.einsum("ij,ij->i", Ya[:, k], r)
+            b = ra[:, k] * _dot(Ya[:, k], r)
             r += np.where(k < nh, alpha[:, k] - b, 0.0)[:, None] * Sa[:, k]
         direction = -np.where(frozen, 0.0, r)
-        slope = np.einsum("ij,ij->i", direction, pg)
+        slope = _dot(direction, pg)
         bad = ~(slope < 0)                                  # not a descent direction: steepest descent
         direction[bad] = -pg[bad] * gamma[bad, None]
-        slope[bad] = -np.einsum("ij,ij->i", pg[bad], pg[bad]) * gamma[bad]
+        slope[bad] = -_dot(pg[bad], pg[bad]) * gamma[bad]
         # Armijo backtracking on the projected path.  A launch costs the same for 100 points as for 800, so every
         # round evaluates LS_K consecutive step lengths t, t/2, ... of every start that still needs one and takes
         # the FIRST that satisfies the condition -- the same step sequential backtracking would take, in ~1 launch
@@ -120,7 +131,7 @@ def minimize_batched(fun_batch, x0, bounds, maxiter=2000, m=8, ftol=2.2204460492
             cand = _project(xa[j, None, :] + tk[:, :, None] * direction[j, None, :], lo, hi)
             fc = np.asarray(fun_batch(cand.reshape(-1, d)), dtype=float).reshape(j.size, LS_K)
             fc = np.where(np.isfinite(fc), fc, BIG)
-            ok = fc <= fa[j, None] + 1e-4 * np.einsum("ikj,ij->ik", cand - xa[j, None, :], pg[j])
+            ok = fc <= fa[j, None] + 1e-4 * _dot(cand - xa[j, None, :], pg[j, None, :])
             first = np.argmax(ok, axis=1)
             hit = ok.any(axis=1)
             nfev[idx[j]] += np.where(hit, first + 1, LS_K)                              # as sequential backtracking counts
@@ -138,8 +149,8 @@ def minimize_batched(fun_batch, x0, bounds, maxiter=2000, m=8, ftol=2.2204460492
         im = idx[mv]
         fnew, gnew = f_and_g(xn[mv], im)
         s_vec, y_vec = xn[mv] - xa[mv], gnew - ga[mv]
-        sy = np.einsum("ij,ij->i", s_vec, y_vec)
-        good = sy > 1e-10 * np.einsum("ij,ij->i", y_vec, y_vec)
+        sy = _dot(s_vec, y_vec)
+        good = sy > 1e-10 * _dot(y_vec, y_vec)
         ig = im[good]                                       # history update, vectorised over the starts
         full = ig[nhist[ig] == m]
         if full.size:                                       # drop the oldest pair
@@ -165,5 +176,5 @@ def minimize_batched(fun_batch, x0, bounds, maxiter=2000, m=8, ftol=2.2204460492
         for i in im[conv]:
             msg[i] = "converged: relative reduction of f <= ftol"
         active[im[conv]] = False
-    return [BatchResult(x[i].copy(), float(f[i]), int(nit[i]), int(nfev[i]), not msg[i].startswith(("maximum", "line")), msg[i])
+    return [BatchResult(x[i].copy(), float(f[i]), int(nit[i]), int(nfev[i]), msg[i].startswith("converged"), msg[i])
             for i in range(B)]
