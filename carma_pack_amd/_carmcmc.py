@@ -146,6 +146,7 @@ class CARMA(CARp):
 # samples, carma_pack.py:513-546, 596-623); carma_pack.py calls these through this module like every other compute call
 sigma_noise_batch = _lib.sigma_noise_batch
 psd_band = _lib.psd_band
+mpsd_band = _lib.mpsd_band
 simulate_cond_carma = _lib.simulate_cond_carma
 simulate_cond_car1 = _lib.simulate_cond_car1
 
@@ -191,10 +192,12 @@ class SetRunSampler(object):
     """One run of a multi-series sampler call (MultiContext.pt_run) seen as the sampler object CarmaSample / Car1Sample wrap:
     the coldest chain of the run's first replica, like the objects run_mcmc_car1 / run_mcmc_carma return.  loglik: the
     log-densities of that trace with the prior bounds ignored, when the caller has evaluated them for all runs in one launch
-    (CarmaModelSet.run_mcmc) -- getLogDensityBatch hands them out instead of launching again."""
+    (CarmaModelSet.run_mcmc) -- getLogDensityBatch hands them out instead of launching again; sigma: likewise the driving-noise
+    amplitudes of that trace with the inputs they were computed from (getSigmaNoise)."""
 
-    def __init__(self, mctx, series, samples, logposts, loglik=None, accept_rate=None, swap_rate=None):
+    def __init__(self, mctx, series, samples, logposts, loglik=None, accept_rate=None, swap_rate=None, sigma=None):
         self._mctx, self._series = mctx, int(series)
+        self._sigma = sigma                                                # None or (ar_roots, ma_coefs, var, sigma) of the trace
         self.p, self.q = mctx.p, mctx.q
         self._all_samples, self._all_logposts = samples, logposts          # [R][S][d], [R][S]
         self._samples, self._logposts = samples[0], logposts[0]
@@ -218,6 +221,16 @@ class SetRunSampler(object):
         # carpack.hpp:118-126 with measerr_dof = 50 (carpack.hpp:63): host arithmetic
         s = float(_arr(theta)[1])
         return -0.5 * 50.0 / s - (1.0 + 50.0 / 2.0) * np.log(s)
+
+    def getSigmaNoise(self, ar_roots, ma_coefs, var):
+        """sigma of the driving noise of the trace, when the caller has computed it for all runs in one launch and these are
+        the inputs it used; else None."""
+        if self._sigma is None:
+            return None
+        roots0, ma0, var0, sigma = self._sigma
+        if all(np.shape(a) == np.shape(b) and np.array_equal(a, b) for a, b in ((ar_roots, roots0), (ma_coefs, ma0), (var, var0))):
+            return sigma
+        return None
 
     def getLogDensity(self, theta):
         return float(self.getLogDensityBatch(_arr(theta).reshape(1, -1))[0])

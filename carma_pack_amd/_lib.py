@@ -180,6 +180,10 @@ def _load():
                                            _dp, _dp, _dp, _ip, _ip, C.c_int]
     L.carma_sigma_noise_batch.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int]
     L.carma_psd_band.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int]
+    L.carma_mpsd_band.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_long), C.c_int, _dp, C.c_int, _dp, C.c_int, _dp,
+                                  C.c_int]
+    L.carma_mpsd_fused_max.argtypes = []
+    L.carma_mpsd_freq_tile.argtypes = []
     L.carma_pt_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_uint64,
                                _dp, _dp]
     L.carma_pt_create.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, C.c_uint64]
@@ -231,6 +235,7 @@ EXPORTS = [
     "carma_mle_batched_ms", "carma_mkfilter", "carma_mpredict", "carma_mpt_create", "carma_mpt_start", "carma_mpt_set_chains",
     "carma_mpt_get_chains", "carma_mpt_get_factor", "carma_mpt_set_factor", "carma_mpt_iterate", "carma_mpt_sample",
     "carma_mpt_stats", "carma_mpt_iterations_done", "carma_mpt_logdensity", "carma_mpt_kernel_name", "carma_mpt_run",
+    "carma_mpsd_band", "carma_mpsd_fused_max", "carma_mpsd_freq_tile",
 ]
 
 
@@ -1078,6 +1083,48 @@ def psd_band(ar_coefs, ma_coefs, sigma, freq, percentiles, return_samples=False,
                              ptr(band), ptr(grid) if return_samples else None, default_device() if device is None else device),
           "carma_psd_band")
     return (band, grid) if return_samples else band
+
+
+def mpsd_fused_max():
+    """The largest sample count of a series that carma_mpsd_band serves with its fused kernel (carma_mpsd_fused_max)."""
+    return int(lib.carma_mpsd_fused_max())
+
+
+def mpsd_freq_tile():
+    """Frequencies per workgroup of the fused kernel (carma_mpsd_freq_tile)."""
+    return int(lib.carma_mpsd_freq_tile())
+
+
+def mpsd_band(ar_coefs, ma_coefs, sigma, sample_start, freq, percentiles, device=None):
+    """psd_band's percentiles for every series of a set in one call (carma_mpsd_band).  ar_coefs [N, p + 1] highest order
+    first, ma_coefs [N, nma] lowest first, sigma [N]: the samples of all S series back to back, series s owning the rows
+    sample_start[s] ... sample_start[s + 1] - 1 (sample_start [S + 1], from 0, strictly increasing, ending at N).  freq: [nf]
+    for every series, or [S, nf] with a grid per series.  percentiles: 1 ... 4 values in [0, 100].  Returns band [S, nf, nperc]."""
+    ar = as_f64(np.atleast_2d(np.asarray(ar_coefs, dtype=float)))
+    ma = as_f64(np.atleast_2d(np.asarray(ma_coefs, dtype=float)))
+    sg = as_f64(np.ravel(sigma))
+    pc = as_f64(np.ravel(percentiles))
+    st = np.ascontiguousarray(np.ravel(sample_start), dtype=np.int64)
+    if ar.ndim != 2 or ma.ndim != 2:
+        raise ValueError("mpsd_band: ar_coefs and ma_coefs must be [N, p + 1] and [N, nma]")
+    N = ar.shape[0]
+    if ma.shape[0] != N or sg.size != N:
+        raise ValueError("mpsd_band: one row of AR coefficients, MA coefficients and one sigma per sample")
+    if st.size < 2 or st[0] != 0 or st[-1] != N or (np.diff(st) < 1).any():
+        raise ValueError("mpsd_band: sample_start must be [S + 1], start at 0, increase strictly and end at N = %d" % N)
+    S = st.size - 1
+    fr = as_f64(np.asarray(freq, dtype=float))
+    if fr.ndim == 1:
+        fr = as_f64(np.broadcast_to(fr, (S, fr.size)))
+    if fr.ndim != 2 or fr.shape[0] != S or fr.shape[1] < 1:
+        raise ValueError("mpsd_band: freq must be [nf] or [%d, nf] with nf >= 1, got %r" % (S, fr.shape))
+    if not 1 <= pc.size <= 4:
+        raise ValueError("mpsd_band: 1 ... 4 percentiles, got %d" % pc.size)
+    band = np.empty((S, fr.shape[1], pc.size))
+    check(lib.carma_mpsd_band(ar.shape[1], ma.shape[1], ptr(ar), ptr(ma), ptr(sg), st.ctypes.data_as(C.POINTER(C.c_long)), S,
+                              ptr(fr), fr.shape[1], ptr(pc), pc.size, ptr(band), default_device() if device is None else device),
+          "carma_mpsd_band")
+    return band
 
 
 def pt_sample_sharded(contexts, nsamples, thin=1, comm=None):

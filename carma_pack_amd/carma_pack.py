@@ -316,20 +316,33 @@ class CarmaSample(MCMCSample):
     def _ar_coefs(self):
         self._samples["ar_coefs"] = _poly_from_roots(self._samples["ar_roots"]).real
 
-    def _ma_coefs(self, trace):
-        ns = trace.shape[0]
-        if self.q == 0:
-            self._samples["ma_coefs"] = np.ones((ns, 1))
-            return
-        roots = _roots_from_log_quads(trace[:, 3 + self.p:3 + self.p + self.q])
+    @staticmethod
+    def _ma_coefs_of(trace, p, q):
+        """[ns, q + 1] MA coefficients, lowest order first and scaled to a leading 1, of the rows of a trace."""
+        if q == 0:
+            return np.ones((trace.shape[0], 1))
+        roots = _roots_from_log_quads(trace[:, 3 + p:3 + p + q])
         c = _poly_from_roots(roots)
-        self._samples["ma_coefs"] = (c / c[:, self.q:self.q + 1])[:, ::-1].real
+        return (c / c[:, q:q + 1])[:, ::-1].real
+
+    def _ma_coefs(self, trace):
+        self._samples["ma_coefs"] = self._ma_coefs_of(trace, self.p, self.q)
+
+    @staticmethod
+    def _sigma_inputs_of(trace, p, q):
+        """(ar_roots, ma_coefs, var) of the rows of a trace, derived step by step as the constructor derives the entries of
+        `_samples` that _sigma_noise reads."""
+        quad = np.exp(trace[:, 3:p + 3])
+        return _roots_from_log_quads(np.log(quad)), CarmaSample._ma_coefs_of(trace, p, q), trace[:, 0] ** 2
 
     def _sigma_noise(self):
         """sigma of the driving noise per sample = sqrt(var / Variance(roots, ma, 1)) (reference :513-546): one launch for all
-        samples (carma_sigma_noise_batch)."""
-        self._samples["sigma"] = carmcmcLib.sigma_noise_batch(self._samples["ar_roots"], self._samples["ma_coefs"],
-                                                              self._samples["var"])
+        samples (carma_sigma_noise_batch) -- unless the sampler holds them already, computed with those of the other series of
+        a set in one launch (SetRunSampler.getSigmaNoise)."""
+        args = self._samples["ar_roots"], self._samples["ma_coefs"], self._samples["var"]
+        offer = getattr(self._sampler, "getSigmaNoise", None)
+        sigma = offer(*args) if offer is not None else None
+        self._samples["sigma"] = carmcmcLib.sigma_noise_batch(*args) if sigma is None else sigma
 
     def add_mle(self, MLE):
         x = np.asarray(MLE.x, dtype=float)
@@ -803,14 +816,56 @@ class CarmaModelSet(object):
         if p > 1:
             ns = samples.shape[2]
             loglik = mc.logdensity(samples[:, 0].reshape(-1, d), np.repeat(order, ns), ignore_prior=True).reshape(S, ns)
+        # and the "sigma" column: the samples of all series back to back, one launch (one lane per sample)
+        sigma = [None] * S
+        if p > 1:
+            ins = [CarmaSample._sigma_inputs_of(samples[j, 0], p, q) for j in range(S)]
+            flat = carmcmcLib.sigma_noise_batch(*(np.concatenate([a[k] for a in ins]) for k in range(3)))
+            sigma = [ins[j] + (flat[j * ns:(j + 1) * ns],) for j in range(S)]
         out = [None] * S
         for j, s in enumerate(order):
             m = self.models[s]
-            run = carmcmcLib.SetRunSampler(mc, s, samples[j], logposts[j], None if loglik is None else loglik[j], acc[j], swp[j])
+            run = carmcmcLib.SetRunSampler(mc, s, samples[j], logposts[j], None if loglik is None else loglik[j], acc[j], swp[j],
+                                           sigma=sigma[j])
             out[s] = Car1Sample(m.time, m.y, m.ysig, run) if p == 1 else CarmaSample(m.time, m.y, m.ysig, run, q=q)
             m.mcmc_sample = out[s]
         self.mcmc_samples = out
         return out
+
+    def power_spectrum_band(self, percentile=68.0, nsamples=None, freq=None, samples=None):
+        """CarmaSample.power_spectrum_band of EVERY series in one call per order present (carma_mpsd_band): the posterior median
+        and `percentile` credibility band of the power spectrum.  samples: a list of S CarmaSample / Car1Sample, by default
+        self.mcmc_samples of run_mcmc.  freq: None (each series' own 1000 log-spaced frequencies), one grid for all series, or
+        [S, nf].  nsamples: the evenly spaced subsample of each series that the single-series call takes.  Returns
+        (lower, upper, median, frequencies), each [S, nf]."""
+        S = self.nseries
+        if samples is None:
+            samples = self.mcmc_samples
+            if samples is None:
+                raise ValueError("no samples: call run_mcmc first, or pass samples=")
+        samples = list(samples)
+        if len(samples) != S:
+            raise ValueError("samples must hold one sample object per series (%d), got %d" % (S, len(samples)))
+        if freq is None:
+            freq = np.stack([smp._psd_frequencies() for smp in samples])
+        else:
+            freq = np.asarray(freq, dtype=float)
+            if freq.ndim == 1:
+                freq = np.broadcast_to(freq, (S, freq.size))
+            if freq.ndim != 2 or freq.shape[0] != S or freq.shape[1] < 1:
+                raise ValueError("freq must be [nf] or [%d, nf], got %r" % (S, freq.shape))
+        lower = (100.0 - percentile) / 2.0
+        ins = []
+        for smp in samples:
+            index = smp._subsample(nsamples, smp._samples["sigma"].shape[0])
+            ins.append(smp._psd_inputs(index))
+        band = np.empty((S, freq.shape[1], 3))
+        for _, idx in group_by_order([(a.shape[1], m.shape[1]) for a, m, _ in ins]).items():
+            start = np.zeros(len(idx) + 1, dtype=np.int64)
+            start[1:] = np.cumsum([ins[s][2].size for s in idx])
+            band[idx] = carmcmcLib.mpsd_band(*(np.concatenate([ins[s][k] for s in idx]) for k in range(3)), start, freq[idx],
+                                             [lower, 50.0, 100.0 - lower])
+        return band[:, :, 0], band[:, :, 2], band[:, :, 1], np.array(freq)
 
     def _set_starts(self, p, q, ntrials, seed):
         """The starts of get_mle(starts="set"): CarmaModel._mle_problem's short tempered run (25 adapting iterations, one

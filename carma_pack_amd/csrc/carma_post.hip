@@ -23,11 +23,10 @@
 
 #include "../../include/carma_mi355.h"
 #include "carma_host.h"
+#include "carma_post_dev.h"
 
 namespace carma {
 
-constexpr int POST_PMAX = CARMA_PMAX;       // AR order <= 7: alpha has <= 8 coefficients, delta <= 7
-constexpr int POST_NQ = 8;                  // order statistics per row: two per percentile, four percentiles
 constexpr int PSD_FT = 8;                   // frequencies per lane of k_psd_grid
 constexpr int QT = 1024;                    // threads of k_row_quantiles (one workgroup per row)
 constexpr int QU = 4;                       // independent loads in flight per thread and trip of its row loops
@@ -99,40 +98,9 @@ __global__ __launch_bounds__(256) void k_psd_grid(int nar, int nma, const double
     const double sg = sigma[s], s2 = sg * sg;
     const int f0 = blockIdx.y * PSD_FT;
     for (int i = 0; i < PSD_FT && f0 + i < nf; i++) {
-        const double w = 2.0 * M_PI * freq[f0 + i];           // z = i w:  acc z + c = (c - acc.im w) + i (acc.re w)
-        double are = 0.0, aim = 0.0;
-        for (int k = 0; k < nar; k++) {
-            const double t = are;
-            are = fma(-aim, w, a[k]);
-            aim = t * w;
-        }
-        double mre = 0.0, mim = 0.0;
-        for (int k = nma - 1; k >= 0; k--) {
-            const double t = mre;
-            mre = fma(-mim, w, b[k]);
-            mim = t * w;
-        }
-        psd[(long)(f0 + i) * ns + s] = s2 * (mre * mre + mim * mim) / (are * are + aim * aim);
+        const double w = 2.0 * M_PI * freq[f0 + i];
+        psd[(long)(f0 + i) * ns + s] = psd_value(nar, nma, a, b, s2, w);
     }
-}
-
-// order-preserving image of a double: unsigned comparison of the keys == numerical comparison of the values (-0 < +0)
-__device__ __forceinline__ unsigned long long key_of(double x)
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    return b ^ ((b >> 63) ? ~0ull : 0x8000000000000000ull);
-}
-__device__ __forceinline__ double value_of(unsigned long long k)
-{
-    const unsigned long long b = k ^ ((k >> 63) ? 0x8000000000000000ull : ~0ull);
-    return __longlong_as_double((long long)b);
-}
-
-// numpy's _lerp (np.percentile, method "linear"): a + (b - a) t, from the other end for t >= 0.5
-__device__ __forceinline__ double np_lerp(double a, double b, double t)
-{
-    const double d = b - a;
-    return t >= 0.5 ? b - d * (1.0 - t) : a + d * t;
 }
 
 // One workgroup per row.  ranks[2 j], ranks[2 j + 1] = the order statistics either side of percentile j, gammas[j] its
@@ -288,6 +256,25 @@ struct DevBufs {                                              // frees what it h
         return e;
     }
 };
+
+hipError_t post_grid_band(int nar, int nma, const double* d_ar, const double* d_ma, const double* d_sigma, int ns,
+                          const double* d_freq, int nf, int nperc, const int* d_ranks, const double* d_gammas, double* d_grid,
+                          int fc, double* d_band)
+{
+    hipError_t e = hipSuccess;
+    for (int f0 = 0; f0 < nf && e == hipSuccess; f0 += fc) {
+        const int nfc = std::min(fc, nf - f0);
+        hipLaunchKernelGGL(k_psd_grid, dim3((ns + 255) / 256, (nfc + PSD_FT - 1) / PSD_FT), dim3(256), 0, nullptr, nar, nma, d_ar,
+                           d_ma, d_sigma, ns, d_freq + f0, nfc, d_grid);
+        e = hipGetLastError();
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_row_quantiles, dim3(nfc), dim3(QT), 0, nullptr, d_grid, ns, 2 * nperc, d_ranks, d_gammas,
+                               d_band + (size_t)f0 * nperc);
+            e = hipGetLastError();
+        }
+    }
+    return e;
+}
 
 }  // namespace carma
 

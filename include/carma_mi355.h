@@ -348,6 +348,26 @@ int carma_psd_band(int nar, int nma, const double* ar_coefs, const double* ma_co
                    int device);
 
 /*
+ * carma_mpsd_band == carma_psd_band's percentiles for EVERY series of a sampled set in one call (CarmaModelSet.power_spectrum_band):
+ *   nseries series, series s holding the samples sample_start[s] ... sample_start[s + 1] - 1 of the N = sample_start[nseries]
+ *   rows of ar_coefs [N][nar] (highest order first), ma_coefs [N][nma] (lowest first) and sigma [N]; sample_start[0] = 0,
+ *   strictly increasing.  freq = [nseries][nf], every series its own grid; percentiles [nperc], 1 <= nperc <= 4, in [0, 100];
+ *   band = [nseries][nf][nperc].  All host pointers.  One device block and one copy each way per call.  A series of at most
+ *   carma_mpsd_fused_max() samples is served by a kernel that forms the spectrum values of a row in LDS, sorts them there and
+ *   writes only the percentiles (one launch for all such series, a workgroup per series and carma_mpsd_freq_tile() frequencies);
+ *   a longer one goes through carma_psd_band's grid and row-selection kernels inside the same call.  Either way band[s] is what
+ *   carma_psd_band gives for series s alone: the same spectrum values to the bit, the exact order statistics, numpy's linear
+ *   interpolation, and NaN for every percentile of a row that holds a NaN (that row only).
+ *   Bad arguments -- a null pointer, nar / nma outside carma_psd_band's ranges, nseries < 1, nf < 1, a sample_start that does
+ *   not start at 0 or does not increase, nperc outside 1 ... 4, a percentile outside [0, 100] -- return CARMA_EINVAL before any
+ *   device work.
+ */
+int carma_mpsd_band(int nar, int nma, const double* ar_coefs, const double* ma_coefs, const double* sigma, const long* sample_start,
+                    int nseries, const double* freq, int nf, const double* percentiles, int nperc, double* band, int device);
+int carma_mpsd_fused_max(void);
+int carma_mpsd_freq_tile(void);
+
+/*
  * Parallel-tempered Robust-Adaptive-Metropolis sampler == RunCarmaSampler / RunCar1Sampler
  * (src/carmcmc.cpp:30-177; bindings run_mcmc_car1 / run_mcmc_carma, boost_python_wrapper.cpp:76-77)
  * with every chain advanced on the GPU by one persistent kernel (carma_pt.hip).
