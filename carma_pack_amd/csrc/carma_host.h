@@ -1,9 +1,10 @@
-// carma_host.h -- host-side state behind the C ABI (carma_capi.hip, carma_pt_host.hip)
+// carma_host.h -- host-side state behind the C ABI (carma_capi.hip, carma_pt_host.hip): device allocation, the single-series
+// context Ctx, and the state the two parallel-tempering samplers share (PtEnsemble and its pt_ens_* functions; the host-only
+// decisions of the samplers -- ladder, initial factor, chunking, starting values -- are in carma_pt_sched.h)
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <random>
 #include <vector>
 
 #include "carma_launch.h"
@@ -25,24 +26,32 @@ static inline hipError_t dev_free(void* p) { return carma_dev_free(p); }
 
 namespace carma {
 
-// Parallel-tempering sampler state of one context (carma_pt_host.hip, carma_shard.hip)
-struct PtState {
-    int T = 0, R = 0;
-    unsigned T_global = 0, slot0 = 0, replica0 = 0;
+// What both parallel-tempering samplers hold: an ensemble of R ladders of T chains (chain = ladder * T + temperature) with its
+// buffers.  carma_pt_* (PtState below): the R replicas of one series; carma_mpt_* (MptState, carma_mseries.hip): the ladders of
+// all runs of a call.  The pt_ens_* functions (carma_pt_host.hip) work on this part alone.
+struct PtEnsemble {
+    int T = 0, R = 0;                  // temperatures of a ladder, ladders (what PtLaunch::T and ::R receive)
     int maxiter = 0;
     uint64_t seed = 0;
-    unsigned long long iter = 0;
+    unsigned long long iter = 0, stat_iters = 0;
+    bool started = false;
     std::vector<double> temps;
     double *d_temps = nullptr, *d_theta = nullptr, *d_lp = nullptr, *d_chol = nullptr;
-    // lane sampler (use_lane): the factors live in the chain-minor scratch between calls
-    bool lane_factor_loaded = false;   // the scratch holds the current factors (else: take them from d_chol at the next launch)
-    bool chol_stale = false;           // d_chol is behind the scratch (pt_sync_factor brings it up to date)
-    bool ext_state = false;
     unsigned *d_nacc = nullptr, *d_nswap = nullptr;
     double *d_samples = nullptr, *d_slp = nullptr;
-    long cap = 0;
-    bool started = false;
-    unsigned long long stat_iters = 0;
+    long cap = 0;                      // samples per ladder d_samples / d_slp hold; during a sampling call: that call's stride
+    // lane sampler (carma_pt_lane.hip): one chain per lane, an iteration as propose kernel + batched log-density + finish kernel;
+    // the factors live in the chain-minor scratch between calls
+    double* d_scratch = nullptr;       // chain-minor working state (current value, R^T z, packed factor, proposals, ...)
+    bool factor_loaded = false;        // the scratch holds the current factors (else: take them from d_chol at the next launch)
+    bool chol_stale = false;           // d_chol is behind the scratch (pt_ens_sync_factor brings it up to date)
+    bool ext_state = false;            // d_theta / d_lp belong to the caller (carma_pt_bind_state)
+    size_t nchain() const { return (size_t)T * R; }
+};
+
+// Parallel-tempering sampler state of one context (carma_pt_host.hip, carma_shard.hip): the ensemble, and which kernel runs it
+struct PtState : PtEnsemble {
+    unsigned T_global = 0, slot0 = 0, replica0 = 0;
     // row-variant kernel (k_pt_row): ladders spread over wpl workgroups, swap through global staging
     bool use_row = false;
     int wpl = 0;
@@ -50,9 +59,7 @@ struct PtState {
     unsigned long long epoch = 0;               // launches so far (PtRowSync::epoch)
     unsigned* d_abort = nullptr;
     double* d_backup = nullptr;         // chain state before the chunk in flight (theta, logpost, chol): abort recovery
-    // large ensembles (carma_pt_lane.hip): one chain per lane, an iteration as propose kernel + batched log-density + finish kernel
-    bool use_lane = false;
-    double* d_lane_scratch = nullptr;   // chain-minor working state (current value, R^T z, packed factor, proposals, ...)
+    bool use_lane = false;              // large ensembles: the lane sampler (d_scratch)
     // ladder sharded across ranks (carma_shard.hip): boundary staging and statistics
     double *d_send = nullptr, *d_recv = nullptr;       // [R][d+1] each
     unsigned* d_bnd_swaps = nullptr;                   // [1] accepted boundary swaps (this block's side)
@@ -92,10 +99,6 @@ void set_prior_bounds(Prior& pr, const double* t, long n, double max_stdev);
 bool series_repeated_dt(const double* packed, long n);
 // AR roots in the order the KalmanFilterp-type kernels expect (carma_normalize_roots); CARMA_EINVAL unless closed under conjugation
 int normalize_roots(int p, const double* om, double* out);
-// starting values of the samplers (carma_pt_host.hip): one draw from the reference's starting-value distribution for a series
-// (sorted, distinct times), and the generator of a chain's draws -- keyed by the chain's global slot and the attempt
-void draw_start(const double* t, const double* y, int n, const Prior& pr, int p, int q, std::mt19937_64& rng, double* theta);
-std::mt19937_64 start_rng(uint64_t seed, uint64_t gslot, int round);
 int hip_fail(hipError_t e, const char* what);
 int select_device(int device);
 void pt_state_free(Ctx* c);
@@ -104,10 +107,29 @@ void pt_state_free(Ctx* c);
 int pt_enqueue(Ctx* c, long niter, int do_exchange, int thin, long* save_offset, hipStream_t st);
 // after the stream has been synchronised: did a cross-workgroup rendezvous of the row kernel time out?
 int pt_check_abort(Ctx* c, bool* aborted);
-// The lane sampler keeps the proposal factors in its chain-minor working state between calls.  pt_sync_factor: bring the chain-major
-// array d_chol up to date before it is read (enqueued on st; no-op for the other kernels); pt_factor_written: d_chol was written, the
-// next launch reloads.
-hipError_t pt_sync_factor(Ctx* c, hipStream_t st);
-void pt_factor_written(Ctx* c);
+
+// ---- the ensemble (PtEnsemble) of either sampler; d: parameter dimension.  The hipError_t ones leave the failure to the entry point.
+// R ladders of T chains with their buffers: allocated, temps[T] and the factors chol[R * T][d * d] uploaded, counters zeroed
+hipError_t pt_ens_create(PtEnsemble* s, int T, int R, int d, const std::vector<double>& temps, const double* chol);
+void pt_ens_release(PtEnsemble* s);   // every device buffer of the ensemble (not the caller's: ext_state)
+// arguments of a launch of ch iterations from the current one: the whole ensemble is the whole ladder (slot0 = 0, T_global = T,
+// replica0 = 0); n: (longest) series length
+PtLaunch pt_ens_launch(const PtEnsemble* s, int d, int q, int n, long ch, int do_exchange, int thin, long save_offset);
+void pt_ens_advance(PtEnsemble* s, long ch, int thin, long* save_offset);   // ... and the books after it has been enqueued
+hipError_t pt_ens_set_chains(PtEnsemble* s, int d, const double* theta, const double* lp);
+hipError_t pt_ens_get_chains(const PtEnsemble* s, int d, double* theta, double* lp);   // either may be null
+// Room for nsamples per ladder, which become the stride of the launches that follow (PtLaunch::sample_cap); *capacity: what the
+// buffers hold, for the caller to put back into s->cap when the call ends.  fetch: those samples, [R][nsamples][d] and [R][nsamples]
+hipError_t pt_ens_reserve_samples(PtEnsemble* s, int d, int nsamples, long* capacity);
+hipError_t pt_ens_fetch_samples(const PtEnsemble* s, int d, int nsamples, double* samples, double* logposts);
+// rates per chain since the last reset (entry i of swap_rate = swaps between temperature i and i - 1); either may be null
+hipError_t pt_ens_stats(PtEnsemble* s, double* accept_rate, double* swap_rate, int reset);
+// The lane sampler keeps the proposal factors in its scratch between calls.  sync: bring the chain-major array d_chol up to date
+// before it is read (enqueued on st; nothing to do after the other kernels); written: d_chol was written, the next launch reloads.
+// get / set: [R][T][d * d] to and from the host, after what is in flight on st.
+hipError_t pt_ens_sync_factor(PtEnsemble* s, int d, hipStream_t st);
+void pt_ens_factor_written(PtEnsemble* s);
+hipError_t pt_ens_get_factor(PtEnsemble* s, int d, hipStream_t st, double* chol);
+hipError_t pt_ens_set_factor(PtEnsemble* s, int d, hipStream_t st, const double* chol);
 
 }  // namespace carma

@@ -43,6 +43,7 @@
 #include "carma_host.h"
 #include "carma_lane.h"
 #include "carma_predict.h"
+#include "carma_pt_sched.h"
 
 namespace carma {
 
@@ -311,32 +312,14 @@ struct DevBuf {
     T* as() const { return static_cast<T*>(p); }
 };
 
-// Sampler state of a multi-series context (carma_mpt_*): M runs of R ladders of T chains = one ensemble of M R ladders
-struct MptState {
-    int M = 0, R = 0, T = 0;          // runs, replicas per run, temperatures
-    long nlad = 0, nc = 0;            // M R ladders, M R T chains
+// Sampler state of a multi-series context (carma_mpt_*): M runs of `reps` ladders of T chains = one ensemble of R = M reps ladders
+struct MptState : PtEnsemble {
+    int M = 0, reps = 0;              // runs, replicas per run
     std::vector<int> series;          // [M] series of run j
     int nmax = 0;                     // the longest series of the call
     bool any_plain = false, any_rep = false;   // the call holds irregular / regular-cadence series
-    int maxiter = 0;
-    uint64_t seed = 0;
-    unsigned long long iter = 0, stat_iters = 0;
-    bool started = false;
-    bool factor_loaded = false;       // the chain-minor working state holds the current factors (else: d_chol does)
-    bool chol_stale = false;          // d_chol is behind the working state
-    std::vector<double> temps;
-    int* d_lser = nullptr;            // [M R] series of every ladder, uploaded once
+    int* d_lser = nullptr;            // [R] series of every ladder, uploaded once
     char* d_rep = nullptr;            // [S] SERIES_REPEATED_DT of every series
-    double *d_temps = nullptr, *d_theta = nullptr, *d_lp = nullptr, *d_chol = nullptr, *d_scratch = nullptr;
-    unsigned *d_nacc = nullptr, *d_nswap = nullptr;
-    double *d_samples = nullptr, *d_slp = nullptr;
-    long cap = 0;
-    void release()
-    {
-        for (void* p : {(void*)d_lser, (void*)d_rep, (void*)d_temps, (void*)d_theta, (void*)d_lp, (void*)d_chol, (void*)d_scratch,
-                        (void*)d_nacc, (void*)d_nswap, (void*)d_samples, (void*)d_slp})
-            if (p) (void)dev_free(p);
-    }
 };
 
 // Multi-series context: the series of a set packed one after another in HBM, each as carma_ctx_create packs one
@@ -472,7 +455,9 @@ static hipError_t launch_logdens_chains_ms(const Mctx* c, const MptState* s, con
 static void mpt_free(Mctx* c)
 {
     if (!c->mpt) return;
-    c->mpt->release();
+    pt_ens_release(c->mpt);
+    if (c->mpt->d_lser) (void)dev_free(c->mpt->d_lser);
+    if (c->mpt->d_rep) (void)dev_free(c->mpt->d_rep);
     delete c->mpt;
     c->mpt = nullptr;
 }
@@ -515,29 +500,8 @@ static int mpt_iterate(Mctx* c, long niter, int do_exchange, int thin, long* sav
     };
     long left = niter;
     while (left > 0) {
-        long ch = std::min(left, chunk0);
-        if (thin > 0) {
-            ch = std::max<long>(thin, (ch / thin) * thin);   // whole thinning intervals per chunk
-            ch = std::min(ch, left);
-        }
-        PtLaunch L{};
-        L.d = c->d;
-        L.q = c->q;
-        L.n = s->nmax;
-        L.T = s->T;
-        L.R = (int)s->nlad;
-        L.maxiter = s->maxiter;
-        L.iter0 = s->iter;
-        L.niter = (int)ch;
-        L.do_exchange = do_exchange;
-        L.save_thin = thin;
-        L.save_offset = save_offset ? *save_offset : 0;
-        L.sample_cap = s->cap;
-        L.seed0 = (unsigned)(s->seed & 0xffffffffu);
-        L.seed1 = (unsigned)(s->seed >> 32);
-        L.slot0 = 0;
-        L.T_global = (unsigned)s->T;
-        L.replica0 = 0;
+        const long ch = pt_next_chunk(left, chunk0, thin);
+        const PtLaunch L = pt_ens_launch(s, c->d, c->q, s->nmax, ch, do_exchange, thin, save_offset ? *save_offset : 0);
         hipError_t e = launch_pt_lane_k1(c->p, L, s->d_scratch, k1, s->d_temps, s->d_theta, s->d_lp, s->d_chol, s->d_nacc, s->d_nswap,
                                          s->d_samples, s->d_slp, !s->factor_loaded, c->stream);
         if (e == hipSuccess) {
@@ -546,24 +510,10 @@ static int mpt_iterate(Mctx* c, long niter, int do_exchange, int thin, long* sav
             e = hipStreamSynchronize(c->stream);
         }
         if (e != hipSuccess) return hip_fail(e, "carma_mpt: sampler launch");
-        s->iter += ch;
-        s->stat_iters += ch;
-        if (thin > 0 && save_offset) *save_offset += ch / thin;
+        pt_ens_advance(s, ch, thin, save_offset);
         left -= ch;
     }
     return CARMA_OK;
-}
-
-static double pop_var(const double* y, long n)
-{
-    // src/carmcmc.cpp:85-88
-    double sum = 0, sq = 0;
-    for (long i = 0; i < n; i++) {
-        sum += y[i];
-        sq += y[i] * y[i];
-    }
-    const double mean = sum / (size_t)n;
-    return sq / (size_t)n - mean * mean;
 }
 
 }  // namespace carma
@@ -1060,51 +1010,33 @@ int carma_mpt_create(carma_mctx* h, const int* series, int M, int ntemps, int nr
     MptState* s = new MptState();
     c->mpt = s;
     s->M = M;
-    s->R = nreplicas;
-    s->T = ntemps;
-    s->nlad = (long)M * nreplicas;
-    s->nc = s->nlad * ntemps;
+    s->reps = nreplicas;
     s->maxiter = adapt_iters;
     s->seed = seed;
     s->series.assign(series, series + M);
-    s->temps.resize(ntemps);
-    for (int i = 0; i < ntemps; i++)      // src/carmcmc.cpp:92-95: exp(linspace(0, ln 100, nwalkers)), shared by all runs
-        s->temps[i] = temperatures ? temperatures[i] : (ntemps == 1 ? 1.0 : std::exp(std::log(100.0) * (double)i / (double)(ntemps - 1)));
-    const int d = c->d;
-    const size_t nchain = (size_t)s->nc;
-    // initial proposal factor of run j, from ITS series (src/carmcmc.cpp:132-136 / :50-54): diag 0.01, [0,0] = sqrt(2 var^2 / n),
-    // [2,2] = sqrt(var / n)
-    std::vector<double> chol(nchain * d * d, 0.0);
-    std::vector<int> lser((size_t)s->nlad);
+    std::vector<double> temps;
+    default_ladder(ntemps, temperatures, temps);             // shared by all runs
+    const int d = c->d, nlad = M * nreplicas;
+    const size_t nchain = (size_t)nc_ll;
+    // initial proposal factor of run j, from ITS series
+    std::vector<double> chol(nchain * d * d, 0.0), R0((size_t)d * d);
+    std::vector<int> lser((size_t)nlad);
     for (int j = 0; j < M; j++) {
         const int sj = series[j];
         const long n = c->n[sj];
         s->nmax = std::max(s->nmax, (int)n);
         (c->repdt[sj] ? s->any_rep : s->any_plain) = true;
-        const double var = pop_var(c->y.data() + c->hoff[sj], n);
-        std::vector<double> R0((size_t)d * d, 0.0);
-        for (int i = 0; i < d; i++) R0[(size_t)i * d + i] = 0.01;
-        R0[0] = std::sqrt(2.0 * var * var / n);
-        R0[(size_t)2 * d + 2] = std::sqrt(var / n);
+        initial_factor(pop_var(c->y.data() + c->hoff[sj], n), n, d, R0.data());
         for (size_t k = (size_t)j * nreplicas * ntemps; k < (size_t)(j + 1) * nreplicas * ntemps; k++)
             std::memcpy(&chol[k * d * d], R0.data(), sizeof(double) * d * d);
         for (int r = 0; r < nreplicas; r++) lser[(size_t)j * nreplicas + r] = sj;
     }
-    e = dev_malloc(&s->d_temps, sizeof(double) * ntemps);
-    if (e == hipSuccess) e = dev_malloc(&s->d_theta, sizeof(double) * nchain * d);
-    if (e == hipSuccess) e = dev_malloc(&s->d_lp, sizeof(double) * nchain);
-    if (e == hipSuccess) e = dev_malloc(&s->d_chol, sizeof(double) * nchain * d * d);
-    if (e == hipSuccess) e = dev_malloc(&s->d_nacc, sizeof(unsigned) * nchain);
-    if (e == hipSuccess) e = dev_malloc(&s->d_nswap, sizeof(unsigned) * nchain);
+    e = pt_ens_create(s, ntemps, nlad, d, temps, chol.data());
     if (e == hipSuccess) e = dev_malloc(&s->d_lser, sizeof(int) * lser.size());
     if (e == hipSuccess) e = dev_malloc(&s->d_rep, sizeof(char) * (size_t)c->S);
-    if (e == hipSuccess) e = dev_malloc(&s->d_scratch, sizeof(double) * pt_lane_scratch_doubles(d, s->nc));
-    if (e == hipSuccess) e = hipMemcpy(s->d_temps, s->temps.data(), sizeof(double) * ntemps, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(s->d_chol, chol.data(), sizeof(double) * chol.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = dev_malloc(&s->d_scratch, sizeof(double) * pt_lane_scratch_doubles(d, (long)nchain));
     if (e == hipSuccess) e = hipMemcpy(s->d_lser, lser.data(), sizeof(int) * lser.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(s->d_rep, c->repdt.data(), sizeof(char) * (size_t)c->S, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(s->d_nacc, 0, sizeof(unsigned) * nchain);
-    if (e == hipSuccess) e = hipMemset(s->d_nswap, 0, sizeof(unsigned) * nchain);
     if (e != hipSuccess) {
         const int rc = hip_fail(e, "carma_mpt_create");
         mpt_free(c);
@@ -1122,19 +1054,18 @@ int carma_mpt_set_chains(carma_mctx* h, const double* theta, const double* logpo
         return CARMA_EINVAL;
     }
     Mctx* c = reinterpret_cast<Mctx*>(h);
-    const size_t nchain = (size_t)s->nc;
+    const size_t nchain = s->nchain();
     std::vector<double> lp(nchain);
     if (logpost) {
         std::memcpy(lp.data(), logpost, sizeof(double) * nchain);
     } else {
         std::vector<int> which(nchain);
-        for (size_t k = 0; k < nchain; k++) which[k] = s->series[k / ((size_t)s->R * s->T)];
+        for (size_t k = 0; k < nchain; k++) which[k] = s->series[k / ((size_t)s->reps * s->T)];
         const int rc = carma_mlogdensity_batch(h, theta, which.data(), (int)nchain, 0, lp.data());
         if (rc != CARMA_OK) return rc;
     }
     hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = hipMemcpy(s->d_theta, theta, sizeof(double) * nchain * c->d, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(s->d_lp, lp.data(), sizeof(double) * nchain, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = pt_ens_set_chains(s, c->d, theta, lp.data());
     if (e != hipSuccess) return hip_fail(e, "carma_mpt_set_chains");
     s->started = true;
     return CARMA_OK;
@@ -1146,8 +1077,7 @@ int carma_mpt_get_chains(carma_mctx* h, double* theta, double* logpost)
     if (!s) return CARMA_EINVAL;
     Mctx* c = reinterpret_cast<Mctx*>(h);
     hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess && theta) e = hipMemcpy(theta, s->d_theta, sizeof(double) * (size_t)s->nc * c->d, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && logpost) e = hipMemcpy(logpost, s->d_lp, sizeof(double) * (size_t)s->nc, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = pt_ens_get_chains(s, c->d, theta, logpost);
     if (e != hipSuccess) return hip_fail(e, "carma_mpt_get_chains");
     return CARMA_OK;
 }
@@ -1158,11 +1088,11 @@ int carma_mpt_start(carma_mctx* h, const double* init)
     if (!s) return CARMA_EINVAL;
     Mctx* c = reinterpret_cast<Mctx*>(h);
     const int d = c->d, M = s->M;
-    const size_t per_run = (size_t)s->R * s->T, nchain = (size_t)s->nc;
+    const size_t per_run = (size_t)s->reps * s->T, nchain = s->nchain();
     std::vector<double> theta(nchain * d), lp(nchain, -std::numeric_limits<double>::infinity());
     std::vector<char> done(nchain, 0);
-    // a run's init row is honoured when its log-density on the run's series is finite (as carma_pt_start; src/samplers.cpp:75-93):
-    // all M rows in one launch
+    // a run's init row is honoured when its log-density on the run's series is finite (src/samplers.cpp:75-93): all M rows in one
+    // launch
     if (init) {
         std::vector<double> l0(M);
         const int rc = carma_mlogdensity_batch(h, init, s->series.data(), M, 0, l0.data());
@@ -1176,35 +1106,22 @@ int carma_mpt_start(carma_mctx* h, const double* init)
             }
         }
     }
-    // Drawn starts: chain k = ladder T + temperature of the ENSEMBLE keys its generator (start_rng, as carma_pt_start with
-    // replica0 = 0), so run j draws what a single-series sampler sharded to replica0 = j R draws; the candidates still pending
-    // of ALL runs are evaluated in one launch per round.
-    std::vector<size_t> todo;
-    std::vector<double> cand, out;
+    // Drawn starts: chain k = ladder T + temperature of the ENSEMBLE keys its generator, so run j draws what a single-series sampler
+    // sharded to replica0 = j R draws; the candidates still pending of ALL runs are evaluated in one launch per round.
     std::vector<int> which;
-    for (int round = 0; round < 4000; round++) {
-        todo.clear();
-        for (size_t k = 0; k < nchain; k++)
-            if (!done[k]) todo.push_back(k);
-        if (todo.empty()) break;
-        cand.resize(todo.size() * d);
-        out.resize(todo.size());
-        which.resize(todo.size());
-        for (size_t i = 0; i < todo.size(); i++) {
-            const int sj = s->series[todo[i] / per_run];
-            std::mt19937_64 rng = start_rng(s->seed, (uint64_t)todo[i], round);
-            draw_start(c->t.data() + c->hoff[sj], c->y.data() + c->hoff[sj], c->n[sj], c->pr[sj], c->p, c->q, rng, &cand[i * d]);
-            which[i] = sj;
-        }
-        const int rc = carma_mlogdensity_batch(h, cand.data(), which.data(), (int)todo.size(), 0, out.data());
-        if (rc != CARMA_OK) return rc;
-        for (size_t i = 0; i < todo.size(); i++)
-            if (std::isfinite(out[i])) {
-                std::memcpy(&theta[todo[i] * d], &cand[i * d], sizeof(double) * d);
-                lp[todo[i]] = out[i];
-                done[todo[i]] = 1;
-            }
-    }
+    const int rc = find_starts(
+        nchain, d, theta.data(), lp.data(), done.data(),
+        [&](size_t k, int round, double* out) {
+            const int sj = s->series[k / per_run];
+            std::mt19937_64 rng = start_rng(s->seed, (uint64_t)k, round);
+            draw_start(c->t.data() + c->hoff[sj], c->y.data() + c->hoff[sj], c->n[sj], c->pr[sj], c->p, c->q, rng, out);
+        },
+        [&](const double* cand, const size_t* idx, size_t m, double* out) {
+            which.resize(m);
+            for (size_t i = 0; i < m; i++) which[i] = s->series[idx[i] / per_run];
+            return carma_mlogdensity_batch(h, cand, which.data(), (int)m, 0, out);
+        });
+    if (rc != CARMA_OK) return rc;
     for (size_t k = 0; k < nchain; k++)
         if (!done[k]) {
             set_error("carma_mpt_start: no finite starting value found for chain %zu of run %zu (series %d)", k % per_run, k / per_run,
@@ -1214,27 +1131,13 @@ int carma_mpt_start(carma_mctx* h, const double* init)
     return carma_mpt_set_chains(h, theta.data(), lp.data());
 }
 
-// the chain-major factors brought up to date with the working state, and waited for
-static hipError_t mpt_sync_factor(Mctx* c)
-{
-    MptState* s = c->mpt;
-    hipError_t e = hipSuccess;
-    if (s->chol_stale) {
-        e = pt_lane_store_factor(c->d, s->T, (int)s->nlad, s->d_scratch, s->d_chol, c->stream);
-        if (e == hipSuccess) s->chol_stale = false;
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    return e;
-}
-
 int carma_mpt_get_factor(carma_mctx* h, double* chol)
 {
     MptState* s = mpt_state(h, "carma_mpt_get_factor", false);
     if (!s || !chol) return CARMA_EINVAL;
     Mctx* c = reinterpret_cast<Mctx*>(h);
     hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = mpt_sync_factor(c);
-    if (e == hipSuccess) e = hipMemcpy(chol, s->d_chol, sizeof(double) * (size_t)s->nc * c->d * c->d, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = pt_ens_get_factor(s, c->d, c->stream, chol);
     if (e != hipSuccess) return hip_fail(e, "carma_mpt_get_factor");
     return CARMA_OK;
 }
@@ -1245,11 +1148,8 @@ int carma_mpt_set_factor(carma_mctx* h, const double* chol)
     if (!s || !chol) return CARMA_EINVAL;
     Mctx* c = reinterpret_cast<Mctx*>(h);
     hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(s->d_chol, chol, sizeof(double) * (size_t)s->nc * c->d * c->d, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = pt_ens_set_factor(s, c->d, c->stream, chol);
     if (e != hipSuccess) return hip_fail(e, "carma_mpt_set_factor");
-    s->factor_loaded = false;
-    s->chol_stale = false;
     return CARMA_OK;
 }
 
@@ -1278,32 +1178,21 @@ int carma_mpt_sample(carma_mctx* h, int nsamples, int thin, double* samples, dou
     Mctx* c = reinterpret_cast<Mctx*>(h);
     hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    const size_t nlp = (size_t)s->nlad * nsamples, bytes = sizeof(double) * nlp * c->d;
-    if (s->cap < nsamples) {
-        if (s->d_samples) (void)dev_free(s->d_samples);
-        if (s->d_slp) (void)dev_free(s->d_slp);
-        s->d_samples = s->d_slp = nullptr;
-        s->cap = 0;
-        e = dev_malloc(&s->d_samples, bytes);
-        if (e == hipSuccess) e = dev_malloc(&s->d_slp, sizeof(double) * nlp);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("carma_mpt_sample: no device memory for the sample buffer: %zu bytes asked for (%ld ladders x %d samples x %d)",
-                      bytes + sizeof(double) * nlp, s->nlad, nsamples, c->d);
-            return CARMA_ENOMEM;
-        }
-        s->cap = nsamples;
+    long capacity = 0;
+    e = pt_ens_reserve_samples(s, c->d, nsamples, &capacity);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("carma_mpt_sample: no device memory for the sample buffer: %zu bytes asked for (%ld ladders x %d samples x %d)",
+                  sizeof(double) * (size_t)s->R * nsamples * (c->d + 1), (long)s->R, nsamples, c->d);
+        return CARMA_ENOMEM;
     }
     long off = 0;
-    const long cap_saved = s->cap;
-    s->cap = nsamples;   // stride of this call's output
     int rc = mpt_iterate(c, (long)nsamples * thin, 1, thin, &off);
     if (rc == CARMA_OK) {
-        e = hipMemcpy(samples, s->d_samples, bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(logposts, s->d_slp, sizeof(double) * nlp, hipMemcpyDeviceToHost);
+        e = pt_ens_fetch_samples(s, c->d, nsamples, samples, logposts);
         if (e != hipSuccess) rc = hip_fail(e, "carma_mpt_sample: D2H");
     }
-    s->cap = cap_saved;
+    s->cap = capacity;
     return rc;
 }
 
@@ -1312,22 +1201,9 @@ int carma_mpt_stats(carma_mctx* h, double* accept_rate, double* swap_rate, int r
     MptState* s = mpt_state(h, "carma_mpt_stats", false);
     if (!s) return CARMA_EINVAL;
     Mctx* c = reinterpret_cast<Mctx*>(h);
-    const size_t nchain = (size_t)s->nc;
-    std::vector<unsigned> a(nchain), w(nchain);
     hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = hipMemcpy(a.data(), s->d_nacc, sizeof(unsigned) * nchain, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(w.data(), s->d_nswap, sizeof(unsigned) * nchain, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = pt_ens_stats(s, accept_rate, swap_rate, reset);
     if (e != hipSuccess) return hip_fail(e, "carma_mpt_stats");
-    const double it = s->stat_iters ? (double)s->stat_iters : 1.0;
-    for (size_t k = 0; k < nchain; k++) {
-        if (accept_rate) accept_rate[k] = a[k] / it;
-        if (swap_rate) swap_rate[k] = w[k] / it;   // entry i = swaps between temperature i and i-1
-    }
-    if (reset) {
-        (void)hipMemset(s->d_nacc, 0, sizeof(unsigned) * nchain);
-        (void)hipMemset(s->d_nswap, 0, sizeof(unsigned) * nchain);
-        s->stat_iters = 0;
-    }
     return CARMA_OK;
 }
 
@@ -1346,7 +1222,7 @@ int carma_mpt_logdensity(carma_mctx* h, const double* theta, double* out)
         return CARMA_EINVAL;
     }
     Mctx* c = reinterpret_cast<Mctx*>(h);
-    const size_t nchain = (size_t)s->nc, GUARD = 64;
+    const size_t nchain = s->nchain(), GUARD = 64;
     // [nc][d] proposals, [nc] results, then GUARD words nobody may write: a kernel whose idle lanes stored would show here
     std::vector<double> res(nchain + GUARD, 0.0);
     const double mark = -12345.678;
@@ -1356,7 +1232,7 @@ int carma_mpt_logdensity(carma_mctx* h, const double* theta, double* out)
     double *d_th = c->k_res.as<double>(), *d_ll = d_th + nchain * c->d;
     if (e == hipSuccess) e = hipMemcpyAsync(d_th, theta, sizeof(double) * nchain * c->d, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_ll, res.data(), sizeof(double) * res.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_logdens_chains_ms(c, s, d_th, s->nc, d_ll, c->stream);
+    if (e == hipSuccess) e = launch_logdens_chains_ms(c, s, d_th, (long)nchain, d_ll, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(res.data(), d_ll, sizeof(double) * res.size(), hipMemcpyDeviceToHost, c->stream);
     const hipError_t es = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = es;

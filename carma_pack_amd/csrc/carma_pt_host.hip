@@ -15,55 +15,167 @@
 
 #include "../../include/carma_mi355.h"
 #include "carma_host.h"
+#include "carma_pt_sched.h"
 
 namespace carma {
+
+// ---- the ensemble both samplers hold (PtEnsemble, carma_host.h) ------------------------------------------------------------------
+hipError_t pt_ens_create(PtEnsemble* s, int T, int R, int d, const std::vector<double>& temps, const double* chol)
+{
+    s->T = T;
+    s->R = R;
+    s->temps = temps;
+    const size_t nchain = s->nchain();
+    hipError_t e = dev_malloc(&s->d_temps, sizeof(double) * T);
+    if (e == hipSuccess) e = dev_malloc(&s->d_theta, sizeof(double) * nchain * d);
+    if (e == hipSuccess) e = dev_malloc(&s->d_lp, sizeof(double) * nchain);
+    if (e == hipSuccess) e = dev_malloc(&s->d_chol, sizeof(double) * nchain * d * d);
+    if (e == hipSuccess) e = dev_malloc(&s->d_nacc, sizeof(unsigned) * nchain);
+    if (e == hipSuccess) e = dev_malloc(&s->d_nswap, sizeof(unsigned) * nchain);
+    if (e == hipSuccess) e = hipMemcpy(s->d_temps, s->temps.data(), sizeof(double) * T, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(s->d_chol, chol, sizeof(double) * nchain * d * d, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(s->d_nacc, 0, sizeof(unsigned) * nchain);
+    if (e == hipSuccess) e = hipMemset(s->d_nswap, 0, sizeof(unsigned) * nchain);
+    return e;
+}
+
+void pt_ens_release(PtEnsemble* s)
+{
+    if (s->ext_state) s->d_theta = s->d_lp = nullptr;
+    for (void* p : {(void*)s->d_temps, (void*)s->d_theta, (void*)s->d_lp, (void*)s->d_chol, (void*)s->d_nacc, (void*)s->d_nswap,
+                    (void*)s->d_samples, (void*)s->d_slp, (void*)s->d_scratch})
+        if (p) (void)dev_free(p);
+}
+
+PtLaunch pt_ens_launch(const PtEnsemble* s, int d, int q, int n, long ch, int do_exchange, int thin, long save_offset)
+{
+    PtLaunch L{};
+    L.d = d;
+    L.q = q;
+    L.n = n;
+    L.T = s->T;
+    L.R = s->R;
+    L.maxiter = s->maxiter;
+    L.iter0 = s->iter;
+    L.niter = (int)ch;
+    L.do_exchange = do_exchange;
+    L.save_thin = thin;
+    L.save_offset = save_offset;
+    L.sample_cap = s->cap;
+    L.seed0 = (unsigned)(s->seed & 0xffffffffu);
+    L.seed1 = (unsigned)(s->seed >> 32);
+    L.slot0 = 0;
+    L.T_global = (unsigned)s->T;
+    L.replica0 = 0;
+    return L;
+}
+
+void pt_ens_advance(PtEnsemble* s, long ch, int thin, long* save_offset)
+{
+    s->iter += ch;
+    s->stat_iters += ch;
+    if (thin > 0 && save_offset) *save_offset += ch / thin;
+}
+
+hipError_t pt_ens_set_chains(PtEnsemble* s, int d, const double* theta, const double* lp)
+{
+    hipError_t e = hipMemcpy(s->d_theta, theta, sizeof(double) * s->nchain() * d, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(s->d_lp, lp, sizeof(double) * s->nchain(), hipMemcpyHostToDevice);
+    return e;
+}
+
+hipError_t pt_ens_get_chains(const PtEnsemble* s, int d, double* theta, double* lp)
+{
+    hipError_t e = hipSuccess;
+    if (theta) e = hipMemcpy(theta, s->d_theta, sizeof(double) * s->nchain() * d, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && lp) e = hipMemcpy(lp, s->d_lp, sizeof(double) * s->nchain(), hipMemcpyDeviceToHost);
+    return e;
+}
+
+hipError_t pt_ens_reserve_samples(PtEnsemble* s, int d, int nsamples, long* capacity)
+{
+    if (s->cap < nsamples) {
+        if (s->d_samples) (void)dev_free(s->d_samples);
+        if (s->d_slp) (void)dev_free(s->d_slp);
+        s->d_samples = s->d_slp = nullptr;
+        s->cap = 0;
+        hipError_t e = dev_malloc(&s->d_samples, sizeof(double) * (size_t)s->R * nsamples * d);
+        if (e == hipSuccess) e = dev_malloc(&s->d_slp, sizeof(double) * (size_t)s->R * nsamples);
+        if (e != hipSuccess) return e;
+        s->cap = nsamples;
+    }
+    *capacity = s->cap;
+    s->cap = nsamples;   // stride of this call's output
+    return hipSuccess;
+}
+
+hipError_t pt_ens_fetch_samples(const PtEnsemble* s, int d, int nsamples, double* samples, double* logposts)
+{
+    hipError_t e = hipMemcpy(samples, s->d_samples, sizeof(double) * (size_t)s->R * nsamples * d, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(logposts, s->d_slp, sizeof(double) * (size_t)s->R * nsamples, hipMemcpyDeviceToHost);
+    return e;
+}
+
+hipError_t pt_ens_stats(PtEnsemble* s, double* accept_rate, double* swap_rate, int reset)
+{
+    const size_t nchain = s->nchain();
+    std::vector<unsigned> a(nchain), w(nchain);
+    hipError_t e = hipMemcpy(a.data(), s->d_nacc, sizeof(unsigned) * nchain, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(w.data(), s->d_nswap, sizeof(unsigned) * nchain, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return e;
+    const double it = s->stat_iters ? (double)s->stat_iters : 1.0;
+    for (size_t k = 0; k < nchain; k++) {
+        if (accept_rate) accept_rate[k] = a[k] / it;
+        if (swap_rate) swap_rate[k] = w[k] / it;   // entry i = swaps between temperature i and i-1
+    }
+    if (reset) {
+        (void)hipMemset(s->d_nacc, 0, sizeof(unsigned) * nchain);
+        (void)hipMemset(s->d_nswap, 0, sizeof(unsigned) * nchain);
+        s->stat_iters = 0;
+    }
+    return hipSuccess;
+}
+
+hipError_t pt_ens_sync_factor(PtEnsemble* s, int d, hipStream_t st)
+{
+    if (!s->chol_stale) return hipSuccess;
+    const hipError_t e = pt_lane_store_factor(d, s->T, s->R, s->d_scratch, s->d_chol, st);
+    if (e == hipSuccess) s->chol_stale = false;
+    return e;
+}
+
+void pt_ens_factor_written(PtEnsemble* s)
+{
+    s->factor_loaded = false;
+    s->chol_stale = false;
+}
+
+hipError_t pt_ens_get_factor(PtEnsemble* s, int d, hipStream_t st, double* chol)
+{
+    hipError_t e = pt_ens_sync_factor(s, d, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipMemcpy(chol, s->d_chol, sizeof(double) * s->nchain() * d * d, hipMemcpyDeviceToHost);
+    return e;
+}
+
+hipError_t pt_ens_set_factor(PtEnsemble* s, int d, hipStream_t st, const double* chol)
+{
+    hipError_t e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipMemcpy(s->d_chol, chol, sizeof(double) * s->nchain() * d * d, hipMemcpyHostToDevice);
+    if (e == hipSuccess) pt_ens_factor_written(s);
+    return e;
+}
 
 void pt_state_free(Ctx* c)
 {
     PtState* s = c->pt;
     if (!s) return;
-    if (s->d_temps) (void)dev_free(s->d_temps);
-    if (!s->ext_state) {
-        if (s->d_theta) (void)dev_free(s->d_theta);
-        if (s->d_lp) (void)dev_free(s->d_lp);
-    }
-    if (s->d_chol) (void)dev_free(s->d_chol);
-    if (s->d_nacc) (void)dev_free(s->d_nacc);
-    if (s->d_nswap) (void)dev_free(s->d_nswap);
-    if (s->d_samples) (void)dev_free(s->d_samples);
-    if (s->d_slp) (void)dev_free(s->d_slp);
-    if (s->d_stage) (void)dev_free(s->d_stage);
-    if (s->d_abort) (void)dev_free(s->d_abort);
-    if (s->d_backup) (void)dev_free(s->d_backup);
-    if (s->d_lane_scratch) (void)dev_free(s->d_lane_scratch);
-    if (s->d_send) (void)dev_free(s->d_send);
-    if (s->d_recv) (void)dev_free(s->d_recv);
-    if (s->d_bnd_swaps) (void)dev_free(s->d_bnd_swaps);
-    if (s->d_checksum) (void)dev_free(s->d_checksum);
+    pt_ens_release(s);
+    for (void* p : {(void*)s->d_stage, (void*)s->d_abort, (void*)s->d_backup, (void*)s->d_send, (void*)s->d_recv, (void*)s->d_bnd_swaps,
+                    (void*)s->d_checksum})
+        if (p) (void)dev_free(p);
     delete s;
     c->pt = nullptr;
-}
-
-static double pop_var(const std::vector<double>& y)
-{
-    // src/carmcmc.cpp:85-88
-    double sum = 0, sq = 0;
-    for (double v : y) {
-        sum += v;
-        sq += v * v;
-    }
-    const double mean = sum / y.size();
-    return sq / y.size() - mean * mean;
-}
-
-static double sample_var(const double* y, int n)   // arma::var
-{
-    double mean = 0;
-    for (int i = 0; i < n; i++) mean += y[i];
-    mean /= (size_t)n;
-    double s = 0;
-    for (int i = 0; i < n; i++) s += (y[i] - mean) * (y[i] - mean);
-    return s / ((size_t)n - 1);
 }
 
 static int chunk_iters(const Ctx* c)
@@ -83,97 +195,14 @@ static int chunk_iters(const Ctx* c)
     return (int)std::max(1.0, std::min(4096.0, 250000.0 / est_us));
 }
 
-// One draw from the reference's starting-value distribution for the series (t, y)[n] (sorted, distinct times) with prior pr.
-void draw_start(const double* t, const double* y, int n, const Prior& pr, int p, int q, std::mt19937_64& rng, double* theta)
-{
-    std::normal_distribution<double> norm(0.0, 1.0);
-    std::uniform_real_distribution<double> unif(0.0, 1.0);
-    auto scaled_inv_chisq = [&](int dof, double ssqr) {       // src/random.cpp:180-186
-        std::chi_squared_distribution<double> chi(dof);
-        return ssqr / chi(rng) * (double)dof;
-    };
-    double ymean = 0;
-    for (int i = 0; i < n; i++) ymean += y[i];
-    ymean /= n;
-    const double yvar = scaled_inv_chisq(n - 1, sample_var(y, n));
-    const double mu = ymean + std::sqrt(yvar) / n * norm(rng);
-    double scale = scaled_inv_chisq((int)pr.measerr_dof, 1.0);
-    scale = std::max(std::min(scale, 1.99), 0.51);
-    theta[0] = std::sqrt(yvar);
-    theta[1] = scale;
-    theta[2] = mu;
-    if (p == 1) {
-        // CAR1::StartingValue (src/carpack.cpp:38-81)
-        std::vector<double> dt(n - 1);
-        for (int i = 1; i < n; i++) dt[i - 1] = t[i] - t[i - 1];
-        std::sort(dt.begin(), dt.end());
-        const double med = (dt.size() % 2) ? dt[dt.size() / 2] : 0.5 * (dt[dt.size() / 2 - 1] + dt[dt.size() / 2]);
-        double lw = -1.0 * std::log(med * (1.0 + 49.0 * unif(rng)));
-        lw = std::min(lw, pr.max_freq);     // sic (carpack.cpp:56)
-        theta[3] = lw;
-        return;
-    }
-    // CARp::StartingAR (src/carpack.cpp:268-311)
-    const double min_freq = pr.min_freq, max_freq = pr.max_freq;
-    const int nc = (p + 1) / 2;
-    std::vector<double> cent(nc), width(nc);
-    for (int i = 0; i < nc; i++) cent[i] = std::exp(std::log(max_freq / min_freq) * unif(rng) + std::log(min_freq));
-    std::sort(cent.begin(), cent.end(), std::greater<double>());
-    for (int i = 0; i < nc; i++) width[i] = std::exp(std::log(max_freq / min_freq) * unif(rng) + std::log(min_freq));
-    if (p % 2 == 1) {
-        cent[p / 2] = 0.0;
-        const double lo = std::log(min_freq), hi = std::log(cent[p / 2 - 1]);
-        width[p / 2] = std::exp(lo + (hi - lo) * unif(rng));
-    }
-    for (int i = 0; i < p / 2; i++) {
-        const double re = -2.0 * M_PI * width[i], im = 2.0 * M_PI * cent[i];
-        theta[3 + 2 * i] = std::log(re * re + im * im);
-        theta[3 + 2 * i + 1] = std::log(-2.0 * re);
-    }
-    if (p % 2 == 1) theta[3 + p - 1] = std::log(2.0 * M_PI * width[p / 2]);
-    // CARMA::StartingMA (src/carpack.cpp:515-519)
-    for (int i = 0; i < q; i++) theta[3 + p + i] = std::fabs(norm(rng));
-}
-
-// The generator of a chain's starting-value draws: keyed by (seed, the chain's GLOBAL slot, attempt)
-std::mt19937_64 start_rng(uint64_t seed, uint64_t gslot, int round)
-{
-    uint64_t z = seed * 0x9E3779B97F4A7C15ull + 0x1234567ull;
-    z ^= (gslot + 1) * 0xBF58476D1CE4E5B9ull;
-    z ^= ((uint64_t)round + 1) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return std::mt19937_64(z * 0xD6E8FEB86659FD93ull + 0x2545F4914F6CDD1Dull);
-}
-
-static PtLaunch pt_launch_args(const Ctx* c, long ch, int do_exchange, int thin, long save_offset)
-{
-    const PtState* s = c->pt;
-    PtLaunch L{};
-    L.d = c->d;
-    L.q = c->q;
-    L.n = c->n;
-    L.T = s->T;
-    L.R = s->R;
-    L.maxiter = s->maxiter;
-    L.iter0 = s->iter;
-    L.niter = (int)ch;
-    L.do_exchange = do_exchange;
-    L.save_thin = thin;
-    L.save_offset = save_offset;
-    L.sample_cap = s->cap;
-    L.seed0 = (unsigned)(s->seed & 0xffffffffu);
-    L.seed1 = (unsigned)(s->seed >> 32);
-    L.slot0 = s->slot0;
-    L.T_global = s->T_global;
-    L.replica0 = s->replica0;
-    return L;
-}
-
 // one launch of `ch` iterations on `st`
 static int pt_enqueue_one(Ctx* c, long ch, int do_exchange, int thin, long* save_offset, hipStream_t st)
 {
     PtState* s = c->pt;
-    const PtLaunch L = pt_launch_args(c, ch, do_exchange, thin, save_offset ? *save_offset : 0);
+    PtLaunch L = pt_ens_launch(s, c->d, c->q, c->n, ch, do_exchange, thin, save_offset ? *save_offset : 0);
+    L.slot0 = s->slot0;                                     // this context's block of the ladder and of the replicas (carma_pt_shard)
+    L.T_global = s->T_global;
+    L.replica0 = s->replica0;
     hipError_t e;
     if (s->use_row) {
         PtRowSync S{s->d_stage, s->d_abort, ++s->epoch, s->wpl, device_cus(), 1, c->series_flags(), 0};
@@ -185,21 +214,19 @@ static int pt_enqueue_one(Ctx* c, long ch, int do_exchange, int thin, long* save
         }
     }
     if (!s->use_row && s->use_lane) {
-        e = launch_pt_lane(c->p, L, s->d_lane_scratch, reinterpret_cast<const double4*>(c->d_series), c->pr, s->d_temps, s->d_theta,
-                           s->d_lp, s->d_chol, s->d_nacc, s->d_nswap, s->d_samples, s->d_slp, c->series_flags(), !s->lane_factor_loaded,
+        e = launch_pt_lane(c->p, L, s->d_scratch, reinterpret_cast<const double4*>(c->d_series), c->pr, s->d_temps, s->d_theta,
+                           s->d_lp, s->d_chol, s->d_nacc, s->d_nswap, s->d_samples, s->d_slp, c->series_flags(), !s->factor_loaded,
                            st);
         if (e == hipSuccess) {
-            s->lane_factor_loaded = true;                   // ... and stays in the scratch: the chain-major copy is behind until
-            s->chol_stale = true;                           // somebody asks for it (pt_sync_factor)
+            s->factor_loaded = true;                   // ... and stays in the scratch: the chain-major copy is behind until
+            s->chol_stale = true;                           // somebody asks for it (pt_ens_sync_factor)
         }
     } else if (!s->use_row) {
         e = launch_pt(c->p, L, reinterpret_cast<const double4*>(c->d_series), c->pr, s->d_temps, s->d_theta, s->d_lp,
                       s->d_chol, s->d_nacc, s->d_nswap, s->d_samples, s->d_slp, st);
     }
     if (e != hipSuccess) return hip_fail(e, "launch pt kernel");
-    s->iter += ch;
-    s->stat_iters += ch;
-    if (thin > 0 && save_offset) *save_offset += ch / thin;
+    pt_ens_advance(s, ch, thin, save_offset);
     return CARMA_OK;
 }
 
@@ -208,11 +235,7 @@ int pt_enqueue(Ctx* c, long niter, int do_exchange, int thin, long* save_offset,
     const int chunk0 = chunk_iters(c);
     long left = niter;
     while (left > 0) {
-        long ch = std::min<long>(left, chunk0);
-        if (thin > 0) {
-            ch = std::max<long>(thin, (ch / thin) * thin);   // whole thinning intervals per launch
-            ch = std::min(ch, left);
-        }
+        const long ch = pt_next_chunk(left, chunk0, thin);
         int rc = pt_enqueue_one(c, ch, do_exchange, thin, save_offset, st);
         if (rc != CARMA_OK) return rc;
         left -= ch;
@@ -232,25 +255,6 @@ int pt_check_abort(Ctx* c, bool* aborted)
     return CARMA_OK;
 }
 
-// The chain-major factors d_chol brought up to date with the lane sampler's working state (no-op for the other kernels): before
-// anything reads d_chol.  Enqueued on st.
-hipError_t pt_sync_factor(Ctx* c, hipStream_t st)
-{
-    PtState* s = c->pt;
-    if (!s || !s->use_lane || !s->chol_stale) return hipSuccess;
-    const hipError_t e = pt_lane_store_factor(c->d, s->T, s->R, s->d_lane_scratch, s->d_chol, st);
-    if (e == hipSuccess) s->chol_stale = false;
-    return e;
-}
-// ... and the other way round: d_chol was written (carma_pt_set_factor, a restored backup): the next launch reloads the factors
-void pt_factor_written(Ctx* c)
-{
-    if (c->pt) {
-        c->pt->lane_factor_loaded = false;
-        c->pt->chol_stale = false;
-    }
-}
-
 // chain state <-> backup (theta, logpost, chol), asynchronous on st
 static hipError_t pt_backup(Ctx* c, bool restore, hipStream_t st)
 {
@@ -259,10 +263,10 @@ static hipError_t pt_backup(Ctx* c, bool restore, hipStream_t st)
     double* b = s->d_backup;
     struct Part { double* p; size_t n; } parts[3] = {{s->d_theta, nchain * d}, {s->d_lp, nchain}, {s->d_chol, nchain * d * d}};
     if (!restore) {
-        const hipError_t es = pt_sync_factor(c, st);
+        const hipError_t es = pt_ens_sync_factor(s, c->d, st);
         if (es != hipSuccess) return es;
     } else {
-        pt_factor_written(c);
+        pt_ens_factor_written(s);
     }
     for (auto& pt : parts) {
         hipError_t e = restore ? hipMemcpyAsync(pt.p, b, sizeof(double) * pt.n, hipMemcpyDeviceToDevice, st)
@@ -290,11 +294,7 @@ static int pt_launch_chunks(Ctx* c, long niter, int do_exchange, int thin, long*
     const int chunk0 = chunk_iters(c);
     long left = niter;
     while (left > 0) {
-        long ch = std::min<long>(left, chunk0);
-        if (thin > 0) {
-            ch = std::max<long>(thin, (ch / thin) * thin);
-            ch = std::min(ch, left);
-        }
+        const long ch = pt_next_chunk(left, chunk0, thin);
         if (!s->use_row) return pt_launch_chunks(c, left, do_exchange, thin, save_offset);     // after a fall-back
         const unsigned long long iter_before = s->iter, stat_before = s->stat_iters;
         const long off_before = save_offset ? *save_offset : 0;
@@ -347,39 +347,18 @@ int carma_pt_create(carma_ctx* h, int ntemps, int nreplicas, const double* tempe
     pt_state_free(c);
     PtState* s = new PtState();
     c->pt = s;
-    s->T = ntemps;
-    s->R = nreplicas;
     s->T_global = ntemps;
     s->maxiter = adapt_iters;
     s->seed = seed;
-    s->temps.resize(ntemps);
-    for (int i = 0; i < ntemps; i++) {
-        // src/carmcmc.cpp:92-95: exp(linspace(0, ln 100, nwalkers))
-        if (temperatures)
-            s->temps[i] = temperatures[i];
-        else
-            s->temps[i] = (ntemps == 1) ? 1.0 : std::exp(std::log(100.0) * (double)i / (double)(ntemps - 1));
-    }
+    std::vector<double> temps;
+    default_ladder(ntemps, temperatures, temps);
     const int d = c->d;
     const size_t nchain = (size_t)ntemps * nreplicas;
-    // initial proposal covariance (src/carmcmc.cpp:132-136 / :50-54): diag(1e-4), [0,0]=2 var^2/n, [2,2]=var/n
-    const double var = pop_var(c->y);
-    std::vector<double> R0((size_t)d * d, 0.0);
-    for (int i = 0; i < d; i++) R0[(size_t)i * d + i] = 0.01;
-    R0[0] = std::sqrt(2.0 * var * var / c->n);
-    R0[(size_t)2 * d + 2] = std::sqrt(var / c->n);
+    std::vector<double> R0((size_t)d * d);
+    initial_factor(pop_var(c->y.data(), c->n), c->n, d, R0.data());
     std::vector<double> chol(nchain * d * d);
     for (size_t k = 0; k < nchain; k++) std::memcpy(&chol[k * d * d], R0.data(), sizeof(double) * d * d);
-    e = dev_malloc(&s->d_temps, sizeof(double) * ntemps);
-    if (e == hipSuccess) e = dev_malloc(&s->d_theta, sizeof(double) * nchain * d);
-    if (e == hipSuccess) e = dev_malloc(&s->d_lp, sizeof(double) * nchain);
-    if (e == hipSuccess) e = dev_malloc(&s->d_chol, sizeof(double) * nchain * d * d);
-    if (e == hipSuccess) e = dev_malloc(&s->d_nacc, sizeof(unsigned) * nchain);
-    if (e == hipSuccess) e = dev_malloc(&s->d_nswap, sizeof(unsigned) * nchain);
-    if (e == hipSuccess) e = hipMemcpy(s->d_temps, s->temps.data(), sizeof(double) * ntemps, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(s->d_chol, chol.data(), sizeof(double) * chol.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(s->d_nacc, 0, sizeof(unsigned) * nchain);
-    if (e == hipSuccess) e = hipMemset(s->d_nswap, 0, sizeof(unsigned) * nchain);
+    e = pt_ens_create(s, ntemps, nreplicas, d, temps, chol.data());
     // Kernel choice.  The row variant needs every workgroup of the grid resident at the same time
     // (its swap step is a cross-workgroup rendezvous); otherwise one workgroup per ladder (k_pt).
     // CARMA_PT_KERNEL=ladder|row overrides (row only where it is safe).
@@ -421,7 +400,7 @@ int carma_pt_create(carma_ctx* h, int ntemps, int nreplicas, const double* tempe
         const bool forced = force && std::strcmp(force, "lane") == 0;
         if (forced || (!force && pays)) {
             s->use_lane = true;
-            e = dev_malloc(&s->d_lane_scratch, sizeof(double) * pt_lane_scratch_doubles(d, (long)nchain));
+            e = dev_malloc(&s->d_scratch, sizeof(double) * pt_lane_scratch_doubles(d, (long)nchain));
         }
     }
     if (e == hipSuccess && c->p >= 2 && !s->use_lane) {
@@ -510,8 +489,7 @@ int carma_pt_set_chains(carma_ctx* h, const double* theta, const double* logpost
         int rc = logdensity_of_chain_states(h, theta, nchain, c->d, lp.data());
         if (rc != CARMA_OK) return rc;
     }
-    hipError_t e = hipMemcpy(s->d_theta, theta, sizeof(double) * nchain * c->d, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(s->d_lp, lp.data(), sizeof(double) * nchain, hipMemcpyHostToDevice);
+    hipError_t e = pt_ens_set_chains(s, c->d, theta, lp.data());
     // a new set of chains starts a new history of boundary decisions: the two sides of a boundary compare folds of the
     // decisions since this point (carma_shard.hip), so one side re-created on its own must not inherit the old sum
     if (e == hipSuccess && s->d_checksum) e = hipMemset(s->d_checksum, 0, 4 * sizeof(unsigned long long));
@@ -525,11 +503,7 @@ int carma_pt_get_chains(carma_ctx* h, double* theta, double* logpost)
 {
     if (!h || !reinterpret_cast<Ctx*>(h)->pt) return CARMA_EINVAL;
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    PtState* s = c->pt;
-    const size_t nchain = (size_t)s->T * s->R;
-    hipError_t e = hipSuccess;
-    if (theta) e = hipMemcpy(theta, s->d_theta, sizeof(double) * nchain * c->d, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && logpost) e = hipMemcpy(logpost, s->d_lp, sizeof(double) * nchain, hipMemcpyDeviceToHost);
+    const hipError_t e = pt_ens_get_chains(c->pt, c->d, theta, logpost);
     if (e != hipSuccess) return hip_fail(e, "carma_pt_get_chains");
     return CARMA_OK;
 }
@@ -564,30 +538,15 @@ int carma_pt_start(carma_ctx* h, const double* init, int ninit)
     // happens to visit its chains: a replica or a temperature gets the same starting value whichever rank holds it
     // (carma_pt_shard), so a sharded run starts -- and, the sampler's streams being keyed the same way, continues --
     // exactly as the single-process run does.
-    auto chain_rng = [&](size_t k, int round) {
-        const uint64_t gslot = ((uint64_t)s->replica0 + k / (size_t)s->T) * (uint64_t)s->T_global + s->slot0 + k % (size_t)s->T;
-        return start_rng(s->seed, gslot, round);
-    };
-    for (int round = 0; round < 4000; round++) {
-        std::vector<size_t> todo;
-        for (size_t k = 0; k < nchain; k++)
-            if (!done[k]) todo.push_back(k);
-        if (todo.empty()) break;
-        std::vector<double> cand(todo.size() * d), out(todo.size());
-        for (size_t i = 0; i < todo.size(); i++) {
-            std::mt19937_64 rng = chain_rng(todo[i], round);
-            draw_start(c->t.data(), c->y.data(), c->n, c->pr, c->p, c->q, rng, &cand[i * d]);
-        }
-        int rc = logdensity_of_chain_states(h, cand.data(), todo.size(), d, out.data());
-        if (rc != CARMA_OK) return rc;
-        for (size_t i = 0; i < todo.size(); i++) {
-            if (std::isfinite(out[i])) {
-                std::memcpy(&theta[todo[i] * d], &cand[i * d], sizeof(double) * d);
-                lp[todo[i]] = out[i];
-                done[todo[i]] = 1;
-            }
-        }
-    }
+    const int rc = find_starts(
+        nchain, d, theta.data(), lp.data(), done.data(),
+        [&](size_t k, int round, double* out) {
+            const uint64_t gslot = ((uint64_t)s->replica0 + k / (size_t)s->T) * (uint64_t)s->T_global + s->slot0 + k % (size_t)s->T;
+            std::mt19937_64 rng = start_rng(s->seed, gslot, round);
+            draw_start(c->t.data(), c->y.data(), c->n, c->pr, c->p, c->q, rng, out);
+        },
+        [&](const double* cand, const size_t*, size_t m, double* out) { return logdensity_of_chain_states(h, cand, m, d, out); });
+    if (rc != CARMA_OK) return rc;
     for (size_t k = 0; k < nchain; k++) {
         if (!done[k]) {
             set_error("carma_pt_start: no finite starting value found for chain %zu", k);
@@ -624,49 +583,24 @@ int carma_pt_sample(carma_ctx* h, int nsamples, int thin, double* samples, doubl
     }
     hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    if (s->cap < nsamples) {
-        if (s->d_samples) (void)dev_free(s->d_samples);
-        if (s->d_slp) (void)dev_free(s->d_slp);
-        s->d_samples = s->d_slp = nullptr;
-        s->cap = 0;
-        e = dev_malloc(&s->d_samples, sizeof(double) * (size_t)s->R * nsamples * c->d);
-        if (e == hipSuccess) e = dev_malloc(&s->d_slp, sizeof(double) * (size_t)s->R * nsamples);
-        if (e != hipSuccess) return hip_fail(e, "dev_malloc(samples)");
-        s->cap = nsamples;
-    }
+    long capacity = 0;
+    e = pt_ens_reserve_samples(s, c->d, nsamples, &capacity);
+    if (e != hipSuccess) return hip_fail(e, "dev_malloc(samples)");
     long off = 0;
-    const long cap_saved = s->cap;
-    s->cap = nsamples;   // stride of this call's output
     int rc = pt_launch_chunks(c, (long)nsamples * thin, 1, thin, &off);
     if (rc == CARMA_OK) {
-        e = hipMemcpy(samples, s->d_samples, sizeof(double) * (size_t)s->R * nsamples * c->d, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(logposts, s->d_slp, sizeof(double) * (size_t)s->R * nsamples, hipMemcpyDeviceToHost);
+        e = pt_ens_fetch_samples(s, c->d, nsamples, samples, logposts);
         if (e != hipSuccess) rc = hip_fail(e, "D2H samples");
     }
-    s->cap = cap_saved;
+    s->cap = capacity;
     return rc;
 }
 
 int carma_pt_stats(carma_ctx* h, double* accept_rate, double* swap_rate, int reset)
 {
     if (!h || !reinterpret_cast<Ctx*>(h)->pt) return CARMA_EINVAL;
-    Ctx* c = reinterpret_cast<Ctx*>(h);
-    PtState* s = c->pt;
-    const size_t nchain = (size_t)s->T * s->R;
-    std::vector<unsigned> a(nchain), w(nchain);
-    hipError_t e = hipMemcpy(a.data(), s->d_nacc, sizeof(unsigned) * nchain, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(w.data(), s->d_nswap, sizeof(unsigned) * nchain, hipMemcpyDeviceToHost);
+    const hipError_t e = pt_ens_stats(reinterpret_cast<Ctx*>(h)->pt, accept_rate, swap_rate, reset);
     if (e != hipSuccess) return hip_fail(e, "carma_pt_stats");
-    const double it = s->stat_iters ? (double)s->stat_iters : 1.0;
-    for (size_t k = 0; k < nchain; k++) {
-        if (accept_rate) accept_rate[k] = a[k] / it;
-        if (swap_rate) swap_rate[k] = w[k] / it;   // entry i = swaps between temperature i and i-1
-    }
-    if (reset) {
-        (void)hipMemset(s->d_nacc, 0, sizeof(unsigned) * nchain);
-        (void)hipMemset(s->d_nswap, 0, sizeof(unsigned) * nchain);
-        s->stat_iters = 0;
-    }
     return CARMA_OK;
 }
 

@@ -197,6 +197,29 @@ def test_run_does_not_depend_on_its_neighbours(cpa, sset, p, q, T, R):
         assert np.isfinite(x).all() and not np.array_equal(x[0], x[1])
 
 
+# ---- 3b. a second, smaller sampling call --------------------------------------------------------------------------------
+def test_a_second_smaller_sample_call_continues_the_first(cpa):
+    """pt_sample(8) and then pt_sample(3) on one sampler: the second call writes into the buffer the first one sized, with a stride
+    of its own.  Together they are the 11 samples one call gives from the same seed and chains, bit for bit."""
+    mc = cpa.MultiContext([irregular_series(30, seed=671), irregular_series(64, seed=672)], 2, 1)
+    runs, T, R = [0, 1], 3, 2
+    mc.pt_create(runs, T, R, 10 ** 6, seed=SEED)
+    mc.pt_start()
+    th0, lp0 = mc.pt_get_chains()
+    s8, l8 = mc.pt_sample(8, 2)
+    s3, l3 = mc.pt_sample(3, 2)
+    th1, lp1 = mc.pt_get_chains()
+    mc.pt_create(runs, T, R, 10 ** 6, seed=SEED)
+    mc.pt_set_chains(th0, lp0)
+    s11, l11 = mc.pt_sample(11, 2)
+    assert s8.shape == (2, R, 8, mc.d) and s3.shape == (2, R, 3, mc.d) and l3.shape == (2, R, 3)
+    assert np.array_equal(s8, s11[:, :, :8]) and np.array_equal(l8, l11[:, :, :8])
+    assert np.array_equal(s3, s11[:, :, 8:]) and np.array_equal(l3, l11[:, :, 8:])
+    assert np.isfinite(l11).all() and not np.array_equal(s11[:, :, 0], s11[:, :, 10])
+    th2, lp2 = mc.pt_get_chains()
+    assert np.array_equal(th1, th2) and np.array_equal(lp1, lp2)
+
+
 # ---- 4. chunking is invisible --------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("p,q,T,R", [(2, 1, 3, 5), (5, 3, 10, 2), (7, 6, 10, 2)])
 def test_iterations_do_not_depend_on_how_they_are_split(cpa, sset, p, q, T, R):

@@ -321,6 +321,37 @@ def test_lane_sampler_keeps_its_factors_between_calls(cpa, monkeypatch):
         np.testing.assert_array_equal(a, b)
 
 
+@pytest.mark.parametrize("kern", ["ladder", "lane"])
+def test_a_second_smaller_sample_call_continues_the_first(cpa, kern, monkeypatch):
+    """pt_sample(8) and then pt_sample(3) on one sampler: the second call writes into the buffer the first one sized, with a stride
+    of its own.  Together they are the 11 samples one call gives from the same seed and chains, bit for bit."""
+    from helpers import irregular_series
+    monkeypatch.setenv("CARMA_PT_KERNEL", kern)
+    t, y, yerr = irregular_series(60, seed=9)
+    ms = _pop_stdev(y)
+
+    def sampler():
+        ctx = cpa.Context(t, y, yerr, 2, 1, max_stdev=ms)
+        ctx.pt_create(3, 2, adapt_iters=10 ** 6, seed=5)
+        assert ctx.pt_kernel() == kern
+        return ctx
+
+    a, b = sampler(), sampler()
+    a.pt_start(None)
+    b.pt_set_chains(*a.pt_get_chains())
+    s8, l8 = a.pt_sample(8, thin=2)
+    s3, l3 = a.pt_sample(3, thin=2)
+    s11, l11 = b.pt_sample(11, thin=2)
+    assert s8.shape == (2, 8, a.d) and s3.shape == (2, 3, a.d) and l3.shape == (2, 3)
+    np.testing.assert_array_equal(s8, s11[:, :8])
+    np.testing.assert_array_equal(l8, l11[:, :8])
+    np.testing.assert_array_equal(s3, s11[:, 8:])
+    np.testing.assert_array_equal(l3, l11[:, 8:])
+    assert np.isfinite(l11).all() and not np.array_equal(s11[:, 0], s11[:, 10])
+    for x, z in zip(a.pt_get_chains(), b.pt_get_chains()):
+        np.testing.assert_array_equal(x, z)
+
+
 def test_lane_kernel_is_the_choice_for_large_ensembles(cpa, monkeypatch):
     """Dispatch by chain count (carma_pt_create): small ensembles keep the row / ladder kernels, tens of thousands of
     chains take one chain per lane; the stored log-posterior of every chain equals the oracle's LogDensity of its state."""
