@@ -15,7 +15,7 @@
 #include "../../include/carma_mi355.h"
 #include "carma_host.h"
 
-// ---- device allocations (carma_host.h) -------------------------------------------------------------------------
+// ---- device allocations (carma_devbuf.h) -----------------------------------------------------------------------
 #include <map>
 #include <mutex>
 namespace {
@@ -202,37 +202,6 @@ bool series_repeated_dt(const double* packed, long n)
     long rep = 0;
     for (long k = 2; k < n; k++) rep += (packed[4 * (size_t)k] == packed[4 * (size_t)(k - 1)]);
     return n > 8 && 4 * rep >= n;
-}
-
-// AR roots as the kernels expect them: complex-conjugate pairs adjacent (negative imaginary part first), real roots
-// after them -- the order CARp::ARRoots emits (src/carpack.cpp:137-172).  The result of the filter does not depend on
-// the order of the roots, so roots handed over in another order (carma_pack.py's get_ar_roots puts a real root wherever
-// its centroid is zero) are re-ordered here; a set that is not closed under conjugation is not a real-valued process
-// and is rejected.  out = p (re, im) pairs.
-int normalize_roots(int p, const double* om, double* out)
-{
-    std::vector<int> used(p, 0);
-    int k = 0;
-    for (int i = 0; i < p; i++) {
-        if (used[i] || om[2 * i + 1] == 0.0) continue;
-        const double re = om[2 * i], im = om[2 * i + 1], tol = 1e-12 * std::hypot(re, im);
-        int mate = -1;
-        for (int j = i + 1; j < p && mate < 0; j++)
-            if (!used[j] && std::fabs(om[2 * j] - re) <= tol && std::fabs(om[2 * j + 1] + im) <= tol) mate = j;
-        if (mate < 0) return CARMA_EINVAL;
-        used[i] = used[mate] = 1;
-        out[2 * k] = out[2 * k + 2] = re;
-        out[2 * k + 1] = -std::fabs(im);
-        out[2 * k + 3] = std::fabs(im);
-        k += 2;
-    }
-    for (int i = 0; i < p; i++) {
-        if (used[i]) continue;
-        out[2 * k] = om[2 * i];
-        out[2 * k + 1] = 0.0;
-        k++;
-    }
-    return CARMA_OK;
 }
 
 int select_device(int device)
@@ -488,20 +457,13 @@ namespace carma {
 struct Kf {
     int device = 0, p = 0, n = 0;
     double sigsqr = 0.0, car1_omega = 0.0;
-    double *d_series = nullptr, *d_par = nullptr, *d_io = nullptr;
-    int* d_sing = nullptr;
-    size_t io_cap = 0;
+    DevMem d_series, d_par, d_io, d_sing;                    // d_io: exactly what the largest call so far asked for
     hipStream_t stream = nullptr;
     int ensure_io(size_t nd)
     {
-        if (nd <= io_cap) return CARMA_OK;
-        if (d_io) (void)dev_free(d_io);
-        d_io = nullptr;
-        io_cap = 0;
-        hipError_t e = dev_malloc(&d_io, sizeof(double) * nd);
-        if (e != hipSuccess) return hip_fail(e, "carma_kf: hipMalloc");
-        io_cap = nd;
-        return CARMA_OK;
+        if (sizeof(double) * nd <= d_io.capacity()) return CARMA_OK;
+        const hipError_t e = d_io.alloc(sizeof(double) * nd);
+        return e == hipSuccess ? CARMA_OK : hip_fail(e, "carma_kf: hipMalloc");
     }
 };
 
@@ -509,10 +471,6 @@ static void kf_free(Kf* k)
 {
     if (!k) return;
     (void)hipSetDevice(k->device);
-    if (k->d_series) (void)dev_free(k->d_series);
-    if (k->d_par) (void)dev_free(k->d_par);
-    if (k->d_io) (void)dev_free(k->d_io);
-    if (k->d_sing) (void)dev_free(k->d_sing);
     if (k->stream) (void)hipStreamDestroy(k->stream);
     delete k;
 }
@@ -540,11 +498,10 @@ static Kf* kf_make(const double* time, const double* y, const double* yerr, int 
     std::vector<double> s = pack_series(t, yy, ee);
     std::vector<double> par(2 * CARMA_PMAX + CARMA_PMAX, 0.0);
     if (p > 1) {
-        if (normalize_roots(p, omega_re_im, par.data()) != CARMA_OK) {
+        if (pack_model_single(p, omega_re_im, ma, nma, par.data()) != CARMA_OK) {
             set_error("%s: the AR roots must be real or come in complex-conjugate pairs", who);
             return nullptr;
         }
-        for (int i = 0; i < p && i < nma; i++) par[2 * CARMA_PMAX + i] = ma[i];   // zero padded (kfilter.hpp:318-320)
     }
     Kf* k = new Kf();
     k->device = device;
@@ -552,11 +509,11 @@ static Kf* kf_make(const double* time, const double* y, const double* yerr, int 
     k->n = (int)t.size();
     k->sigsqr = sigsqr;
     k->car1_omega = car1_omega;
-    hipError_t e = dev_malloc(&k->d_series, sizeof(double) * s.size());
-    if (e == hipSuccess) e = dev_malloc(&k->d_par, sizeof(double) * par.size());
-    if (e == hipSuccess) e = dev_malloc(&k->d_sing, sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(k->d_series, s.data(), sizeof(double) * s.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(k->d_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice);
+    hipError_t e = k->d_series.alloc(sizeof(double) * s.size());
+    if (e == hipSuccess) e = k->d_par.alloc(sizeof(double) * par.size());
+    if (e == hipSuccess) e = k->d_sing.alloc(sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(k->d_series.as<void>(), s.data(), sizeof(double) * s.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(k->d_par.as<void>(), par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&k->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         rc = hip_fail(e, who);
@@ -576,19 +533,21 @@ static int kf_filter(Kf* k, double* mean, double* var)
     const int m = k->n;
     int rc = k->ensure_io(2 * (size_t)m);
     if (rc != CARMA_OK) return rc;
-    e = hipMemsetAsync(k->d_sing, 0, sizeof(int), k->stream);
+    double* d_io = k->d_io.as<double>();
+    const double* d_par = k->d_par.as<double>();
+    int* d_sing = k->d_sing.as<int>();
+    e = hipMemsetAsync(d_sing, 0, sizeof(int), k->stream);
     if (e == hipSuccess) {
         if (k->p == 1)
-            e = launch_kfilter_car1(k->sigsqr, k->car1_omega, reinterpret_cast<const double4*>(k->d_series), m, k->d_io, k->d_io + m,
-                                    k->stream);
+            e = launch_kfilter_car1(k->sigsqr, k->car1_omega, k->d_series.as<const double4>(), m, d_io, d_io + m, k->stream);
         else
-            e = launch_kfilter_carma(k->p, k->d_par, k->d_par + 2 * CARMA_PMAX, k->sigsqr,
-                                     reinterpret_cast<const double4*>(k->d_series), m, k->d_io, k->d_io + m, k->d_sing, k->stream);
+            e = launch_kfilter_carma(k->p, d_par, d_par + 2 * CARMA_PMAX, k->sigsqr, k->d_series.as<const double4>(), m, d_io,
+                                     d_io + m, d_sing, k->stream);
     }
     int sing = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(mean, k->d_io, sizeof(double) * m, hipMemcpyDeviceToHost, k->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(var, k->d_io + m, sizeof(double) * m, hipMemcpyDeviceToHost, k->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&sing, k->d_sing, sizeof(int), hipMemcpyDeviceToHost, k->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(mean, d_io, sizeof(double) * m, hipMemcpyDeviceToHost, k->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(var, d_io + m, sizeof(double) * m, hipMemcpyDeviceToHost, k->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&sing, d_sing, sizeof(int), hipMemcpyDeviceToHost, k->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(k->stream);
     if (e != hipSuccess) {
         // copies enqueued before the failure may still be writing into the caller's buffers (and into `sing` on this
@@ -611,22 +570,23 @@ static int kf_predict(Kf* k, const double* tpred, int M, double* pmean, double* 
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     int rc = k->ensure_io(3 * (size_t)M);
     if (rc != CARMA_OK) return rc;
-    double* d_io = k->d_io;
+    double* d_io = k->d_io.as<double>();
+    const double* d_par = k->d_par.as<double>();
+    int* d_sing = k->d_sing.as<int>();
     e = hipMemcpyAsync(d_io, tpred, sizeof(double) * M, hipMemcpyHostToDevice, k->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(k->d_sing, 0, sizeof(int), k->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_sing, 0, sizeof(int), k->stream);
     if (e == hipSuccess) {
         if (k->p == 1)
-            e = launch_predict_car1(k->sigsqr, k->car1_omega, reinterpret_cast<const double4*>(k->d_series), k->n, d_io, M, d_io + M,
+            e = launch_predict_car1(k->sigsqr, k->car1_omega, k->d_series.as<const double4>(), k->n, d_io, M, d_io + M,
                                     d_io + 2 * (size_t)M, k->stream);
         else
-            e = launch_predict_carma(k->p, k->d_par, k->d_par + 2 * CARMA_PMAX, k->sigsqr,
-                                     reinterpret_cast<const double4*>(k->d_series), k->n, d_io, M, d_io + M, d_io + 2 * (size_t)M,
-                                     k->d_sing, k->stream);
+            e = launch_predict_carma(k->p, d_par, d_par + 2 * CARMA_PMAX, k->sigsqr, k->d_series.as<const double4>(), k->n, d_io, M,
+                                     d_io + M, d_io + 2 * (size_t)M, d_sing, k->stream);
     }
     int sing = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(pmean, d_io + M, sizeof(double) * M, hipMemcpyDeviceToHost, k->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(pvar, d_io + 2 * (size_t)M, sizeof(double) * M, hipMemcpyDeviceToHost, k->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&sing, k->d_sing, sizeof(int), hipMemcpyDeviceToHost, k->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&sing, d_sing, sizeof(int), hipMemcpyDeviceToHost, k->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(k->stream);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(k->stream);               // see kf_filter
@@ -689,6 +649,7 @@ int carma_kfilter_batch_carma(const double* time, const double* y, const double*
     }
     int rc = select_device(device);
     if (rc != CARMA_OK) return rc;
+    DevMem b_s, b_par, b_mv, b_mean, b_var, b_sing;
     std::vector<double> t(time, time + n), yy(y, y + n), ee(yerr, yerr + n);
     sort_dedup(t, yy, ee);
     const int m = (int)t.size();
@@ -697,24 +658,22 @@ int carma_kfilter_batch_carma(const double* time, const double* y, const double*
     const int PW = 3 * p + 2;
     std::vector<double> par((size_t)nmodels * PW, 0.0);
     for (int b = 0; b < nmodels; b++) {
-        double* pb = par.data() + (size_t)b * PW;
-        if (normalize_roots(p, omega_re_im + (size_t)b * 2 * p, pb) != CARMA_OK) {
+        if (pack_model_row(p, omega_re_im + (size_t)b * 2 * p, ma + (size_t)b * nma, nma, sigsqr[b], mu ? mu[b] : 0.0,
+                           par.data() + (size_t)b * PW) != CARMA_OK) {
             set_error("carma_kfilter_batch_carma: model %d: the AR roots must be real or come in complex-conjugate pairs", b);
             return CARMA_EINVAL;
         }
-        for (int i = 0; i < nma; i++) pb[2 * p + i] = ma[(size_t)b * nma + i];     // zero padded to p (kfilter.hpp:318-320)
-        pb[3 * p] = sigsqr[b];
-        pb[3 * p + 1] = mu ? mu[b] : 0.0;
     }
-    double *d_s = nullptr, *d_par = nullptr, *d_mv = nullptr, *d_mean = nullptr, *d_var = nullptr;
-    int* d_sing = nullptr;
     const size_t nmv = (size_t)2 * m * ((size_t)nmodels + 64), nout = (size_t)nmodels * m;
-    hipError_t e = dev_malloc(&d_s, sizeof(double) * s.size());
-    if (e == hipSuccess) e = dev_malloc(&d_par, sizeof(double) * par.size());
-    if (e == hipSuccess) e = dev_malloc(&d_mv, sizeof(double) * nmv);
-    if (e == hipSuccess) e = dev_malloc(&d_mean, sizeof(double) * nout);
-    if (e == hipSuccess) e = dev_malloc(&d_var, sizeof(double) * nout);
-    if (e == hipSuccess) e = dev_malloc(&d_sing, sizeof(int) * nmodels);
+    hipError_t e = b_s.alloc(sizeof(double) * s.size());
+    if (e == hipSuccess) e = b_par.alloc(sizeof(double) * par.size());
+    if (e == hipSuccess) e = b_mv.alloc(sizeof(double) * nmv);
+    if (e == hipSuccess) e = b_mean.alloc(sizeof(double) * nout);
+    if (e == hipSuccess) e = b_var.alloc(sizeof(double) * nout);
+    if (e == hipSuccess) e = b_sing.alloc(sizeof(int) * nmodels);
+    double *d_s = b_s.as<double>(), *d_par = b_par.as<double>(), *d_mv = b_mv.as<double>(), *d_mean = b_mean.as<double>(),
+           *d_var = b_var.as<double>();
+    int* d_sing = b_sing.as<int>();
     if (e == hipSuccess) e = hipMemcpy(d_s, s.data(), sizeof(double) * s.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess)
@@ -722,8 +681,6 @@ int carma_kfilter_batch_carma(const double* time, const double* y, const double*
     if (e == hipSuccess) e = hipMemcpy(mean, d_mean, sizeof(double) * nout, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(var, d_var, sizeof(double) * nout, hipMemcpyDeviceToHost);
     if (e == hipSuccess && singular) e = hipMemcpy(singular, d_sing, sizeof(int) * nmodels, hipMemcpyDeviceToHost);
-    for (void* q : {(void*)d_s, (void*)d_par, (void*)d_mv, (void*)d_mean, (void*)d_var, (void*)d_sing})
-        if (q) (void)dev_free(q);
     if (e != hipSuccess) return hip_fail(e, "carma_kfilter_batch_carma");
     return CARMA_OK;
 }
@@ -777,23 +734,21 @@ static int simulate_common(const double* time, int n, int p, double sigsqr, cons
     if (npaths == 0) return CARMA_OK;
     int rc = select_device(device);
     if (rc != CARMA_OK) return rc;
+    DevMem b_t, b_par, b_out, b_sing;
     std::vector<double> t(time, time + n);
     std::sort(t.begin(), t.end());                            // time.sort() (carma_pack.py:1176)
     std::vector<double> par(2 * CARMA_PMAX + CARMA_PMAX, 0.0);
-    if (p > 1) {
-        if (normalize_roots(p, omega_re_im, par.data()) != CARMA_OK) {
-            set_error("carma_simulate_carma: the AR roots must be real or come in complex-conjugate pairs");
-            return CARMA_EINVAL;
-        }
-        for (int i = 0; i < p && i < nma; i++) par[2 * CARMA_PMAX + i] = ma[i];
+    if (p > 1 && pack_model_single(p, omega_re_im, ma, nma, par.data()) != CARMA_OK) {
+        set_error("carma_simulate_carma: the AR roots must be real or come in complex-conjugate pairs");
+        return CARMA_EINVAL;
     }
-    double *d_t = nullptr, *d_par = nullptr, *d_out = nullptr;
-    int* d_sing = nullptr;
     const size_t nout = (size_t)npaths * n;
-    hipError_t e = dev_malloc(&d_t, sizeof(double) * n);
-    if (e == hipSuccess) e = dev_malloc(&d_par, sizeof(double) * par.size());
-    if (e == hipSuccess) e = dev_malloc(&d_out, sizeof(double) * nout);
-    if (e == hipSuccess) e = dev_malloc(&d_sing, sizeof(int));
+    hipError_t e = b_t.alloc(sizeof(double) * n);
+    if (e == hipSuccess) e = b_par.alloc(sizeof(double) * par.size());
+    if (e == hipSuccess) e = b_out.alloc(sizeof(double) * nout);
+    if (e == hipSuccess) e = b_sing.alloc(sizeof(int));
+    double *d_t = b_t.as<double>(), *d_par = b_par.as<double>(), *d_out = b_out.as<double>();
+    int* d_sing = b_sing.as<int>();
     if (e == hipSuccess) e = hipMemcpy(d_t, t.data(), sizeof(double) * n, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(d_sing, 0, sizeof(int));
@@ -807,10 +762,6 @@ static int simulate_common(const double* time, int n, int p, double sigsqr, cons
     int sing = 0;
     if (e == hipSuccess) e = hipMemcpy(out, d_out, sizeof(double) * nout, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(&sing, d_sing, sizeof(int), hipMemcpyDeviceToHost);
-    if (d_t) (void)dev_free(d_t);
-    if (d_par) (void)dev_free(d_par);
-    if (d_out) (void)dev_free(d_out);
-    if (d_sing) (void)dev_free(d_sing);
     if (e != hipSuccess) return hip_fail(e, "carma_simulate");
     return sing ? 1 : CARMA_OK;
 }

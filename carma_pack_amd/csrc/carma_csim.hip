@@ -239,6 +239,7 @@ static int csim_run(const char* who, const double* time, const double* y, const 
             return CARMA_EINVAL;
         }
     }
+    DevMem b_s, b_e, b_grid, b_tsim, b_pos, b_par, b_sing, b_unc, b_res, b_noise, b_out;
     std::vector<double> t(time, time + n), yy(y, y + n), ee(yerr, yerr + n);
     sort_dedup(t, yy, ee);
     const int m = (int)t.size();
@@ -273,20 +274,21 @@ static int csim_run(const char* who, const double* time, const double* y, const 
     const int pw = (int)(par.size() / (size_t)npaths);
     const size_t per_path = (size_t)32 * m + (size_t)8 * ng + (noise ? (size_t)8 * m : 0);
     const int chunk = csim_chunk_paths(per_path, npaths);
-    double *d_s = nullptr, *d_e = nullptr, *d_grid = nullptr, *d_tsim = nullptr, *d_par = nullptr, *d_unc = nullptr,
-           *d_res = nullptr, *d_noise = nullptr, *d_out = nullptr;
-    int *d_pos = nullptr, *d_sing = nullptr;
-    hipError_t e = dev_malloc(&d_s, sizeof(double) * s.size());
-    if (e == hipSuccess) e = dev_malloc(&d_e, sizeof(double) * m);
-    if (e == hipSuccess) e = dev_malloc(&d_grid, sizeof(double) * ng);
-    if (e == hipSuccess) e = dev_malloc(&d_tsim, sizeof(double) * M);
-    if (e == hipSuccess) e = dev_malloc(&d_pos, sizeof(int) * ng);
-    if (e == hipSuccess) e = dev_malloc(&d_par, sizeof(double) * par.size());
-    if (e == hipSuccess) e = dev_malloc(&d_sing, sizeof(int) * npaths);
-    if (e == hipSuccess) e = dev_malloc(&d_unc, sizeof(double) * (size_t)chunk * ng);
-    if (e == hipSuccess) e = dev_malloc(&d_res, sizeof(double) * 4 * (size_t)chunk * m);
-    if (e == hipSuccess && noise) e = dev_malloc(&d_noise, sizeof(double) * (size_t)chunk * m);
-    if (e == hipSuccess) e = dev_malloc(&d_out, sizeof(double) * (size_t)chunk * M);
+    hipError_t e = b_s.alloc(sizeof(double) * s.size());
+    if (e == hipSuccess) e = b_e.alloc(sizeof(double) * m);
+    if (e == hipSuccess) e = b_grid.alloc(sizeof(double) * ng);
+    if (e == hipSuccess) e = b_tsim.alloc(sizeof(double) * M);
+    if (e == hipSuccess) e = b_pos.alloc(sizeof(int) * ng);
+    if (e == hipSuccess) e = b_par.alloc(sizeof(double) * par.size());
+    if (e == hipSuccess) e = b_sing.alloc(sizeof(int) * npaths);
+    if (e == hipSuccess) e = b_unc.alloc(sizeof(double) * (size_t)chunk * ng);
+    if (e == hipSuccess) e = b_res.alloc(sizeof(double) * 4 * (size_t)chunk * m);
+    if (e == hipSuccess && noise) e = b_noise.alloc(sizeof(double) * (size_t)chunk * m);
+    if (e == hipSuccess) e = b_out.alloc(sizeof(double) * (size_t)chunk * M);
+    double *d_s = b_s.as<double>(), *d_e = b_e.as<double>(), *d_grid = b_grid.as<double>(), *d_tsim = b_tsim.as<double>(),
+           *d_par = b_par.as<double>(), *d_unc = b_unc.as<double>(), *d_res = b_res.as<double>(), *d_noise = b_noise.as<double>(),
+           *d_out = b_out.as<double>();
+    int *d_pos = b_pos.as<int>(), *d_sing = b_sing.as<int>();
     if (e == hipSuccess) e = hipMemcpy(d_s, s.data(), sizeof(double) * s.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_e, ee.data(), sizeof(double) * m, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_grid, grid.data(), sizeof(double) * ng, hipMemcpyHostToDevice);
@@ -325,9 +327,6 @@ static int csim_run(const char* who, const double* time, const double* y, const 
     }
     std::vector<int> sing(npaths, 0);
     if (e == hipSuccess && p > 1) e = hipMemcpy(sing.data(), d_sing, sizeof(int) * npaths, hipMemcpyDeviceToHost);
-    for (void* q : {(void*)d_s, (void*)d_e, (void*)d_grid, (void*)d_tsim, (void*)d_pos, (void*)d_par, (void*)d_sing, (void*)d_unc,
-                    (void*)d_res, (void*)d_noise, (void*)d_out})
-        if (q) (void)dev_free(q);
     if (e != hipSuccess) return hip_fail(e, who);
     bool any = false;
     for (int k = 0; k < npaths; k++) {
@@ -364,18 +363,15 @@ int carma_simulate_cond_carma(const double* time, const double* y, const double*
     const int pw = 3 * p + 2;
     std::vector<double> par((size_t)npaths * pw, 0.0);
     for (int k = 0; k < npaths; k++) {
-        double* pk = par.data() + (size_t)k * pw;
         if (!(sigsqr[k] > 0.0)) {
             set_error("%s: path %d: need sigsqr > 0", who, k);
             return CARMA_EINVAL;
         }
-        if (normalize_roots(p, omega_re_im + (size_t)k * 2 * p, pk) != CARMA_OK) {
+        if (pack_model_row(p, omega_re_im + (size_t)k * 2 * p, ma + (size_t)k * nma, nma, sigsqr[k], mu ? mu[k] : 0.0,
+                           par.data() + (size_t)k * pw) != CARMA_OK) {
             set_error("%s: path %d: the AR roots must be real or come in complex-conjugate pairs", who, k);
             return CARMA_EINVAL;
         }
-        for (int i = 0; i < nma; i++) pk[2 * p + i] = ma[(size_t)k * nma + i];       // zero padded to p (kfilter.hpp:318-320)
-        pk[3 * p] = sigsqr[k];
-        pk[3 * p + 1] = mu ? mu[k] : 0.0;
     }
     return csim_run(who, time, y, yerr, n, p, npaths, par, tsim, M, seed, path0, out, uncond, noise, singular, n_out, device);
 }

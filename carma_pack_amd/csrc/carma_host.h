@@ -1,28 +1,17 @@
-// carma_host.h -- host-side state behind the C ABI (carma_capi.hip, carma_pt_host.hip): device allocation, the single-series
-// context Ctx, and the state the two parallel-tempering samplers share (PtEnsemble and its pt_ens_* functions; the host-only
-// decisions of the samplers -- ladder, initial factor, chunking, starting values -- are in carma_pt_sched.h)
+// carma_host.h -- host-side state behind the C ABI (carma_capi.hip, carma_pt_host.hip): device allocation (carma_devbuf.h), the
+// model rows the kernels read (carma_model_pack.h), the single-series context Ctx, and the state the two parallel-tempering
+// samplers share (PtEnsemble and its pt_ens_* functions; the host-only decisions of the samplers -- ladder, initial factor,
+// chunking, starting values -- are in carma_pt_sched.h)
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <vector>
 
+#include "carma_devbuf.h"
 #include "carma_launch.h"
+#include "carma_model_pack.h"
 #include "carma_types.h"
-
-// Device allocations of the library go through these two.  CARMA_DEBUG_GUARD=1 (read once; a test switch, off by default)
-// gives every allocation a virtual-memory mapping of its own whose END is the end of the buffer, with unmapped address space
-// behind it: a kernel that reads or writes past a buffer faults instead of getting away with it (round 4: a read of two
-// doubles past the parameter batch had lived in the lane-group kernels for two rounds, caught only when a batch happened to
-// end on a page boundary).  tests/test_gpu_parity.py runs a cross-section of the entry points in that mode.
-hipError_t carma_dev_malloc(void** p, size_t n);
-hipError_t carma_dev_free(void* p);
-template <class T>
-static inline hipError_t dev_malloc(T** p, size_t n)          // (typed front end: dev_malloc(&d_x, bytes))
-{
-    return carma_dev_malloc(reinterpret_cast<void**>(p), n);
-}
-static inline hipError_t dev_free(void* p) { return carma_dev_free(p); }
 
 namespace carma {
 
@@ -97,8 +86,6 @@ void sort_dedup(std::vector<double>& t, std::vector<double>& y, std::vector<doub
 std::vector<double> pack_series(const std::vector<double>& t, const std::vector<double>& y, const std::vector<double>& e);
 void set_prior_bounds(Prior& pr, const double* t, long n, double max_stdev);
 bool series_repeated_dt(const double* packed, long n);
-// AR roots in the order the KalmanFilterp-type kernels expect (carma_normalize_roots); CARMA_EINVAL unless closed under conjugation
-int normalize_roots(int p, const double* om, double* out);
 int hip_fail(hipError_t e, const char* what);
 int select_device(int device);
 void pt_state_free(Ctx* c);

@@ -116,15 +116,6 @@ __global__ __launch_bounds__(MPSD_T) void k_mpsd_fused(int nar, int nma, const d
     }
 }
 
-struct DevBuf {                                               // frees what it holds
-    void* p = nullptr;
-    ~DevBuf()
-    {
-        if (p) (void)dev_free(p);
-    }
-    hipError_t alloc(size_t bytes) { return dev_malloc(&p, bytes ? bytes : 8); }
-};
-
 static inline size_t round16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 }  // namespace carma
@@ -224,18 +215,18 @@ int carma_mpsd_band(int nar, int nma, const double* ar_coefs, const double* ma_c
     }
     // LDS of the launch: room for a whole frequency tile of the widest row, at most the fused limit
     cap = std::min(MPSD_FUSED_MAX, cap * MPSD_FT);
-    DevBuf d_in, d_band, d_grid;
+    DevMem d_in, d_band, d_grid;
     const size_t nband = (size_t)nseries * nf * nperc;
     hipError_t e = d_in.alloc(bytes);
     if (e == hipSuccess) e = d_band.alloc(sizeof(double) * nband);
     if (e == hipSuccess && !big.empty()) e = d_grid.alloc(sizeof(double) * (size_t)grid_vals);
-    if (e == hipSuccess) e = hipMemcpy(d_in.p, host.data(), bytes, hipMemcpyHostToDevice);
-    const unsigned char* base = static_cast<const unsigned char*>(d_in.p);
+    if (e == hipSuccess) e = hipMemcpy(d_in.as<void>(), host.data(), bytes, hipMemcpyHostToDevice);
+    const unsigned char* base = d_in.as<const unsigned char>();
     const double* g_ar = reinterpret_cast<const double*>(base + o_ar);
     const double* g_ma = reinterpret_cast<const double*>(base + o_ma);
     const double* g_sg = reinterpret_cast<const double*>(base + o_sg);
     const double* g_fr = reinterpret_cast<const double*>(base + o_fr);
-    double* g_band = static_cast<double*>(d_band.p);
+    double* g_band = d_band.as<double>();
     if (e == hipSuccess && nfused > 0) {
         const int ntiles = (nf + MPSD_FT - 1) / MPSD_FT;
         hipLaunchKernelGGL(k_mpsd_fused, dim3((unsigned)((long)nfused * ntiles)), dim3(MPSD_T), sizeof(unsigned long long) * cap,
@@ -248,7 +239,7 @@ int carma_mpsd_band(int nar, int nma, const double* ar_coefs, const double* ma_c
         const long st = sample_start[s], ns = sample_start[s + 1] - st;
         e = post_grid_band(nar, nma, g_ar + st * nar, g_ma + st * nma, g_sg + st, (int)ns, g_fr + (size_t)s * nf, nf, nperc,
                            reinterpret_cast<const int*>(base + o_rk) + k * POST_NQ,
-                           reinterpret_cast<const double*>(base + o_gm) + k * (POST_NQ / 2), static_cast<double*>(d_grid.p),
+                           reinterpret_cast<const double*>(base + o_gm) + k * (POST_NQ / 2), d_grid.as<double>(),
                            post_grid_chunk(nf, ns), g_band + (size_t)s * nf * nperc);
     }
     if (e == hipSuccess) e = hipMemcpy(band, g_band, sizeof(double) * nband, hipMemcpyDeviceToHost);

@@ -287,31 +287,6 @@ __global__ __launch_bounds__(64) void k_mpredict_car1(const double* __restrict__
     predict_car1(pm[0], pm[1], records + off[s], nser[s], tpred[e], pmean + e, pvar + e, pm[2]);
 }
 
-// A device buffer of the context that grows on demand
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t bytes)
-    {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)dev_free(p);
-        p = nullptr;
-        cap = 0;
-        const size_t nb = std::max(bytes + bytes / 4, (size_t)4096);
-        const hipError_t e = carma_dev_malloc(&p, nb);
-        if (e == hipSuccess) cap = nb;
-        return e;
-    }
-    void release()
-    {
-        if (p) (void)dev_free(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <class T>
-    T* as() const { return static_cast<T*>(p); }
-};
-
 // Sampler state of a multi-series context (carma_mpt_*): M runs of `reps` ladders of T chains = one ensemble of R = M reps ladders
 struct MptState : PtEnsemble {
     int M = 0, reps = 0;              // runs, replicas per run
@@ -333,38 +308,34 @@ struct Mctx {
     std::vector<int> n;               // [S]
     std::vector<Prior> pr;            // [S]
     std::vector<char> repdt;          // [S] SERIES_REPEATED_DT of each series
-    double4* d_rec = nullptr;
-    long* d_off = nullptr;
-    int* d_n = nullptr;
-    Prior* d_pr = nullptr;
+    DevMem d_rec, d_off, d_n, d_pr;   // records of all series; [S] each: off, n, pr
+    const double4* rec() const { return d_rec.as<const double4>(); }
+    const long* offs() const { return d_off.as<const long>(); }
+    const int* ns() const { return d_n.as<const int>(); }
+    const Prior* prs() const { return d_pr.as<const Prior>(); }
     // per-call buffers, grown on demand: parameter vectors [cap_B][d], results [cap_B], plan [cap_W] + [cap_W][64]
-    double *d_theta = nullptr, *d_out = nullptr;
-    int *d_wser = nullptr, *d_eidx = nullptr;
+    DevMem d_theta, d_out, d_wser, d_eidx;
     char* h_stage = nullptr;          // pinned: the same four, in this order
     long cap_B = 0, cap_W = 0;
     hipStream_t stream = nullptr;
     std::vector<int> cnt, first, order, wser_tmp;
-    // carma_mkfilter / carma_mpredict: parameters and times (doubles), plan tables (ints, longs), tiles, results, flags
-    DevBuf k_par, k_int, k_long, k_tile, k_res, k_sing;
+    // carma_mkfilter / carma_mpredict: parameters and times (doubles), plan tables (ints, longs), tiles, results, flags; grown by
+    // DevMem::need
+    DevMem k_par, k_int, k_long, k_tile, k_res, k_sing;
 
     size_t stage_bytes(long B, long W) const { return sizeof(double) * (size_t)B * (d + 1) + sizeof(int) * (size_t)W * 65; }
     int ensure(long B, long W)
     {
         if (B <= cap_B && W <= cap_W) return CARMA_OK;
         const long nB = std::max(std::max(B, cap_B), 1024L), nW = std::max(std::max(W, cap_W), 64L);
-        if (d_theta) (void)dev_free(d_theta);
-        if (d_out) (void)dev_free(d_out);
-        if (d_wser) (void)dev_free(d_wser);
-        if (d_eidx) (void)dev_free(d_eidx);
+        for (DevMem* b : {&d_theta, &d_out, &d_wser, &d_eidx}) b->release();
         if (h_stage) (void)hipHostFree(h_stage);
-        d_theta = d_out = nullptr;
-        d_wser = d_eidx = nullptr;
         h_stage = nullptr;
         cap_B = cap_W = 0;
-        hipError_t e = dev_malloc(&d_theta, sizeof(double) * (size_t)nB * d);
-        if (e == hipSuccess) e = dev_malloc(&d_out, sizeof(double) * (size_t)nB);
-        if (e == hipSuccess) e = dev_malloc(&d_wser, sizeof(int) * (size_t)nW);
-        if (e == hipSuccess) e = dev_malloc(&d_eidx, sizeof(int) * (size_t)nW * 64);
+        hipError_t e = d_theta.alloc(sizeof(double) * (size_t)nB * d);
+        if (e == hipSuccess) e = d_out.alloc(sizeof(double) * (size_t)nB);
+        if (e == hipSuccess) e = d_wser.alloc(sizeof(int) * (size_t)nW);
+        if (e == hipSuccess) e = d_eidx.alloc(sizeof(int) * (size_t)nW * 64);
         if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h_stage), stage_bytes(nB, nW), hipHostMallocDefault);
         if (e != hipSuccess) return hip_fail(e, "carma_mlogdensity_batch: buffers");
         cap_B = nB;
@@ -390,8 +361,8 @@ static int pack_items(const Mctx* c, const char* who, const int* series, int M, 
             set_error("%s: item %d: series index %d out of range (nseries = %d)", who, i, series[i], c->S);
             return CARMA_EINVAL;
         }
-        double* pb = par.data() + (size_t)i * PW;
         if (p == 1) {
+            double* pb = par.data() + (size_t)i * PW;
             if (om[2 * (size_t)i + 1] != 0.0) {
                 set_error("%s: item %d: the root of a CAR(1) model must be real", who, i);
                 return CARMA_EINVAL;
@@ -401,22 +372,20 @@ static int pack_items(const Mctx* c, const char* who, const int* series, int M, 
             pb[2] = mu ? mu[i] : 0.0;
             continue;
         }
-        if (normalize_roots(p, om + (size_t)i * 2 * p, pb) != CARMA_OK) {
+        if (pack_model_row(p, om + (size_t)i * 2 * p, ma + (size_t)i * nma, nma, sigsqr[i], mu ? mu[i] : 0.0,
+                           par.data() + (size_t)i * PW) != CARMA_OK) {
             set_error("%s: item %d: the AR roots must be real or come in complex-conjugate pairs", who, i);
             return CARMA_EINVAL;
         }
-        for (int k = 0; k < nma; k++) pb[2 * p + k] = ma[(size_t)i * nma + k];       // zero padded to p (kfilter.hpp:318-320)
-        pb[3 * p] = sigsqr[i];
-        pb[3 * p + 1] = mu ? mu[i] : 0.0;
     }
     return CARMA_OK;
 }
 
 template <class T>
-static hipError_t upload(DevBuf& b, const std::vector<T>& v, hipStream_t st)
+static hipError_t upload(DevMem& b, const std::vector<T>& v, hipStream_t st)
 {
     hipError_t e = b.need(sizeof(T) * v.size());
-    if (e == hipSuccess) e = hipMemcpyAsync(b.p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.as<void>(), v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, st);
     return e;
 }
 
@@ -427,7 +396,8 @@ static hipError_t launch_logdens_chains_ms(const Mctx* c, const MptState* s, con
     (void)hipGetLastError();   // HIP's last-error is sticky: drop anything left by earlier calls
     const dim3 grid((unsigned)((nc + 63) / 64)), block(64);
     if (c->p == 1) {
-        hipLaunchKernelGGL(k_logdens_car1_chains_ms, grid, block, 0, st, thn, nc, s->T, c->d_rec, c->d_off, c->d_n, c->d_pr, s->d_lser, ll);
+        hipLaunchKernelGGL(k_logdens_car1_chains_ms, grid, block, 0, st, thn, nc, s->T, c->rec(), c->offs(), c->ns(), c->prs(),
+                           s->d_lser, ll);
         return hipGetLastError();
     }
     for (int rep = 0; rep < 2; rep++) {
@@ -436,11 +406,11 @@ static hipError_t launch_logdens_chains_ms(const Mctx* c, const MptState* s, con
 #define CARMA_MCH(N)                                                                                                              \
     case N:                                                                                                                       \
         if (rep)                                                                                                                  \
-            hipLaunchKernelGGL((k_logdens_carma_chains_ms<N, true>), grid, block, 0, st, thn, c->d, c->q, nc, s->T, c->d_rec,      \
-                               c->d_off, c->d_n, c->d_pr, s->d_rep, s->d_lser, ll);                                               \
+            hipLaunchKernelGGL((k_logdens_carma_chains_ms<N, true>), grid, block, 0, st, thn, c->d, c->q, nc, s->T, c->rec(),     \
+                               c->offs(), c->ns(), c->prs(), s->d_rep, s->d_lser, ll);                                            \
         else                                                                                                                      \
-            hipLaunchKernelGGL((k_logdens_carma_chains_ms<N, false>), grid, block, 0, st, thn, c->d, c->q, nc, s->T, c->d_rec,     \
-                               c->d_off, c->d_n, c->d_pr, s->d_rep, s->d_lser, ll);                                               \
+            hipLaunchKernelGGL((k_logdens_carma_chains_ms<N, false>), grid, block, 0, st, thn, c->d, c->q, nc, s->T, c->rec(),    \
+                               c->offs(), c->ns(), c->prs(), s->d_rep, s->d_lser, ll);                                            \
         break;
             CARMA_MCH(2) CARMA_MCH(3) CARMA_MCH(4) CARMA_MCH(5) CARMA_MCH(6) CARMA_MCH(7)
 #undef CARMA_MCH
@@ -604,14 +574,14 @@ carma_mctx* carma_mctx_create(const double* time, const double* y, const double*
         std::memcpy(&rec[(size_t)c->off[s] * 4], packed[s].data(), sizeof(double) * 4 * nr);
         std::vector<double>().swap(packed[s]);
     }
-    hipError_t e = dev_malloc(&c->d_rec, sizeof(double) * rec.size());
-    if (e == hipSuccess) e = hipMemcpy(c->d_rec, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = dev_malloc(&c->d_off, sizeof(long) * nseries);
-    if (e == hipSuccess) e = hipMemcpy(c->d_off, c->off.data(), sizeof(long) * nseries, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = dev_malloc(&c->d_n, sizeof(int) * nseries);
-    if (e == hipSuccess) e = hipMemcpy(c->d_n, c->n.data(), sizeof(int) * nseries, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = dev_malloc(&c->d_pr, sizeof(Prior) * nseries);
-    if (e == hipSuccess) e = hipMemcpy(c->d_pr, c->pr.data(), sizeof(Prior) * nseries, hipMemcpyHostToDevice);
+    hipError_t e = c->d_rec.alloc(sizeof(double) * rec.size());
+    if (e == hipSuccess) e = hipMemcpy(c->d_rec.as<void>(), rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = c->d_off.alloc(sizeof(long) * nseries);
+    if (e == hipSuccess) e = hipMemcpy(c->d_off.as<void>(), c->off.data(), sizeof(long) * nseries, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = c->d_n.alloc(sizeof(int) * nseries);
+    if (e == hipSuccess) e = hipMemcpy(c->d_n.as<void>(), c->n.data(), sizeof(int) * nseries, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = c->d_pr.alloc(sizeof(Prior) * nseries);
+    if (e == hipSuccess) e = hipMemcpy(c->d_pr.as<void>(), c->pr.data(), sizeof(Prior) * nseries, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         hip_fail(e, "carma_mctx_create");
@@ -626,19 +596,10 @@ void carma_mctx_destroy(carma_mctx* h)
     if (!h) return;
     Mctx* c = reinterpret_cast<Mctx*>(h);
     (void)hipSetDevice(c->device);
-    if (c->d_rec) (void)dev_free(c->d_rec);
-    if (c->d_off) (void)dev_free(c->d_off);
-    if (c->d_n) (void)dev_free(c->d_n);
-    if (c->d_pr) (void)dev_free(c->d_pr);
-    if (c->d_theta) (void)dev_free(c->d_theta);
-    if (c->d_out) (void)dev_free(c->d_out);
-    if (c->d_wser) (void)dev_free(c->d_wser);
-    if (c->d_eidx) (void)dev_free(c->d_eidx);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
-    for (DevBuf* b : {&c->k_par, &c->k_int, &c->k_long, &c->k_tile, &c->k_res, &c->k_sing}) b->release();
     mpt_free(c);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                                 // (the DevMem members release their buffers)
 }
 
 int carma_mctx_nseries(const carma_mctx* h) { return h ? reinterpret_cast<const Mctx*>(h)->S : CARMA_EINVAL; }
@@ -732,19 +693,20 @@ int carma_mlogdensity_batch(carma_mctx* h, const double* theta, const int* serie
         }
     }
     hipStream_t st = c->stream;
-    e = hipMemcpyAsync(c->d_theta, h_th, sizeof(double) * (size_t)B * d, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->d_wser, h_wser, sizeof(int) * (size_t)W, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->d_eidx, h_eidx, sizeof(int) * (size_t)W * 64, hipMemcpyHostToDevice, st);
+    double *d_theta = c->d_theta.as<double>(), *d_out = c->d_out.as<double>();
+    int *d_wser = c->d_wser.as<int>(), *d_eidx = c->d_eidx.as<int>();
+    e = hipMemcpyAsync(d_theta, h_th, sizeof(double) * (size_t)B * d, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_wser, h_wser, sizeof(int) * (size_t)W, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_eidx, h_eidx, sizeof(int) * (size_t)W * 64, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return hip_fail(e, "carma_mlogdensity_batch: H2D");
     (void)hipGetLastError();   // HIP's last-error is sticky: drop anything left by earlier calls
-    const double4* rec = c->d_rec;
-    e = launch_logdens_ms(c->p, false, c->d_theta, d, c->q, rec, c->d_off, c->d_n, c->d_pr, c->d_wser, c->d_eidx, w_plain, ignore_prior,
-                          c->d_out, st);
+    e = launch_logdens_ms(c->p, false, d_theta, d, c->q, c->rec(), c->offs(), c->ns(), c->prs(), d_wser, d_eidx, w_plain, ignore_prior,
+                          d_out, st);
     if (e == hipSuccess)
-        e = launch_logdens_ms(c->p, true, c->d_theta, d, c->q, rec, c->d_off, c->d_n, c->d_pr, c->d_wser + w_plain,
-                              c->d_eidx + (size_t)w_plain * 64, W - w_plain, ignore_prior, c->d_out, st);
+        e = launch_logdens_ms(c->p, true, d_theta, d, c->q, c->rec(), c->offs(), c->ns(), c->prs(), d_wser + w_plain,
+                              d_eidx + (size_t)w_plain * 64, W - w_plain, ignore_prior, d_out, st);
     if (e != hipSuccess) return hip_fail(e, "carma_mlogdensity_batch: launch");
-    e = hipMemcpyAsync(h_out, c->d_out, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, st);
+    e = hipMemcpyAsync(h_out, d_out, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return hip_fail(e, "carma_mlogdensity_batch: D2H");
     std::memcpy(out, h_out, sizeof(double) * (size_t)B);
@@ -807,12 +769,12 @@ int carma_mkfilter(carma_mctx* h, const int* series, int M, const double* sigsqr
         const dim3 grid((unsigned)W), block(64);
         switch (p) {
             case 1:
-                hipLaunchKernelGGL(k_mkfilter_car1, grid, block, 0, st, d_par, M, c->d_rec, c->d_off, c->d_n, d_sser, d_toff, d_mv);
+                hipLaunchKernelGGL(k_mkfilter_car1, grid, block, 0, st, d_par, M, c->rec(), c->offs(), c->ns(), d_sser, d_toff, d_mv);
                 break;
 #define CARMA_MKF(N)                                                                                                              \
     case N:                                                                                                                       \
-        hipLaunchKernelGGL((k_mkfilter_carma_lane<N>), grid, block, 0, st, d_par, M, c->d_rec, c->d_off, c->d_n, d_sser, d_toff,  \
-                           d_mv, c->k_sing.as<int>());                                                                            \
+        hipLaunchKernelGGL((k_mkfilter_carma_lane<N>), grid, block, 0, st, d_par, M, c->rec(), c->offs(), c->ns(), d_sser,        \
+                           d_toff, d_mv, c->k_sing.as<int>());                                                                    \
         break;
                 CARMA_MKF(2) CARMA_MKF(3) CARMA_MKF(4) CARMA_MKF(5) CARMA_MKF(6) CARMA_MKF(7)
 #undef CARMA_MKF
@@ -828,7 +790,7 @@ int carma_mkfilter(carma_mctx* h, const int* series, int M, const double* sigsqr
         if (e == hipSuccess) e = hipMemcpyAsync(mean, d_mean, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipMemcpyAsync(var, d_var, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess && p > 1)
-            e = hipMemcpyAsync(sing.data(), c->k_sing.p, sizeof(int) * (size_t)M, hipMemcpyDeviceToHost, st);
+            e = hipMemcpyAsync(sing.data(), c->k_sing.as<int>(), sizeof(int) * (size_t)M, hipMemcpyDeviceToHost, st);
     }
     const hipError_t es = hipStreamSynchronize(st);           // (also after a failure: enqueued copies read and write this frame's vectors)
     if (e == hipSuccess) e = es;
@@ -926,14 +888,14 @@ int carma_mpredict(carma_mctx* h, const int* series, int M, const double* sigsqr
     std::vector<int> sing((size_t)M, 0);
     const size_t npar = par.size();
     e = c->k_par.need(sizeof(double) * (npar + (size_t)T));
-    if (e == hipSuccess) e = hipMemcpyAsync(c->k_par.p, par.data(), sizeof(double) * npar, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->k_par.as<void>(), par.data(), sizeof(double) * npar, hipMemcpyHostToDevice, st);
     if (e == hipSuccess)
         e = hipMemcpyAsync(c->k_par.as<double>() + npar, tpred + t0, sizeof(double) * (size_t)T, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = upload(c->k_int, tint, st);
     if (e == hipSuccess && p > 1) e = upload(c->k_long, tlong, st);
     if (e == hipSuccess) e = c->k_res.need(sizeof(double) * 2 * (size_t)T);
     if (e == hipSuccess) e = c->k_sing.need(sizeof(int) * (size_t)M);
-    if (e == hipSuccess) e = hipMemsetAsync(c->k_sing.p, 0, sizeof(int) * (size_t)M, st);
+    if (e == hipSuccess) e = hipMemsetAsync(c->k_sing.as<int>(), 0, sizeof(int) * (size_t)M, st);
     if (e == hipSuccess) {
         (void)hipGetLastError();
         const double *d_par = c->k_par.as<double>(), *d_tp = d_par + npar;
@@ -942,13 +904,13 @@ int carma_mpredict(carma_mctx* h, const int* series, int M, const double* sigsqr
         const dim3 grid((unsigned)W), block(64);
         switch (p) {
             case 1:
-                hipLaunchKernelGGL(k_mpredict_car1, grid, block, 0, st, d_par, c->d_rec, c->d_off, c->d_n, d_int, d_int + M, T, d_tp,
+                hipLaunchKernelGGL(k_mpredict_car1, grid, block, 0, st, d_par, c->rec(), c->offs(), c->ns(), d_int, d_int + M, T, d_tp,
                                    d_pm, d_pv);
                 break;
 #define CARMA_MPR(N)                                                                                                              \
     case N:                                                                                                                       \
-        hipLaunchKernelGGL((k_mpredict_carma<N, GroupOf<N>::value>), grid, block, 0, st, d_par, c->d_rec, c->d_off, c->d_n, d_int, \
-                           d_int + W, c->k_long.as<long>(), d_tp, d_pm, d_pv, c->k_sing.as<int>());                               \
+        hipLaunchKernelGGL((k_mpredict_carma<N, GroupOf<N>::value>), grid, block, 0, st, d_par, c->rec(), c->offs(), c->ns(),     \
+                           d_int, d_int + W, c->k_long.as<long>(), d_tp, d_pm, d_pv, c->k_sing.as<int>());                        \
         break;
                 CARMA_MPR(2) CARMA_MPR(3) CARMA_MPR(4) CARMA_MPR(5) CARMA_MPR(6) CARMA_MPR(7)
 #undef CARMA_MPR
@@ -957,7 +919,7 @@ int carma_mpredict(carma_mctx* h, const int* series, int M, const double* sigsqr
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(pmean + t0, d_pm, sizeof(double) * (size_t)T, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipMemcpyAsync(pvar + t0, d_pv, sizeof(double) * (size_t)T, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(sing.data(), c->k_sing.p, sizeof(int) * (size_t)M, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(sing.data(), c->k_sing.as<int>(), sizeof(int) * (size_t)M, hipMemcpyDeviceToHost, st);
     }
     const hipError_t es = hipStreamSynchronize(st);
     if (e == hipSuccess) e = es;

@@ -239,24 +239,6 @@ __global__ __launch_bounds__(QT) void k_row_quantiles(const double* __restrict__
     }
 }
 
-struct DevBufs {                                              // frees what it holds
-    std::vector<void*> p;
-    ~DevBufs()
-    {
-        for (void* q : p)
-            if (q) (void)dev_free(q);
-    }
-    template <class T>
-    hipError_t alloc(T** out, size_t n)
-    {
-        void* q = nullptr;
-        const hipError_t e = dev_malloc(&q, n * sizeof(T) ? n * sizeof(T) : sizeof(T));
-        if (e == hipSuccess) p.push_back(q);
-        *out = reinterpret_cast<T*>(q);
-        return e;
-    }
-};
-
 hipError_t post_grid_band(int nar, int nma, const double* d_ar, const double* d_ma, const double* d_sigma, int ns,
                           const double* d_freq, int nf, int nperc, const int* d_ranks, const double* d_gammas, double* d_grid,
                           int fc, double* d_band)
@@ -292,12 +274,12 @@ int carma_sigma_noise_batch(int p, int nma, const double* ar_roots_re_im, const 
     if (ns == 0) return CARMA_OK;
     int rc = select_device(device);
     if (rc != CARMA_OK) return rc;
-    DevBufs B;
-    double *d_r = nullptr, *d_m = nullptr, *d_v = nullptr, *d_s = nullptr;
-    hipError_t e = B.alloc(&d_r, (size_t)ns * p * 2);
-    if (e == hipSuccess) e = B.alloc(&d_m, (size_t)ns * nma);
-    if (e == hipSuccess) e = B.alloc(&d_v, (size_t)ns);
-    if (e == hipSuccess) e = B.alloc(&d_s, (size_t)ns);
+    DevMem b_r, b_m, b_v, b_s;
+    hipError_t e = b_r.alloc(sizeof(double) * ns * p * 2);
+    if (e == hipSuccess) e = b_m.alloc(sizeof(double) * ns * nma);
+    if (e == hipSuccess) e = b_v.alloc(sizeof(double) * ns);
+    if (e == hipSuccess) e = b_s.alloc(sizeof(double) * ns);
+    double *d_r = b_r.as<double>(), *d_m = b_m.as<double>(), *d_v = b_v.as<double>(), *d_s = b_s.as<double>();
     if (e == hipSuccess) e = hipMemcpy(d_r, ar_roots_re_im, sizeof(double) * ns * p * 2, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_m, ma_coefs, sizeof(double) * ns * nma, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_v, var, sizeof(double) * ns, hipMemcpyHostToDevice);
@@ -327,6 +309,7 @@ int carma_psd_band(int nar, int nma, const double* ar_coefs, const double* ma_co
         }
     int rc = select_device(device);
     if (rc != CARMA_OK) return rc;
+    DevMem b_a, b_m, b_s, b_f, b_g, b_band, b_gam, b_rk;
     // sample-major copies of the coefficient arrays (coalesced loads in k_psd_grid)
     std::vector<double> art((size_t)nar * ns), mat((size_t)nma * ns);
     for (int s = 0; s < ns; s++) {
@@ -336,29 +319,21 @@ int carma_psd_band(int nar, int nma, const double* ar_coefs, const double* ma_co
     // np.percentile(x, q) with the default method: virtual index (n - 1) q / 100, the order statistics either side of it
     std::vector<int> ranks(2 * (nperc > 0 ? nperc : 1), 0);
     std::vector<double> gam(nperc > 0 ? nperc : 1, 0.0);
-    for (int j = 0; j < nperc; j++) {
-        const double vi = (double)(ns - 1) * (percentiles[j] / 100.0);
-        double lo = std::floor(vi);
-        if (lo > ns - 1) lo = ns - 1;
-        const int ilo = (int)lo, ihi = ilo + 1 < ns ? ilo + 1 : ns - 1;
-        ranks[2 * j] = ilo;
-        ranks[2 * j + 1] = ihi;
-        gam[j] = vi - lo;
-    }
-    // the grid is held for `fc` frequencies at a time: at most 2^30 values (8 GiB) -- 3.2 million samples (all 64 cold chains of
-    // BASELINE configs[2]) take 335 rows per round
-    const int fc = (int)std::min<long>(nf, std::max<long>(1, (1L << 30) / ns));
-    DevBufs B;
-    double *d_a = nullptr, *d_m = nullptr, *d_s = nullptr, *d_f = nullptr, *d_g = nullptr, *d_band = nullptr, *d_gam = nullptr;
-    int* d_rk = nullptr;
-    hipError_t e = B.alloc(&d_a, art.size());
-    if (e == hipSuccess) e = B.alloc(&d_m, mat.size());
-    if (e == hipSuccess) e = B.alloc(&d_s, (size_t)ns);
-    if (e == hipSuccess) e = B.alloc(&d_f, (size_t)nf);
-    if (e == hipSuccess) e = B.alloc(&d_g, (size_t)fc * ns);
-    if (e == hipSuccess) e = B.alloc(&d_band, (size_t)nf * (nperc > 0 ? nperc : 1));
-    if (e == hipSuccess) e = B.alloc(&d_gam, gam.size());
-    if (e == hipSuccess) e = B.alloc(&d_rk, ranks.size());
+    for (int j = 0; j < nperc; j++) percentile_ranks(ns, percentiles[j], &ranks[2 * j], &gam[j]);
+    // the grid is held for `fc` frequencies at a time -- 3.2 million samples (all 64 cold chains of BASELINE configs[2]) take
+    // 335 rows per round
+    const int fc = post_grid_chunk(nf, ns);
+    hipError_t e = b_a.alloc(sizeof(double) * art.size());
+    if (e == hipSuccess) e = b_m.alloc(sizeof(double) * mat.size());
+    if (e == hipSuccess) e = b_s.alloc(sizeof(double) * ns);
+    if (e == hipSuccess) e = b_f.alloc(sizeof(double) * nf);
+    if (e == hipSuccess) e = b_g.alloc(sizeof(double) * fc * ns);
+    if (e == hipSuccess) e = b_band.alloc(sizeof(double) * nf * (nperc > 0 ? nperc : 1));
+    if (e == hipSuccess) e = b_gam.alloc(sizeof(double) * gam.size());
+    if (e == hipSuccess) e = b_rk.alloc(sizeof(int) * ranks.size());
+    double *d_a = b_a.as<double>(), *d_m = b_m.as<double>(), *d_s = b_s.as<double>(), *d_f = b_f.as<double>(), *d_g = b_g.as<double>(),
+           *d_band = b_band.as<double>(), *d_gam = b_gam.as<double>();
+    int* d_rk = b_rk.as<int>();
     if (e == hipSuccess) e = hipMemcpy(d_a, art.data(), sizeof(double) * art.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_m, mat.data(), sizeof(double) * mat.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_s, sigma, sizeof(double) * ns, hipMemcpyHostToDevice);

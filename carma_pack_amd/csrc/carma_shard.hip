@@ -576,24 +576,20 @@ int carma_pt_sample_sharded(carma_ctx* const* shards, int nlocal, int nsamples, 
         set_error("carma_pt_sample_sharded: the process that owns temperature 0 must pass sample buffers");
         return CARMA_EINVAL;
     }
-    double *d_s = nullptr, *d_l = nullptr;
+    DevMem b_s, b_l;                                  // (empty, null pointers, in the processes that do not own it)
     const size_t R = (size_t)c0->pt->R, d = (size_t)c0->d;
     if (owner) {
         hipError_t e = hipSetDevice(c0->device);
-        if (e == hipSuccess) e = dev_malloc(&d_s, sizeof(double) * R * nsamples * d);
-        if (e == hipSuccess) e = dev_malloc(&d_l, sizeof(double) * R * nsamples);
-        if (e != hipSuccess) {
-            if (d_s) (void)dev_free(d_s);
-            return hip_fail(e, "carma_pt_sample_sharded: sample buffers");
-        }
+        if (e == hipSuccess) e = b_s.alloc(sizeof(double) * R * nsamples * d);
+        if (e == hipSuccess) e = b_l.alloc(sizeof(double) * R * nsamples);
+        if (e != hipSuccess) return hip_fail(e, "carma_pt_sample_sharded: sample buffers");
     }
+    double *d_s = b_s.as<double>(), *d_l = b_l.as<double>();
     int rc = iterate_sharded(shards, nlocal, (long)nsamples * thin, comm, thin, nsamples, d_s, d_l);
     if (owner) {
         hipError_t e = hipSuccess;
         if (rc == CARMA_OK) e = hipMemcpy(samples, d_s, sizeof(double) * R * nsamples * d, hipMemcpyDeviceToHost);
         if (rc == CARMA_OK && e == hipSuccess) e = hipMemcpy(logposts, d_l, sizeof(double) * R * nsamples, hipMemcpyDeviceToHost);
-        (void)dev_free(d_s);
-        (void)dev_free(d_l);
         if (e != hipSuccess) rc = hip_fail(e, "carma_pt_sample_sharded: D2H");
     }
     return rc;
@@ -630,9 +626,10 @@ int carma_pt_debug_draws(carma_ctx* h, int replica, int temperature, unsigned lo
     }
     const int d = c->d;
     hipError_t e = hipSetDevice(c->device);
-    double* dbuf = nullptr;
-    if (e == hipSuccess) e = dev_malloc(&dbuf, sizeof(double) * (d + 2));
+    DevMem b_draws;
+    if (e == hipSuccess) e = b_draws.alloc(sizeof(double) * (d + 2));
     if (e != hipSuccess) return hip_fail(e, "carma_pt_debug_draws");
+    double* dbuf = b_draws.as<double>();
     const unsigned chain = (s->replica0 + (unsigned)replica) * s->T_global + s->slot0 + (unsigned)temperature;
     hipLaunchKernelGGL(k_pt_debug_draws, dim3(1), dim3(64), 0, c->stream, (unsigned)(s->seed & 0xffffffffu), (unsigned)(s->seed >> 32),
                        chain, iter, d, dbuf);
@@ -640,7 +637,6 @@ int carma_pt_debug_draws(carma_ctx* h, int replica, int temperature, unsigned lo
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(hb.data(), dbuf, sizeof(double) * (d + 2), hipMemcpyDeviceToHost);
-    (void)dev_free(dbuf);
     if (e != hipSuccess) return hip_fail(e, "carma_pt_debug_draws");
     std::memcpy(z, hb.data(), sizeof(double) * d);
     if (u_accept) *u_accept = hb[d];

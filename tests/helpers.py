@@ -335,3 +335,31 @@ def model_ma(rng, p, q):
         c = np.poly(-rng.uniform(0.3, 3.0, q))                   # highest order first
         ma[:q + 1] = (c / c[-1])[::-1]
     return ma
+
+
+# Buffer regrowth of the long-lived handles (KalmanHandle, MultiContext): one handle makes small, large and small calls in turn,
+# and every result must equal (np.array_equal) that of a fresh handle making that one call.
+REGROW_ORDERS = [(1, 0), (2, 0), (2, 1), (5, 0), (5, 1)]
+
+
+def regrow_series():
+    """Three irregular series of 20, 33 and 70 points."""
+    return [irregular_series(n, 900 + k) for k, n in enumerate((20, 33, 70))]
+
+
+def regrow_models(p, q, count, seed):
+    """`count` well-conditioned models: (sigsqr [count], roots [count][p] complex, ma [count][q + 1])."""
+    rng = np.random.default_rng(seed)
+    roots = np.array([model_roots(rng, p, "mixed" if p > 1 else "real") for _ in range(count)])
+    ma = np.array([model_ma(rng, p, q)[:q + 1] for _ in range(count)])
+    return rng.uniform(0.5, 2.0, count), roots, ma
+
+
+def assert_all_equal(got, want, what):
+    """np.array_equal on every array of two equally nested results (arrays, or tuples / lists of them)."""
+    if isinstance(got, (tuple, list)):
+        assert len(got) == len(want), what
+        for k, (a, b) in enumerate(zip(got, want)):
+            assert_all_equal(a, b, "%s[%d]" % (what, k))
+    else:
+        assert np.array_equal(got, want), what

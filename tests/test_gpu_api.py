@@ -324,3 +324,25 @@ def test_kalman_filter_objects_keep_their_series_on_the_device(cm, golden_dir):
     o1m, o1v = orc.kfilter_car1(t, y, e, 0.3, 0.05)
     np.testing.assert_allclose(np.array(k1.GetVar()), o1v, rtol=1e-11)
     assert abs(k1.Predict(float(tp[2])).first - orc.predict_car1(t, y, e, 0.3, 0.05, [tp[2]])[0][0]) < 1e-10
+
+
+@pytest.mark.parametrize("p,q", [(1, 0), (2, 0), (2, 1), (5, 0), (5, 1)])
+def test_kalman_handle_regrows_its_result_buffer(p, q):
+    """One KalmanHandle on a 70-point series: predict at 5 times, Filter(), predict at 300, Filter(), predict at 5 -- its one
+    result buffer holds exactly what the largest call so far asked for (15 -> 140 -> 900 doubles) and is reallocated on the
+    way.  Every result equals that of a fresh handle making only that call."""
+    import carma_pack_amd as cpa
+    from helpers import assert_all_equal, regrow_models, regrow_series
+    t, y, e = regrow_series()[2]
+    sig, roots, ma = regrow_models(p, q, 1, 40 + 10 * p + q)
+    args = (t, y, e, sig[0], -roots[0][0].real) if p == 1 else (t, y, e, sig[0], roots[0], ma[0])
+    rng = np.random.default_rng(7)
+    few, many = np.sort(rng.uniform(t[0] - 5.0, t[-1] + 5.0, 5)), rng.uniform(t[0] - 5.0, t[-1] + 5.0, 300)
+    kf = cpa._lib.KalmanHandle(*args)
+    for step, tp in enumerate((few, None, many, None, few)):
+        fresh = cpa._lib.KalmanHandle(*args)
+        got, want = (kf.filter(), fresh.filter()) if tp is None else (kf.predict(tp), fresh.predict(tp))
+        fresh.close()
+        assert all(np.isfinite(a).all() for a in want)
+        assert_all_equal(got, want, "CARMA(%d,%d) step %d" % (p, q, step))
+    kf.close()

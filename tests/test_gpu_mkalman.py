@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 import oracle as orc
-from helpers import irregular_series, prior_like_theta, record_allowance
+from helpers import (REGROW_ORDERS, assert_all_equal, irregular_series, prior_like_theta, record_allowance, regrow_models,
+                     regrow_series)
 from mp_truth import predict_truth, predict_truth_car1
 from test_gpu_model_kernels import GROUP, REPEATED_ROOTS, assert_near_truth, make_model
 
@@ -399,3 +400,33 @@ def test_model_set_assess_fit_and_predict(lib):
         a, b = kf.PredictBatch(tgrid)
         assert np.array_equal(pm_one[s], np.asarray(a) + mu) and np.array_equal(pv_one[s], np.asarray(b)), (s, p, q)
         assert np.array_equal(pm_lst[s], pm_one[s][:s + 1]) and np.array_equal(pv_lst[s], pv_one[s][:s + 1]), (s, p, q)
+
+
+@pytest.mark.parametrize("p,q", REGROW_ORDERS)
+def test_one_context_regrows_its_item_buffers(lib, p, q):
+    """One MultiContext on series of 20, 33 and 70 points: kfilter of 2, 130 and 2 items (130: three waves, and at p = 5 a
+    parameter upload of 130 x 17 doubles, past the 4096-byte floor of the grown buffers), then predict at 3 times in all, at 700
+    spread unevenly with one item given none, and at 3 again.  Every result equals that of a fresh context making only that call."""
+    series = regrow_series()
+    sig, roots, ma = regrow_models(p, q, 130, 60 + 10 * p + q)
+    if p == 1:
+        roots = roots[:, 0]
+    which = np.arange(130) % 3
+    ctx = lib.MultiContext(series, p, q)
+    for step, M in enumerate((2, 130, 2)):
+        fresh = lib.MultiContext(series, p, q)
+        call = (which[:M], sig[:M], roots[:M], ma[:M])
+        got, want = ctx.kfilter(*call, mu=sig[:M] - 1.0), fresh.kfilter(*call, mu=sig[:M] - 1.0)
+        fresh.close()
+        assert not want[2].any() and all(np.isfinite(a).all() for a in want[0] + want[1])
+        assert_all_equal(got, want, "kfilter CARMA(%d,%d) step %d" % (p, q, step))
+    rng = np.random.default_rng(8)
+    item = (np.array([2, 0, 1, 2]), sig[:4], roots[:4], ma[:4])
+    for step, counts in enumerate(((2, 0, 1, 0), (300, 0, 250, 150), (2, 0, 1, 0))):
+        times = [rng.uniform(-5.0, 150.0, k) for k in counts]
+        fresh = lib.MultiContext(series, p, q)
+        got, want = ctx.predict(*item, times), fresh.predict(*item, times)
+        fresh.close()
+        assert all(np.isfinite(a).all() for a in want[0] + want[1])
+        assert_all_equal(got, want, "predict CARMA(%d,%d) step %d" % (p, q, step))
+    ctx.close()

@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 import oracle as orc
-from helpers import assert_parity, irregular_series, loglik_truth, prior_like_theta, theta_batch
+from helpers import (REGROW_ORDERS, assert_parity, irregular_series, loglik_truth, prior_like_theta, regrow_series,
+                     theta_batch)
 
 pytestmark = pytest.mark.gpu
 
@@ -250,3 +251,22 @@ def test_error_paths(cpa, sset):
     assert cpa.MultiContext(sset[:2], 1, 0).kernel_name() == "k_logdens_car1_ms"
     with pytest.raises(ValueError):
         mc.mle_batched(np.tile(th, (2, 1)), [0, 5], -np.inf, np.inf)
+
+
+@pytest.mark.parametrize("p,q", REGROW_ORDERS)
+def test_one_context_regrows_its_batch_buffers(cpa, p, q):
+    """One MultiContext on series of 20, 33 and 70 points, `which` cycling over them: logdensity of 3, 1500, 3, 4500 and 3
+    parameter vectors.  The batch buffers start at 1024 vectors and 64 waves: 1500 vectors (24 waves) outgrow the first, 4500
+    (72 waves) both.  Every result equals that of a fresh context making only that call."""
+    series = regrow_series()
+    rng = np.random.default_rng(70 + 10 * p + q)
+    which = np.arange(4500) % 3
+    th = np.array([prior_like_theta(rng, p, q, series[w][0], series[w][1]) for w in which])
+    ctx = cpa.MultiContext(series, p, q)
+    for step, B in enumerate((3, 1500, 3, 4500, 3)):
+        fresh = cpa.MultiContext(series, p, q)
+        got, want = ctx.logdensity(th[:B], which[:B]), fresh.logdensity(th[:B], which[:B])
+        fresh.close()
+        assert not np.isnan(want).any() and (B < 1500 or np.isfinite(want).any())
+        assert np.array_equal(got, want), "CARMA(%d,%d) step %d" % (p, q, step)
+    ctx.close()
