@@ -147,6 +147,7 @@ class CARMA(CARp):
 sigma_noise_batch = _lib.sigma_noise_batch
 psd_band = _lib.psd_band
 mpsd_band = _lib.mpsd_band
+chain_diag = _lib.chain_diag
 simulate_cond_carma = _lib.simulate_cond_carma
 simulate_cond_car1 = _lib.simulate_cond_car1
 

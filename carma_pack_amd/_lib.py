@@ -184,6 +184,10 @@ def _load():
                                   C.c_int]
     L.carma_mpsd_fused_max.argtypes = []
     L.carma_mpsd_freq_tile.argtypes = []
+    L.carma_chain_diag.argtypes = [_dp, C.c_long, C.c_int, C.c_long, C.c_int, _dp, _dp, _dp, _ip, _dp, C.c_int]
+    L.carma_chain_diag_dmax.argtypes = []
+    L.carma_chain_diag_kernel_ms.argtypes = []
+    L.carma_chain_diag_kernel_ms.restype = C.c_double
     L.carma_pt_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_uint64,
                                _dp, _dp]
     L.carma_pt_create.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, C.c_uint64]
@@ -235,7 +239,7 @@ EXPORTS = [
     "carma_mle_batched_ms", "carma_mkfilter", "carma_mpredict", "carma_mpt_create", "carma_mpt_start", "carma_mpt_set_chains",
     "carma_mpt_get_chains", "carma_mpt_get_factor", "carma_mpt_set_factor", "carma_mpt_iterate", "carma_mpt_sample",
     "carma_mpt_stats", "carma_mpt_iterations_done", "carma_mpt_logdensity", "carma_mpt_kernel_name", "carma_mpt_run",
-    "carma_mpsd_band", "carma_mpsd_fused_max", "carma_mpsd_freq_tile",
+    "carma_mpsd_band", "carma_mpsd_fused_max", "carma_mpsd_freq_tile", "carma_chain_diag", "carma_chain_diag_dmax", "carma_chain_diag_kernel_ms",
 ]
 
 
@@ -1125,6 +1129,54 @@ def mpsd_band(ar_coefs, ma_coefs, sigma, sample_start, freq, percentiles, device
                               ptr(fr), fr.shape[1], ptr(pc), pc.size, ptr(band), default_device() if device is None else device),
           "carma_mpsd_band")
     return band
+
+
+def chain_diag_dmax():
+    """The widest column count one carma_chain_diag call serves (carma_chain_diag_dmax)."""
+    return int(lib.carma_chain_diag_dmax())
+
+
+def chain_diag_kernel_ms():
+    """Device time in ms of the kernels of the last carma_chain_diag call of this process (carma_chain_diag_kernel_ms)."""
+    return float(lib.carma_chain_diag_kernel_ms())
+
+
+def chain_diag(x, rhat=True, device=None):
+    """Chain diagnostics of a whole sampled set on the device (carma_chain_diag).  x: [G, R, L, d] -- G groups of R replicas of
+    L samples of d columns; [L], [L, d] and [R, L, d] are taken as one column, one chain, one group.  Returns a dict: tau
+    (Goodman's acor autocorrelation time), mean, sigma (the standard error of the mean), status (0 OK, 1 SHORT, 2 CONSTANT,
+    3 NONFINITE; tau and sigma are NaN unless it is 0), each [G, R, d], and rhat [G, d] (split R-hat over the replicas of a
+    group; None with rhat=False).  More than chain_diag_dmax() columns are served in slabs of that many."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim == 1:
+        x = x[None, None, :, None]
+    elif x.ndim == 2:
+        x = x[None, None]
+    elif x.ndim == 3:
+        x = x[None]
+    if x.ndim != 4:
+        raise ValueError("chain_diag: x must be [G, R, L, d] ([L], [L, d] and [R, L, d] are promoted), got %d axes" % x.ndim)
+    if 0 in x.shape:
+        raise ValueError("chain_diag: x has an empty axis: %r" % (x.shape,))
+    G, R, L, d = x.shape
+    dev = default_device() if device is None else int(device)
+    dmax = chain_diag_dmax()
+    out = dict(tau=np.empty((G, R, d)), mean=np.empty((G, R, d)), sigma=np.empty((G, R, d)),
+               status=np.empty((G, R, d), dtype=np.int32), rhat=np.empty((G, d)) if rhat else None)
+    for c0 in range(0, d, dmax):
+        c1 = min(d, c0 + dmax)
+        xs = as_f64(x if (c0, c1) == (0, d) else x[..., c0:c1])
+        part = [np.empty((G, R, c1 - c0)) for _ in range(3)]
+        st = np.empty((G, R, c1 - c0), dtype=np.int32)
+        rh = np.empty((G, c1 - c0)) if rhat else None
+        check(lib.carma_chain_diag(ptr(xs), G, R, L, c1 - c0, ptr(part[0]), ptr(part[1]), ptr(part[2]), st.ctypes.data_as(_ip),
+                                   ptr(rh) if rhat else None, dev), "carma_chain_diag")
+        for k, name in enumerate(("tau", "mean", "sigma")):
+            out[name][..., c0:c1] = part[k]
+        out["status"][..., c0:c1] = st
+        if rhat:
+            out["rhat"][:, c0:c1] = rh
+    return out
 
 
 def pt_sample_sharded(contexts, nsamples, thin=1, comm=None):

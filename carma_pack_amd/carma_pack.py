@@ -164,8 +164,8 @@ STATUS_TEXT = ("converged: projected gradient <= gtol", "converged: relative red
 
 
 class MCMCSample(object):
-    """Minimal sample container (the reference's samplers.MCMCSample holds the same `_samples` dict;
-    its plotting/diagnostic methods are outside the hot path)."""
+    """Minimal sample container (the reference's samplers.MCMCSample holds the same `_samples` dict; its plotting methods are
+    outside the hot path, its two diagnostics -- autocorr_timescale, effective_samples -- run on the device)."""
 
     def __init__(self, filename=None, logpost=None, trace=None):
         # reference samplers.py:27-45: a trace wins over a file name
@@ -203,6 +203,40 @@ class MCMCSample(object):
         out = dict(median=np.median(s, axis=0), mean=np.mean(s, axis=0), std=np.std(s, axis=0),
                    ci68=np.percentile(s, [16.0, 84.0], axis=0), ci95=np.percentile(s, [2.5, 97.5], axis=0))
         return out
+
+
+    def autocorr_timescale(self, trace):
+        """The autocorrelation time of every column of a trace ([ns] or [ns, k]; the real part of a complex one), as estimated
+        by Goodman's `acor` (reference samplers.py:74-84) -- all columns in one device call (carma_chain_diag).  A column the
+        estimator has no answer for (too short, constant, non-finite: chain_diag's status) comes back NaN."""
+        trace = np.asarray(trace)
+        if trace.ndim not in (1, 2):
+            raise ValueError("trace must be [ns] or [ns, k], got %d axes" % trace.ndim)
+        if trace.ndim == 1:
+            trace = trace[:, None]
+        return carmcmcLib.chain_diag(np.ascontiguousarray(trace.real, dtype=float), rhat=False)["tau"][0, 0]
+
+    def effective_samples(self, name):
+        """The effective number of independent samples of parameter `name`: ns / autocorr_timescale, per column (reference
+        samplers.py:86-101).  An unknown name is a KeyError."""
+        if name not in self._samples:
+            raise KeyError("sampler does not have %r" % (name,))
+        traces = self._samples[name]
+        return traces.shape[0] / self.autocorr_timescale(traces)
+
+
+def _diagnostics_of(par, lp):
+    """chain_diag results of the parameter columns (par) and of the log-posterior column (lp) joined: the columns are the
+    parameter vector followed by logpost."""
+    return {k: np.concatenate([par[k], lp[k]], axis=-1) for k in ("tau", "mean", "sigma", "status", "rhat")}
+
+
+def _ess_of(tau, status, L):
+    """Sum over the replicas (the last axis but one) of L / tau; NaN where a replica's status is not 0."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ess = np.sum(L / tau, axis=-2)
+    ess[np.any(status != 0, axis=-2)] = np.nan
+    return ess
 
 
 def _roots_from_log_quads(logq):
@@ -343,6 +377,20 @@ class CarmaSample(MCMCSample):
         offer = getattr(self._sampler, "getSigmaNoise", None)
         sigma = offer(*args) if offer is not None else None
         self._samples["sigma"] = carmcmcLib.sigma_noise_batch(*args) if sigma is None else sigma
+
+    def diagnostics(self):
+        """Has the run mixed?  Over ALL replicas of the run (getAllSamples of the wrapped sampler), per column of the sampler's
+        own parameter vector followed by logpost as the last column: tau [R, d + 1] (acor autocorrelation time), ess [d + 1]
+        (sum over the replicas of L / tau; NaN where a replica's status is not 0), rhat [d + 1] (split R-hat over the
+        replicas), status [R, d + 1], mean and sigma [R, d + 1] -- two device calls (carma_chain_diag)."""
+        samples, logposts = self._sampler.getAllSamples()
+        if samples is None:
+            raise ValueError("the sampler holds no samples")
+        samples, logposts = np.asarray(samples, dtype=float), np.asarray(logposts, dtype=float)
+        out = _diagnostics_of(carmcmcLib.chain_diag(samples[None]), carmcmcLib.chain_diag(logposts[None, :, :, None]))
+        out = {k: v[0] for k, v in out.items()}
+        out["ess"] = _ess_of(out["tau"], out["status"], samples.shape[1])
+        return out
 
     def add_mle(self, MLE):
         x = np.asarray(MLE.x, dtype=float)
@@ -866,6 +914,34 @@ class CarmaModelSet(object):
             band[idx] = carmcmcLib.mpsd_band(*(np.concatenate([ins[s][k] for s in idx]) for k in range(3)), start, freq[idx],
                                              [lower, 50.0, 100.0 - lower])
         return band[:, :, 0], band[:, :, 2], band[:, :, 1], np.array(freq)
+
+    def diagnostics(self, samples=None):
+        """CarmaSample.diagnostics of EVERY series, in the caller's order, in two device calls (carma_chain_diag: one over the
+        parameter vectors of all series' replicas, one over their log-posteriors): tau [S, R, d + 1], ess [S, d + 1],
+        rhat [S, d + 1], status [S, R, d + 1], mean and sigma [S, R, d + 1]; the last column is logpost.  samples: a list of S
+        CarmaSample / Car1Sample, by default self.mcmc_samples of run_mcmc; all must hold the same number of replicas, of
+        samples and of parameters."""
+        S = self.nseries
+        if samples is None:
+            samples = self.mcmc_samples
+            if samples is None:
+                raise ValueError("no samples: call run_mcmc first, or pass samples=")
+        samples = list(samples)
+        if len(samples) != S:
+            raise ValueError("samples must hold one sample object per series (%d), got %d" % (S, len(samples)))
+        runs = [smp._sampler.getAllSamples() for smp in samples]
+        if any(par is None or lp is None for par, lp in runs):
+            raise ValueError("a sample object's sampler holds no samples")
+        shape = np.shape(runs[0][0])
+        for s, (par, lp) in enumerate(runs):
+            if len(np.shape(par)) != 3 or np.shape(par) != shape or np.shape(lp) != shape[:2]:
+                raise ValueError("series %d: samples of shape %r with log-posteriors %r; every series must hold [R, L, d] = %r "
+                                 "(the same replicas, sample count and order)" % (s, np.shape(par), np.shape(lp), tuple(shape)))
+        par = np.stack([np.asarray(r[0], dtype=float) for r in runs])
+        lp = np.stack([np.asarray(r[1], dtype=float) for r in runs])[..., None]
+        out = _diagnostics_of(carmcmcLib.chain_diag(par), carmcmcLib.chain_diag(lp))
+        out["ess"] = _ess_of(out["tau"], out["status"], shape[1])
+        return out
 
     def _set_starts(self, p, q, ntrials, seed):
         """The starts of get_mle(starts="set"): CarmaModel._mle_problem's short tempered run (25 adapting iterations, one

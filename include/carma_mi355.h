@@ -368,6 +368,31 @@ int carma_mpsd_fused_max(void);
 int carma_mpsd_freq_tile(void);
 
 /*
+ * carma_chain_diag == the chain diagnostics of a sampled set in one call (MCMCSample.autocorr_timescale / effective_samples,
+ * CarmaSample.diagnostics, CarmaModelSet.diagnostics): x = [ngroups][nreplicas][nsamples][d], row-major -- what carma_pt_run and
+ * carma_mpt_run return -- every (group, replica) one chain of nsamples rows of d columns.  Per chain and column:
+ *   tau     Goodman's `acor` autocorrelation time (MAXLAG 10, WINMULT 5, MINFAC 5: the series is centred, its autocovariances at
+ *           lags 0 ... 10 give D = C[0] + 2 sum C[s] and tau = D / C[0]; while tau >= 2 neighbouring values are summed in pairs
+ *           and the estimate is repeated on the halved series, and the result is unwound as D = sigma^2 L / 4 level by level)
+ *   mean    the plain mean,  sigma: the standard error of the mean that comes with tau
+ *   status  0 OK; 1 SHORT: a level had fewer than 50 rows before tau < 2 was reached (the C original silently reports a quarter
+ *           of the enclosing level's value there); 2 CONSTANT: C[0] == 0 at level 0; 3 NONFINITE: the column holds a NaN or Inf.
+ *           tau = sigma = NaN unless the status is 0.  A negative tau (a short anti-correlated chain) is a legitimate result.
+ * rhat = [ngroups][d], or NULL when it is not wanted: split R-hat (BDA3, no rank normalisation) over the 2 nreplicas halves
+ * (first and last nsamples / 2 rows) of a group's chains; NaN when nsamples / 2 < 2, when the mean variance W is 0, or when a
+ * chain of the group holds a non-finite value in that column.  tau, mean, sigma, status = [ngroups][nreplicas][d].
+ * All host pointers.  One device block (the input, the workspace of the halved levels, the results) and one copy each way.  The
+ * results are deterministic: the same bits on every call, and a chain's do not depend on the other chains of the call.
+ * Bad arguments -- a null x, tau, mean, sigma or status; ngroups, nreplicas or nsamples < 1; d < 1 or d > carma_chain_diag_dmax()
+ * (16: the widest parameter vector, 3 + p + q at p = 7) -- return CARMA_EINVAL before any device work.  Short chains are not an
+ * argument error.
+ */
+int carma_chain_diag(const double* x, long ngroups, int nreplicas, long nsamples, int d, double* tau, double* mean, double* sigma,
+                     int* status, double* rhat, int device);
+int carma_chain_diag_dmax(void);
+double carma_chain_diag_kernel_ms(void);    /* device time of the kernels of this process's last successful call; -1 before one */
+
+/*
  * Parallel-tempered Robust-Adaptive-Metropolis sampler == RunCarmaSampler / RunCar1Sampler
  * (src/carmcmc.cpp:30-177; bindings run_mcmc_car1 / run_mcmc_carma, boost_python_wrapper.cpp:76-77)
  * with every chain advanced on the GPU by one persistent kernel (carma_pt.hip).
