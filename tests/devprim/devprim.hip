@@ -1,5 +1,6 @@
 // devprim.hip -- TEST HARNESS ONLY: thin kernels around the device building blocks of carma_pack_amd/csrc (carma_math.h,
-// grp_device.h, carma_row_asm.h, carma_rng.h), one primitive call per lane, arguments and results in plain arrays.
+// grp_device.h, carma_row_asm.h, carma_rng.h, and of the windowed pipeline carma_pipew.h: pipew_merge, WinAsm<P>::init / ::chunk,
+// recip, rsqrt_pos), one primitive call per lane, arguments and results in plain arrays.
 // tests/devprim_ref.py builds it into tests/devprim/libdevprim.so and loads it with ctypes; the product never loads it.
 //
 // Every launcher: allocate, copy in, launch, synchronise, copy out, free; returns 0 or the HIP error code.  Launches are
@@ -8,6 +9,8 @@
 #include "grp_device.h"
 #include "carma_math.h"
 #include "carma_rng.h"
+#include "carma_core.h"
+#include "carma_pipew.h"
 
 #include <cstdint>
 #include <vector>
@@ -60,7 +63,8 @@ struct Bufs {
 bool full_waves(int n, int threads) { return n > 0 && (threads == 64 || threads == 256) && n % threads == 0; }
 
 // ------------------------------------------------------------------------------------------------------------ math
-enum { F_EXP_NEG, F_EXP_NEG_TAB, F_SINCOS_CW, F_CEXP, F_CEXP_TAB, F_CEXP_EXACT, F_CEXP_TAB_EXACT, F_COUNT };
+enum { F_EXP_NEG, F_EXP_NEG_TAB, F_SINCOS_CW, F_CEXP, F_CEXP_TAB, F_CEXP_EXACT, F_CEXP_TAB_EXACT, F_RECIP, F_RSQRT_POS, F_RCP_RAW,
+       F_RSQ_RAW, F_COUNT };
 
 template <int FN>
 __global__ __launch_bounds__(256) void k_math(int n, const double* __restrict__ a, const double* __restrict__ b,
@@ -80,6 +84,10 @@ __global__ __launch_bounds__(256) void k_math(int n, const double* __restrict__ 
     if constexpr (FN == F_CEXP_TAB) cexp_step_tab<false>(a[i], b[i], dt[i], &r0, &r1, tab);
     if constexpr (FN == F_CEXP_EXACT) cexp_step<true>(a[i], b[i], dt[i], &r0, &r1, dt_lo[i]);
     if constexpr (FN == F_CEXP_TAB_EXACT) cexp_step_tab<true>(a[i], b[i], dt[i], &r0, &r1, tab);
+    if constexpr (FN == F_RECIP) r0 = recip(a[i]);
+    if constexpr (FN == F_RSQRT_POS) r0 = rsqrt_pos(a[i]);
+    if constexpr (FN == F_RCP_RAW) r0 = __builtin_amdgcn_rcp(a[i]);
+    if constexpr (FN == F_RSQ_RAW) r0 = __builtin_amdgcn_rsq(a[i]);
     o0[i] = r0;
     o1[i] = r1;
 }
@@ -198,6 +206,84 @@ __global__ __launch_bounds__(256) void k_row(int n, const double* __restrict__ i
     o[RO_INNOV] = innov;
 }
 
+// ------------------------------------------------------------------------------------------- two-sided merge, window blocks
+// One wave per block.  The merge: per lane in kf[P], nu (carma_pipew.h: the virtual lanes ND + j of rows 0 / 2 carry column j of Da
+// and -a_j, those of rows 1 / 3 column j of Db and -beta_j); out {acc.total(), the row pair's sum as pipew_recur forms it}.
+template <int P>
+__global__ __launch_bounds__(64) void k_merge(int n, const double* __restrict__ in, double* __restrict__ out)
+{
+    __shared__ double2 ring[PipeWGeom<P>::ENTRIES];
+    const int lane = threadIdx.x, i = blockIdx.x * 64 + lane;
+    if (i >= n) return;                                       // (never: full waves only)
+    const double* x = in + (size_t)i * (P + 1);
+    double kf[P];
+#pragma unroll
+    for (int r = 0; r < P; r++) kf[r] = x[r];
+    const double nu = x[P];
+    LogLikAcc acc;
+    acc.init();
+    pipew_merge<P>(lane, kf, nu, ring, acc);
+    const double tot = acc.total();
+    double ll = Grp<16>::sum(tot);
+    ll += __shfl_xor(ll, 16, 64);
+    out[(size_t)i * 2] = tot;
+    out[(size_t)i * 2 + 1] = ll;
+}
+
+// WinAsm<P>::init -- per lane in: kn[P], nun, kk[P], nuF, hn[P];  out: kn[P], nun
+template <int P>
+__global__ __launch_bounds__(64) void k_win_init(int n, const double* __restrict__ in, double* __restrict__ out)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const double* x = in + (size_t)i * (3 * P + 2);
+    double kn[P], kk[P], hn[P];
+#pragma unroll
+    for (int r = 0; r < P; r++) {
+        kn[r] = x[r];
+        kk[r] = x[P + 1 + r];
+        hn[r] = x[2 * P + 2 + r];
+    }
+    double nun = x[P];
+    const double nuF = x[2 * P + 1];
+    WinAsm<P>::init(kn, nun, kk, nuF, hn);
+#pragma unroll
+    for (int r = 0; r < P; r++) out[(size_t)i * (P + 1) + r] = kn[r];
+    out[(size_t)i * (P + 1) + P] = nun;
+}
+
+// WinAsm<P>::chunk -- per lane in: kk[P], hh[P], m, nu (mA = mB = m, nuA = nuB = nu, as the start of a chunk leaves them);
+// out: kk[P], mA, mB, nuA, nuB.  MASKED: the call sits under `if (row active)` (rows: bits of a kernel argument), outputs and a
+// marker are stored by the lanes that are active BEHIND the call -- the block narrows EXEC and has to hand the caller's mask back.
+template <int P, bool MASKED>
+__global__ __launch_bounds__(64) void k_win_chunk(int n, int rows, const double* __restrict__ in, double* __restrict__ out,
+                                                  int* __restrict__ marker)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const double* x = in + (size_t)i * (2 * P + 2);
+    double* o = out + (size_t)i * (P + 4);
+    double kk[P], hh[P];
+#pragma unroll
+    for (int r = 0; r < P; r++) {
+        kk[r] = x[r];
+        hh[r] = x[P + r];
+    }
+    double mA = x[2 * P], mB = mA, nuA = x[2 * P + 1], nuB = nuA;
+    if (!MASKED || ((rows >> (threadIdx.x >> 4)) & 1)) {
+        __builtin_amdgcn_sched_barrier(0);
+        WinAsm<P>::chunk(kk, hh, mA, mB, nuA, nuB);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int r = 0; r < P; r++) o[r] = kk[r];
+        o[P] = mA;
+        o[P + 1] = mB;
+        o[P + 2] = nuA;
+        o[P + 3] = nuB;
+        marker[i] = 1;
+    }
+}
+
 // -------------------------------------------------------------------------------------------------------------- RNG
 // words: [n][6] c0 c1 c2 c3 k0 k1 -> out [n][4], u [n] = u01(out0, out1)
 __global__ __launch_bounds__(256) void k_philox(int n, const uint32_t* __restrict__ words, uint32_t* __restrict__ out,
@@ -253,6 +339,10 @@ int devprim_math(int fn, int n, int threads, const double* a, const double* b, c
             DEVPRIM_MATH_CASE(F_CEXP_TAB)
             DEVPRIM_MATH_CASE(F_CEXP_EXACT)
             DEVPRIM_MATH_CASE(F_CEXP_TAB_EXACT)
+            DEVPRIM_MATH_CASE(F_RECIP)
+            DEVPRIM_MATH_CASE(F_RSQRT_POS)
+            DEVPRIM_MATH_CASE(F_RCP_RAW)
+            DEVPRIM_MATH_CASE(F_RSQ_RAW)
 #undef DEVPRIM_MATH_CASE
         }
         B.ran();
@@ -303,6 +393,89 @@ int devprim_row(int P, int n, int threads, const double* in, double e, double y,
     }
     B.back(out, d_o, (size_t)n * ROW_OUT);
     return B.done();
+}
+
+#define DEVPRIM_FOR_P(CALL) \
+    switch (P) {            \
+        case 2: CALL(2); break; \
+        case 3: CALL(3); break; \
+        case 4: CALL(4); break; \
+        case 5: CALL(5); break; \
+        case 6: CALL(6); break; \
+        case 7: CALL(7); break; \
+    }
+
+// in [nblocks * 64][P + 1], out [nblocks * 64][2]
+int devprim_merge(int P, int nblocks, const double* in, double* out)
+{
+    if (nblocks <= 0 || P < 2 || P > 7) return (int)hipErrorInvalidValue;
+    const int n = nblocks * 64;
+    Bufs B;
+    const double* di = B.in(in, (size_t)n * (P + 1));
+    double* d_o = B.out<double>((size_t)n * 2);
+    if (B.err == hipSuccess) {
+#define DEVPRIM_CALL(Q) hipLaunchKernelGGL(k_merge<Q>, dim3(nblocks), dim3(64), 0, nullptr, n, di, d_o)
+        DEVPRIM_FOR_P(DEVPRIM_CALL)
+#undef DEVPRIM_CALL
+        B.ran();
+    }
+    B.back(out, d_o, (size_t)n * 2);
+    return B.done();
+}
+
+// in [nblocks * 64][3 P + 2], out [nblocks * 64][P + 1]
+int devprim_win_init(int P, int nblocks, const double* in, double* out)
+{
+    if (nblocks <= 0 || P < 2 || P > 7) return (int)hipErrorInvalidValue;
+    const int n = nblocks * 64;
+    Bufs B;
+    const double* di = B.in(in, (size_t)n * (3 * P + 2));
+    double* d_o = B.out<double>((size_t)n * (P + 1));
+    if (B.err == hipSuccess) {
+#define DEVPRIM_CALL(Q) hipLaunchKernelGGL(k_win_init<Q>, dim3(nblocks), dim3(64), 0, nullptr, n, di, d_o)
+        DEVPRIM_FOR_P(DEVPRIM_CALL)
+#undef DEVPRIM_CALL
+        B.ran();
+    }
+    B.back(out, d_o, (size_t)n * (P + 1));
+    return B.done();
+}
+
+namespace {
+// in [n][2 P + 2]; out [n][P + 4] and marker [n] keep what the caller put there in the lanes that store nothing
+int win_chunk(int P, int nblocks, bool masked, int rows, const double* in, double* out, int* marker)
+{
+    if (nblocks <= 0 || P < 2 || P > 7) return (int)hipErrorInvalidValue;
+    const int n = nblocks * 64;
+    Bufs B;
+    const double* di = B.in(in, (size_t)n * (2 * P + 2));
+    double* d_o = B.in(out, (size_t)n * (P + 4));
+    int* dm = B.in(marker, n);
+    if (B.err == hipSuccess) {
+#define DEVPRIM_CALL(Q)                                                                                          \
+    if (masked)                                                                                                  \
+        hipLaunchKernelGGL((k_win_chunk<Q, true>), dim3(nblocks), dim3(64), 0, nullptr, n, rows, di, d_o, dm);   \
+    else                                                                                                         \
+        hipLaunchKernelGGL((k_win_chunk<Q, false>), dim3(nblocks), dim3(64), 0, nullptr, n, rows, di, d_o, dm)
+        DEVPRIM_FOR_P(DEVPRIM_CALL)
+#undef DEVPRIM_CALL
+        B.ran();
+    }
+    B.back(out, d_o, (size_t)n * (P + 4));
+    B.back(marker, dm, n);
+    return B.done();
+}
+}  // namespace
+
+int devprim_win_chunk(int P, int nblocks, const double* in, double* out, int* marker)
+{
+    return win_chunk(P, nblocks, false, 0xf, in, out, marker);
+}
+
+// rows: bit q set = row q of every wave is active at the call
+int devprim_win_chunk_masked(int P, int nblocks, int rows, const double* in, double* out, int* marker)
+{
+    return win_chunk(P, nblocks, true, rows & 0xf, in, out, marker);
 }
 
 int devprim_philox(int n, int threads, const uint32_t* words, uint32_t* out, double* u)

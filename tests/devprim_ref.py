@@ -1,6 +1,8 @@
 """Builds and loads the device-primitive harness (tests/devprim/devprim.hip) and the host build of carma_math.h
 (tests/devprim/hostmath.cpp); the argument arrays of the primitive tests; their references, mpmath at 50 digits and numpy
-restatements of grp_device.h / carma_row_asm.h / carma_rng.h.  Test code only."""
+restatements of grp_device.h / carma_row_asm.h / carma_rng.h; for the two-sided merge (carma_pipew.h pipew_merge) the closed form
+in mpmath at 120 digits, for the window blocks (carma_win_asm.h) the elimination of tools/gen_win_asm.py's docstring in mpmath
+with a running error bound.  Test code only."""
 import ctypes as C
 import functools
 import os
@@ -18,7 +20,8 @@ DEV_SRC = os.path.join(HERE, "devprim", "devprim.hip")
 DEV_SO = os.path.join(HERE, "devprim", "libdevprim.so")
 HOST_SRC = os.path.join(HERE, "devprim", "hostmath.cpp")
 HOST_SO = os.path.join(HERE, "devprim", "libhostmath.so")
-DEV_HEADERS = ("grp_device.h", "carma_types.h", "carma_row_asm.h", "carma_math.h", "carma_math_tab.h", "carma_rng.h")
+DEV_HEADERS = ("grp_device.h", "carma_types.h", "carma_row_asm.h", "carma_math.h", "carma_math_tab.h", "carma_rng.h", "carma_core.h",
+               "carma_pipew.h", "carma_pipe3l.h", "carma_win_asm.h")
 
 MP = mp.mp.clone()
 MP.dps = 50
@@ -56,6 +59,10 @@ def device():
     L.devprim_row.argtypes = [C.c_int, C.c_int, C.c_int, _dp, C.c_double, C.c_double, _dp]
     L.devprim_philox.argtypes = [C.c_int, C.c_int, _up, _up, _dp]
     L.devprim_rng.argtypes = [C.c_int, C.c_int, _up, _qp, _dp]
+    L.devprim_merge.argtypes = [C.c_int, C.c_int, _dp, _dp]
+    L.devprim_win_init.argtypes = [C.c_int, C.c_int, _dp, _dp]
+    L.devprim_win_chunk.argtypes = [C.c_int, C.c_int, _dp, _dp, _ip]
+    L.devprim_win_chunk_masked.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp, _ip]
     return L
 
 
@@ -92,7 +99,8 @@ def _ptr(a, t=_dp):
     return a.ctypes.data_as(t)
 
 
-FN = dict(exp_neg=0, exp_neg_tab=1, sincos_cw=2, cexp=3, cexp_tab=4, cexp_exact=5, cexp_tab_exact=6)
+FN = dict(exp_neg=0, exp_neg_tab=1, sincos_cw=2, cexp=3, cexp_tab=4, cexp_exact=5, cexp_tab_exact=6,
+          recip=7, rsqrt_pos=8, rcp_raw=9, rsq_raw=10)         # (7 .. 10: device only -- on the host recip() is a division)
 COMPLEX_FORMS = ("cexp", "cexp_tab", "cexp_exact", "cexp_tab_exact")
 
 
@@ -390,6 +398,11 @@ HOST_MAX = {
                    big_poly_exact=3.34, big_tab_exact=2.84),
     "edges": dict(exp_neg=0.99, exp_neg_tab=1.27, sincos_cw=0.96, cexp=2.13, cexp_exact=2.13, cexp_tab=1.44, cexp_tab_exact=1.44),
     "slow": dict(cexp=0.68, cexp_exact=1.17, cexp_tab=0.80, cexp_tab_exact=1.12),
+    # the float64 restatement of the merge (two_sided.merge_chol) against mpmath on merge_cases(P): largest error in units
+    # U = 2^-53 kappa S over every family but rank 0 (derived bar) and the pivot at 4e-16 (widened allowance) ...
+    "merge": {2: 15.23, 3: 8.32, 4: 4.38, 5: 4.94, 6: 4.16, 7: 4.70},
+    # ... and on real_cases(P): largest error relative to the whole log-likelihood |l_a + l_b + merge|
+    "merge_real": {2: 1.75e-15, 3: 6.63e-9, 5: 1.67e-15, 7: 9.9e-16},
 }
 # What the project states: exp_neg_tab < 2.0 and cexp_step_tab < 3.6 (test_emu_core.py::test_table_math_accuracy), exp_neg and
 # sincos_cw < 2 (header of carma_math.h); cexp_step <= cexp_step_tab + 0.25 (the same test's relation read the other way).
@@ -711,3 +724,551 @@ def rng_refs():
         t8.put(i, tv, 1)
         tb[i] = float(16 * U53 * rad / den + 8 * U53 * abs(tv))
     return dict(uniform=uni, normal=z.freeze(), normal_bound=zb, t8=t8.freeze(), t8_bound=tb)
+
+
+# ---- (g) reciprocals ------------------------------------------------------------------------------------------------------
+RCP_RAW_BOUND = 2.0 ** -24                   # the project's figure is 2^-24.4 "(measured)" on another sample: 0.4 bit of room
+# recip() and rsqrt_pos(): "~1 ulp" / "e^3 ~ 1e-22 plus one rounding".  The host build of carma_core.h divides (0.5 units), so there
+# is no host maximum to add one unit to; the bar is a stated 2 units of 2^-53 |value|.
+RECIP_UNITS = 2.0
+
+
+@functools.lru_cache(None)
+def binade_sweep(kind, n=20000, seed=424242):
+    """Arguments over every binade whose result is a normal number (1 / x: 2^-1021 .. 2^1021, both signs; x^-1/2: every normal
+    positive x), mantissas: 1, the last one of the binade, the neighbours of 2 (where x^-1/2 changes its table half), and a random
+    sweep -- n values in all."""
+    rng = np.random.default_rng(seed + len(kind))
+    lo, hi = (-1021, 1021) if kind == "rcp" else (-1022, 1024)
+    ex = np.arange(lo, hi)
+    per = n // ex.size
+    rest = n - per * ex.size
+    e = np.r_[np.repeat(ex, per), rng.integers(lo, hi, rest)]
+    mant = rng.uniform(1.0, 2.0, e.size)
+    first = np.arange(0, per * ex.size, per)
+    mant[first] = 1.0
+    mant[first + 1] = np.nextafter(2.0, 0.0)
+    mant[first + 2] = np.nextafter(1.0, 2.0)
+    x = np.ldexp(mant, e)
+    if kind == "rcp":
+        x *= np.where(rng.random(x.size) < 0.5, -1.0, 1.0)
+    assert x.size == n and np.isfinite(x).all()
+    x.setflags(write=False)
+    return x
+
+
+@functools.lru_cache(None)
+def recip_refs(kind):
+    x = binade_sweep(kind)
+    ref = Ref(x.size)
+    for i, xi in enumerate(x):
+        v = 1 / MP.mpf(float(xi)) if kind == "rcp" else 1 / MP.sqrt(MP.mpf(float(xi)))
+        ref.put(i, v, abs(v) * U53)
+    return ref.freeze()
+
+
+# ---- (h) the merge of a two-sided evaluation (carma_pipew.h pipew_merge) ---------------------------------------------------
+# An evaluation is (Da, a, Db, beta): forward half  z | y_a ~ N(a, V + Da), backward half  u | y_b ~ N(beta, V^-1 + Db);
+# X = -Da, Y = -Db positive semidefinite, the eigenvalues of X Y in [0, 1).
+MPM = mp.mp.clone()
+MPM.dps = 120
+MERGE_ORDERS = (2, 3, 4, 5, 6, 7)
+
+
+def _proto():
+    import sys
+    d = os.path.join(HERE, "tools", "proto")
+    if d not in sys.path:
+        sys.path.insert(0, d)
+    import two_sided
+    return two_sided
+
+
+def lower_sym(Da):
+    """Da as the device reads it: the stored elements with row >= column, mirrored."""
+    L = np.tril(np.asarray(Da, dtype=np.float64))
+    return L + np.tril(L, -1).T
+
+
+def merge_pack(P, slots, data_fill=0.0):
+    """One wave of k_merge<P>: slots = two evaluations (or None: all zero) -> [64, P + 1].  Slot s: forward row 2 s, backward
+    row 2 s + 1; lane ND + j of the forward row carries column j of Da and -a_j, of the backward row column j of Db and -beta_j."""
+    ND = 16 - P
+    x = np.zeros((64, P + 1))
+    x[(np.arange(64) % 16) < ND] = data_fill
+    for s, ev in enumerate(slots):
+        if ev is None:
+            continue
+        Da, a, Db, beta = ev
+        for j in range(P):
+            x[32 * s + ND + j, :P] = Da[:, j]
+            x[32 * s + ND + j, P] = -a[j]
+            x[32 * s + 16 + ND + j, :P] = Db[:, j]
+            x[32 * s + 16 + ND + j, P] = -beta[j]
+    return x
+
+
+def run_merge(P, x):
+    """x [nblocks * 64, P + 1] -> [nblocks, 64, 2]: {acc.total(), the row pair's sum} per lane."""
+    x = _f64(x)
+    nb = x.shape[0] // 64
+    assert nb >= 1 and x.shape == (nb * 64, P + 1)
+    out = np.full((nb * 64, 2), -7.0)
+    launch(device().devprim_merge, P, nb, _ptr(x), _ptr(out))
+    return out.reshape(nb, 64, 2)
+
+
+def merge_result(P, out, blk, slot):
+    """-> (the evaluation's value: the pair sum in lane 0 of its forward row, the 32 lanes' words as uint64 [32, 2])."""
+    w = out[blk, 32 * slot:32 * slot + 32]
+    return float(w[0, 1]), np.ascontiguousarray(w).view(np.uint64)
+
+
+class MergeTruth(object):
+    """value (mpf, NaN where lambda_max >= 1), lam = lambda_max(X Y), kappa = 1 / (1 - lam), S = the sum of the magnitudes of
+    the terms, U = 2^-53 kappa S."""
+    __slots__ = ("value", "lam", "kappa", "S", "U")
+
+
+def _lam_max_mp(X, Y, XY):
+    """lambda_max(X Y): of the symmetric C^T X C where Y = C C^T is positive definite, else of X Y itself."""
+    M = MPM
+    P = X.rows
+    if not any(XY[i, j] != 0 for i in range(P) for j in range(P)):
+        return M.mpf(0)
+    try:
+        C_ = M.cholesky(Y)
+        return max(M.eigsy(C_.T * X * C_, eigvals_only=True))
+    except (ValueError, ZeroDivisionError):
+        return max(M.re(v) for v in M.eig(XY, left=False, right=False))
+
+
+def merge_truth(Da, a, Db, beta, units=True):
+    """The closed form of two_sided.merge (N = I - Da Db) at 120 digits, from the doubles as the device reads them.  units=False:
+    the value alone (NaN where det N <= 0)."""
+    M = MPM
+    P = len(a)
+    X = -M.matrix(lower_sym(Da).tolist())
+    Y = -M.matrix(np.asarray(Db, dtype=np.float64).tolist())
+    av, bv = M.matrix([float(v) for v in a]), M.matrix([float(v) for v in beta])
+    XY = X * Y
+    N = M.eye(P) - XY
+    out = MergeTruth()
+    out.lam = _lam_max_mp(X, Y, XY) if units else M.nan
+    LU, piv = M.LU_decomp(N)
+    det = M.mpf(1)
+    for i in range(P):
+        det *= LU[i, i] * (-1 if i < len(piv) and piv[i] != i else 1)
+    if (units and not out.lam < 1) or not det > 0:
+        out.value, out.kappa, out.S, out.U = M.nan, M.inf, M.inf, M.inf
+        return out
+    solve = lambda b_: M.U_solve(LU, M.L_solve(LU, b_, piv))   # noqa: E731
+    logdet = M.log(det)
+    x1 = solve(av)
+    x2 = solve(-(X * bv))                                     # N^-1 Da beta
+    dot = lambda p_, q_: sum(p_[i] * q_[i] for i in range(P))  # noqa: E731
+    out.value = -logdet / 2 + dot(bv, x1) + dot(bv, x2) / 2 - dot(Y * av, x1) / 2
+    if not units:
+        out.kappa = out.S = out.U = M.nan
+        return out
+    u = Y * av - bv
+    s2 = dot(u, solve(X * u))                                 # |C^-1 L^T u|^2 = u . N^-1 X u
+    out.kappa = 1 / (1 - out.lam)
+    out.S = abs(logdet) / 2 + sum(abs(bv[j] * av[j]) for j in range(P)) + \
+        sum(abs(av[i] * Y[i, j] * av[j]) for i in range(P) for j in range(P)) / 2 + abs(s2) / 2
+    out.U = M.mpf(U53) * out.kappa * out.S
+    return out
+
+
+def merge_err(got, truth):
+    """|got - truth| as an mpf; a truth of NaN wants NaN (0, else inf); a non-finite result of a finite truth is inf."""
+    if MPM.isnan(truth.value):
+        return MPM.mpf(0) if got != got else MPM.inf
+    if not np.isfinite(got):
+        return MPM.inf
+    return abs(MPM.mpf(float(got)) - truth.value)
+
+
+def merge_host(ev):
+    """The float64 restatement (two_sided.merge_chol: the device's algorithm) on what the device reads."""
+    Da, a, Db, beta = ev
+    with np.errstate(all="ignore"):
+        return float(_proto().merge_chol(lower_sym(Da), np.asarray(a, float), np.asarray(Db, float), np.asarray(beta, float)))
+
+
+def _sym_psd(rng, P, r=None):
+    B = rng.standard_normal((P, P if r is None else r))
+    M_ = B @ B.T
+    return np.tril(M_) + np.tril(M_, -1).T                    # symmetric bit for bit
+
+
+def _lam_max(X, Y):
+    w = np.linalg.eigvals(X @ Y).real
+    return float(w.max())
+
+
+def _scaled_y(rng, X, lam):
+    """A random positive semidefinite Y with lambda_max(X Y) = lam (to rounding); X = 0: any Y."""
+    P = X.shape[0]
+    Y = _sym_psd(rng, P)
+    top = _lam_max(X, Y)
+    return Y * (lam / top) if top > 0 else Y
+
+
+MERGE_LAMS = (0.3, 0.99, 1.0 - 1e-6)
+MERGE_DRAWS = 8
+
+
+def _embed(P, X2):
+    X = np.zeros((P, P))
+    X[:2, :2] = X2
+    return X
+
+
+@functools.lru_cache(None)
+def merge_cases(P):
+    """The synthetic families: [(family, evaluation)].  family "rank0" has the derived bar, "delta-small" the widened one (its
+    partner "delta-zero" is the same evaluation at delta = 0), every other one the measured factor HOST_MAX["merge"][P]."""
+    rng = np.random.default_rng(6100 + P)
+    cases = []
+    for r in range(P + 1):
+        for lam in MERGE_LAMS:
+            for _ in range(MERGE_DRAWS):
+                X = _sym_psd(rng, P, r)
+                Y = _scaled_y(rng, X, lam)
+                cases.append(("rank0" if r == 0 else "rank%d" % r, (-X, rng.standard_normal(P), -Y, rng.standard_normal(P))))
+    for lam in MERGE_LAMS:
+        for _ in range(2):
+            # every pivot a tie: a unit diagonal (a correlation matrix, scaled by exact powers of two) and 3 I
+            X = _sym_psd(rng, P)
+            d = 2.0 ** -np.round(0.5 * np.log2(np.diag(X)))
+            X = X * d[:, None] * d[None, :]
+            X = X / np.sqrt(np.outer(np.diag(X), np.diag(X)))
+            X = np.tril(X) + np.tril(X, -1).T
+            np.fill_diagonal(X, 1.0)
+            if np.linalg.eigvalsh(X).min() > 1e-3:
+                cases.append(("unit-diagonal", (-X, rng.standard_normal(P), -_scaled_y(rng, X, lam), rng.standard_normal(P))))
+            X = 3.0 * np.eye(P)
+            cases.append(("3I", (-X, rng.standard_normal(P), -_scaled_y(rng, X, lam), rng.standard_normal(P))))
+        # a pivot just above the rank cut (taken), just below it (either decision passes), and the same at delta = 0
+        a, beta = rng.standard_normal(P), rng.standard_normal(P)
+        Y = _scaled_y(rng, _embed(P, [[1.0, 1.0], [1.0, 1.0]]), lam)
+        for name, delta in (("delta-large", 4e-14), ("delta-small", 4e-16), ("delta-zero", 0.0)):
+            cases.append((name, (-_embed(P, [[1.0, 1.0], [1.0, 1.0 + delta]]), a, -Y, beta)))
+        # a diagonal entry at -1e-17 with a zero row and column
+        X = _sym_psd(rng, P, P - 1)
+        X[P - 1, :] = X[:, P - 1] = 0.0
+        X[P - 1, P - 1] = -1e-17
+        cases.append(("negative-diagonal", (-X, rng.standard_normal(P), -_scaled_y(rng, X, lam), rng.standard_normal(P))))
+    for _, ev in cases:
+        for arr in ev:
+            arr.setflags(write=False)
+    return tuple(cases)
+
+
+@functools.lru_cache(None)
+def merge_truths(P):
+    return tuple(merge_truth(*ev) for _, ev in merge_cases(P))
+
+
+def merge_allowance(P, factor):
+    """Per case of merge_cases(P): the allowed |result - truth| (float).  rank0: (P + 2) 2^-53 S -- the result is
+    beta.a - 1/2 a.Y a, P + 2 roundings of partial sums that S bounds.  delta-small: factor U + |truth(delta) - truth(0)|.
+    Otherwise factor U."""
+    cases, truths = merge_cases(P), merge_truths(P)
+    out = []
+    for i, (fam, _) in enumerate(cases):
+        t = truths[i]
+        if fam == "rank0":
+            out.append(float((P + 2) * U53 * t.S))
+        elif fam == "delta-small":
+            assert cases[i + 1][0] == "delta-zero"
+            out.append(float(factor * t.U + abs(t.value - truths[i + 1].value)))
+        else:
+            out.append(float(factor * t.U))
+    return np.array(out)
+
+
+def merge_measure(P, results):
+    """results: one value per case -> (largest |result - truth| / U over the families with the measured factor,
+    largest |result - truth| / ((P + 2) 2^-53 S) over rank 0, errors [n] as floats)."""
+    cases, truths = merge_cases(P), merge_truths(P)
+    err = np.array([float(merge_err(results[i], truths[i])) for i in range(len(cases))])
+    worst, worst0 = 0.0, 0.0
+    for i, (fam, _) in enumerate(cases):
+        if fam == "rank0":
+            worst0 = max(worst0, err[i] / float((P + 2) * U53 * truths[i].S))
+        elif fam != "delta-small":
+            worst = max(worst, err[i] / float(truths[i].U))
+    return worst, worst0, err
+
+
+# ---- inputs of the merge from real half filters
+REAL_ORDERS = ((2, 1), (5, 3), (7, 6))
+REAL_N = (6, 20, 41, 120)
+REAL_DRAWS = 8
+COINCIDENT = (3, 1, 120, 34, (17.05379556956296, 1.2281142449115867, 35.43706442791335, -5.014528819389739, -1.7473257300527083,
+                              -2.87620882248127, 18.963673587819525))     # test_state_with_nearly_coincident_real_roots
+
+
+def _halves(t, y, yerr, theta, p, q):
+    """(l_a, Da, a, l_b, Db, beta) of two_sided.loglik_two_sided at the device's split and meeting time."""
+    ts = _proto()
+    om, h, Vz, pairs = ts.real_model(theta, p, q)
+    n = t.size
+    m = (n + 1) // 2
+    yc, e = y - theta[2], theta[1] * yerr ** 2
+    c, s0 = Vz @ h, h @ Vz @ h
+    la, Da, a = ts.half_filter(om, pairs, p, h, c, s0, t[:m], yc[:m], e[:m], t[m - 1], False)
+    lb, Db, beta = ts.half_filter(om, pairs, p, c, h, s0, t[m:][::-1], yc[m:][::-1], e[m:][::-1], t[m - 1], True)
+    return la, Da, a, lb, Db, beta
+
+
+@functools.lru_cache(None)
+def real_cases(p):
+    """[(l_a + l_b, evaluation)] of order p: prior-like draws on irregular series of every length of REAL_N (and, at p = 3, the
+    state with two real roots 6e-4 apart)."""
+    from carma_pack_amd.synth import irregular_series, prior_like_theta
+    out = []
+    todo = []
+    for (pp, q) in REAL_ORDERS:
+        if pp == p:
+            rng = np.random.default_rng(9000 + p)
+            for n in REAL_N:
+                t, y, yerr = irregular_series(n, seed=50 + n)
+                k = 0
+                while k < REAL_DRAWS:
+                    todo.append((t, y, yerr, prior_like_theta(rng, p, q, t, y), q))
+                    k += 1
+    if p == COINCIDENT[0]:
+        t, y, yerr = irregular_series(COINCIDENT[2], seed=COINCIDENT[3])
+        todo.append((t, y, yerr, np.array(COINCIDENT[4]), COINCIDENT[1]))
+    for t, y, yerr, th, q in todo:
+        with np.errstate(all="ignore"):
+            la, Da, a, lb, Db, beta = _halves(t, y, yerr, th, p, q)
+        if not (np.isfinite(la + lb) and np.isfinite(Da).all() and np.isfinite(Db).all()):
+            continue
+        ev = (Da, a, Db, beta)
+        for arr in ev:
+            arr.setflags(write=False)
+        out.append((float(la + lb), ev))
+    return tuple(out)
+
+
+REAL_P = (2, 3, 5, 7)
+
+
+@functools.lru_cache(None)
+def real_truths(p):
+    return tuple(merge_truth(*ev, units=False) for _, ev in real_cases(p))
+
+
+def real_measure(p, results):
+    """Largest |result - truth| / |l_a + l_b + truth| over real_cases(p) (evaluations whose truth is NaN want NaN)."""
+    worst = 0.0
+    for i, (lab, _) in enumerate(real_cases(p)):
+        t = real_truths(p)[i]
+        e = merge_err(results[i], t)
+        worst = max(worst, float(e if MPM.isnan(t.value) else e / abs(lab + t.value)))
+    return worst
+
+
+REAL_FLOOR = 16 * U53                    # the P + 2 additions into a sum of the size of the whole log-likelihood
+
+
+# ---- (i) the window blocks (carma_win_asm.h, generated by tools/gen_win_asm.py) -------------------------------------------
+WIN_EPS_T = 2.0 ** -48                   # t = -G / m@j: v_rcp_f64 to 2^-24.4, one Newton step leaves (2^-24.4)^2, + two roundings
+RCP_REL = 2.0 ** -24.4
+
+
+def win_init_inputs(P, seed, nblocks=1):
+    """[nblocks * 64, 3 P + 2]: kn[P], nun, kk[P], nuF, hn[P], every lane its own values."""
+    rng = np.random.default_rng(seed)
+    x = rng.uniform(1.0, 2.0, (nblocks * 64, 3 * P + 2)) * np.where(rng.random((nblocks * 64, 3 * P + 2)) < 0.5, -1.0, 1.0)
+    return np.ldexp(x, rng.integers(-3, 4, x.shape))
+
+
+def run_win_init(P, x):
+    x = _f64(x)
+    nb = x.shape[0] // 64
+    assert nb >= 1 and x.shape == (nb * 64, 3 * P + 2)
+    out = np.full((nb * 64, P + 1), np.nan)
+    launch(device().devprim_win_init, P, nb, _ptr(x), _ptr(out))
+    return out
+
+
+def win_init_ref(P, x):
+    """WinAsm<P>::init on one row x [16, 3 P + 2] -> [16, P + 1]: the FMA chain in the generator's order (s outer, r inner);
+    kk_r and nuF come from the virtual lane ND + s."""
+    ND = 16 - P
+    out = np.empty((16, P + 1))
+    for l in range(16):
+        kn, nun = [x[l, r] for r in range(P)], x[l, P]
+        for s in range(P):
+            hs = x[l, 2 * P + 2 + s]
+            for r in range(P):
+                kn[r] = fma(x[ND + s, P + 1 + r], hs, kn[r])
+            nun = fma(x[ND + s, 2 * P + 1], hs, nun)
+        out[l, :P], out[l, P] = kn, nun
+    return out
+
+
+def win_chunk_inputs(P, seed, noise=1.0, gain=0.0, nblocks=1):
+    """[nblocks * 64, 2 P + 2]: kk[P], hh[P], m, nu of a chunk as start() leaves it, four independent rows per wave: data lane j
+    h_j random, kk_j = S h_j + c_j, m_j = e_j + h_j . kk_j, nu_j random; virtual lane s: hh = e_s, kk = column s of S (positive
+    semidefinite), m = 1 + S_ss, nu = -z_s.  noise: the size of e_j (small: the pivots cancel); gain: the size of V in c_j = V h_j
+    (V positive semidefinite, so that the chunk's covariance H (S + V) H^T + diag(e) is positive definite: every pivot > 0)."""
+    ND = 16 - P
+    rng = np.random.default_rng(seed)
+    x = np.zeros((nblocks * 64, 2 * P + 2))
+    for row in range(nblocks * 4):
+        A = rng.standard_normal((P, P))
+        S = A @ A.T / P
+        S = np.tril(S) + np.tril(S, -1).T
+        B = rng.standard_normal((P, P))
+        V = gain * (B @ B.T) / P
+        V = np.tril(V) + np.tril(V, -1).T
+        o = x[16 * row:16 * row + 16]
+        for j in range(ND):
+            h = rng.standard_normal(P)
+            kk = S @ h + V @ h
+            o[j, :P], o[j, P:2 * P] = kk, h
+            o[j, 2 * P] = noise * rng.uniform(0.5, 1.5) + h @ kk
+            o[j, 2 * P + 1] = rng.standard_normal()
+        for s in range(P):
+            o[ND + s, :P] = S[:, s]
+            o[ND + s, P + s] = 1.0
+            o[ND + s, 2 * P] = 1.0 + S[s, s]
+            o[ND + s, 2 * P + 1] = rng.standard_normal()
+    return x
+
+
+def win_neutral_inputs(P, seed):
+    """A chunk of neutral slots: data lanes hh = kk = 0, m = 1, nu = 0; the virtual lanes as in win_chunk_inputs."""
+    ND = 16 - P
+    x = win_chunk_inputs(P, seed)
+    data = (np.arange(64) % 16) < ND
+    x[data] = 0.0
+    x[data, 2 * P] = 1.0
+    return x
+
+
+WIN_FILL = -12345.0                      # what a lane that stores nothing leaves in the output array
+
+
+def run_win_chunk(P, x, rows=None):
+    """-> (out [n, P + 4]: kk[P], mA, mB, nuA, nuB; marker [n]).  rows: the call under `if (row active)`, bit q = row q of every wave."""
+    x = _f64(x)
+    nb = x.shape[0] // 64
+    assert nb >= 1 and x.shape == (nb * 64, 2 * P + 2)
+    out = np.full((nb * 64, P + 4), WIN_FILL)
+    marker = np.zeros(nb * 64, dtype=np.int32)
+    if rows is None:
+        launch(device().devprim_win_chunk, P, nb, _ptr(x), _ptr(out), _ptr(marker, _ip))
+    else:
+        launch(device().devprim_win_chunk_masked, P, nb, int(rows), _ptr(x), _ptr(out), _ptr(marker, _ip))
+    return out, marker
+
+
+def win_chunk_truth(P, x):
+    """The elimination of one row x [16, 2 P + 2] in mpmath, every lane and register as the block leaves it:
+        for j = 0 .. ND-1, in the lanes l >= j:  G = sum_r kk_r@j hh_r ;  t = -G / m@j ;  m' = m + G t ;  nu' = nu + nu@j t ;
+                                                 kk_r += kk_r@j t          (m, nu: pivot j reads A / B for j even / odd, writes the other)
+    with a running bound of the device's error per register, to first order in the rounding unit u = 2^-53: G takes P roundings
+    (each at most u times a partial sum, which the sum of the magnitudes bounds), the updates of m, nu and kk_r one each, t carries
+    the relative error WIN_EPS_T; errors of the operands go through the derivatives' magnitudes.
+    -> (val, err): [16, P + 4] object arrays of mpf, columns as run_win_chunk's."""
+    ND = 16 - P
+    f = lambda v: MP.mpf(float(v))                             # noqa: E731
+    u, et_rel = MP.mpf(U53), MP.mpf(WIN_EPS_T)
+    K = [[f(x[l, r]) for r in range(P)] for l in range(16)]
+    eK = [[MP.mpf(0)] * P for _ in range(16)]
+    H = [[f(x[l, P + r]) for r in range(P)] for l in range(16)]
+    M_ = [[f(x[l, 2 * P]) for l in range(16)] for _ in range(2)]
+    NU = [[f(x[l, 2 * P + 1]) for l in range(16)] for _ in range(2)]
+    eM = [[MP.mpf(0)] * 16 for _ in range(2)]
+    eNU = [[MP.mpf(0)] * 16 for _ in range(2)]
+    for j in range(ND):
+        cur, alt = j & 1, 1 - (j & 1)
+        kj, ekj = list(K[j]), list(eK[j])
+        mj, emj, nj, enj = M_[cur][j], eM[cur][j], NU[cur][j], eNU[cur][j]
+        for l in range(j, 16):
+            terms = [kj[r] * H[l][r] for r in range(P)]
+            G = sum(terms)
+            eG = sum(abs(H[l][r]) * ekj[r] for r in range(P))
+            eG += P * u * (sum(abs(v) for v in terms) + eG)
+            t = -G / mj
+            et = eG / abs(mj) + abs(G) * emj / (mj * mj)
+            et += et_rel * (abs(t) + et)
+            mn = M_[cur][l] + G * t
+            e = eM[cur][l] + abs(t) * eG + abs(G) * et + eG * et
+            M_[alt][l], eM[alt][l] = mn, e + u * (abs(mn) + e)
+            nn = NU[cur][l] + nj * t
+            e = eNU[cur][l] + abs(t) * enj + abs(nj) * et + enj * et
+            NU[alt][l], eNU[alt][l] = nn, e + u * (abs(nn) + e)
+            for r in range(P):
+                kn = K[l][r] + kj[r] * t
+                e = eK[l][r] + abs(t) * ekj[r] + abs(kj[r]) * et + ekj[r] * et
+                K[l][r], eK[l][r] = kn, e + u * (abs(kn) + e)
+    val = np.empty((16, P + 4), dtype=object)
+    err = np.empty((16, P + 4), dtype=object)
+    for l in range(16):
+        val[l, :P], err[l, :P] = K[l], eK[l]
+        val[l, P:] = [M_[0][l], M_[1][l], NU[0][l], NU[1][l]]
+        err[l, P:] = [eM[0][l], eM[1][l], eNU[0][l], eNU[1][l]]
+    return val, err
+
+
+def win_chunk_f64(P, x, newton=True):
+    """The instruction sequence of WinAsm<P>::chunk on one row in float64 (correctly rounded FMAs), with v_rcp_f64 replaced by
+    the division moved by the full 2^-24.4 the project states for it, the sign alternating.  newton=False: without the Newton
+    step folded into t (a wrong block, for the test of the bound).  -> [16, P + 4]."""
+    ND = 16 - P
+    K = [[float(x[l, r]) for r in range(P)] for l in range(16)]
+    H = [[float(x[l, P + r]) for r in range(P)] for l in range(16)]
+    M_ = [[float(x[l, 2 * P]) for l in range(16)] for _ in range(2)]
+    NU = [[float(x[l, 2 * P + 1]) for l in range(16)] for _ in range(2)]
+    for j in range(ND):
+        cur, alt = j & 1, 1 - (j & 1)
+        kj, rb, bnu = list(K[j]), M_[cur][j], NU[cur][j]
+        for l in range(j, 16):
+            G = 0.0
+            for r in range(P):
+                G = fma(kj[r], H[l][r], G)
+            r0 = (1.0 / rb) * (1.0 + (RCP_REL if (j + l) & 1 else -RCP_REL))
+            e = fma(-rb, r0, 1.0)
+            t = G * -r0
+            if newton:
+                t = fma(t, e, t)
+            M_[alt][l] = fma(G, t, M_[cur][l])
+            NU[alt][l] = fma(bnu, t, NU[cur][l])
+            for r in range(P):
+                K[l][r] = fma(kj[r], t, K[l][r])
+    out = np.empty((16, P + 4))
+    for l in range(16):
+        out[l, :P] = K[l]
+        out[l, P:] = [M_[0][l], M_[1][l], NU[0][l], NU[1][l]]
+    return out
+
+
+def win_checked(P):
+    """(lane, column) of what the tests hold to the truth: each data lane's final variance and innovation (mA / nuA for an even
+    lane, mB / nuB for an odd one), the virtual lanes' kk (the columns of S) and their nu in the register the last pivot wrote."""
+    ND = 16 - P
+    cells = []
+    for j in range(ND):
+        cells += [(j, P + (j & 1)), (j, P + 2 + (j & 1))]
+    for s in range(P):
+        cells += [(ND + s, r) for r in range(P)] + [(ND + s, P + 2 + (ND & 1))]
+    return cells
+
+
+def win_chunk_worst(P, got, val, err):
+    """Largest |got - truth| / bound over win_checked(P) (a bound of 0 wants the exact value)."""
+    worst = 0.0
+    for l, c in win_checked(P):
+        d = abs(MP.mpf(float(got[l, c])) - val[l, c])
+        if not np.isfinite(got[l, c]):
+            return np.inf
+        worst = max(worst, float(d / err[l, c]) if err[l, c] > 0 else (0.0 if d == 0 else np.inf))
+    return worst
