@@ -150,6 +150,8 @@ mpsd_band = _lib.mpsd_band
 chain_diag = _lib.chain_diag
 simulate_cond_carma = _lib.simulate_cond_carma
 simulate_cond_car1 = _lib.simulate_cond_car1
+smooth_carma = _lib.smooth_carma
+smooth_car1 = _lib.smooth_car1
 
 
 def _pop_max_stdev(y):
@@ -296,6 +298,14 @@ class _KalmanBase(object):
             seed = int(np.random.randint(0, 2 ** 62))
         return self._simulate_cond(_arr(times), int(npaths), int(seed))
 
+    def SmoothBatch(self, times):
+        """Extension: what PredictBatch returns, (mean, variance) of the process at `times` given the series, from ONE forward
+        and ONE backward pass over the merged grid of data and requested times (carma_smooth_*) instead of a filter run per
+        time: O((n + M) p^2) against O(M n p^2).  Equal to PredictBatch to rounding, not to the bit; PredictBatch stays the
+        default route of Predict / CarmaSample.predict."""
+        m, v = self._smooth(_arr(times))
+        return m[0], v[0]
+
 
 class KalmanFilter1(_KalmanBase):
     """KalmanFilter1(time, y, yerr[, sigsqr, omega]) (wrapper :83-90; kfilter.hpp:222-245)."""
@@ -323,6 +333,11 @@ class KalmanFilter1(_KalmanBase):
 
     def _simulate(self, times, seed):
         return _lib.simulate_car1(times, self._sigsqr, self._omega, 1, seed)[0]
+
+    def _smooth(self, times):
+        if self._sigsqr is None or self._omega is None:
+            raise RuntimeError("KalmanFilter1: sigsqr and omega are not set")
+        return _lib.smooth_car1(self._t, self._y, self._e, [float(self._sigsqr)], [float(self._omega)], None, times)
 
     def _simulate_cond(self, times, npaths, seed):
         if self._sigsqr is None or self._omega is None:
@@ -360,6 +375,12 @@ class KalmanFilterp(_KalmanBase):
 
     def _simulate(self, times, seed):
         return _lib.simulate_carma(times, self._sigsqr, self._omega, self._ma, 1, seed)[0]
+
+    def _smooth(self, times):
+        if self._sigsqr is None or self._omega is None or self._ma is None:
+            raise RuntimeError("KalmanFilterp: sigsqr, omega and ma_coefs are not set")
+        return _lib.smooth_carma(self._t, self._y, self._e, [float(self._sigsqr)], self._omega[None, :], self._ma[None, :], None,
+                                 times)
 
     def _simulate_cond(self, times, npaths, seed):
         if self._sigsqr is None or self._omega is None or self._ma is None:

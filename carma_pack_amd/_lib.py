@@ -137,6 +137,7 @@ def _load():
     L.carma_mle_batched_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                        C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]
+    L.carma_msmooth.argtypes = [C.c_void_p, _ip, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, C.POINTER(C.c_long), _dp, _dp, _ip]
     L.carma_mpt_create.argtypes = [C.c_void_p, _ip, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_uint64]
     L.carma_mpt_start.argtypes = [C.c_void_p, _dp]
     L.carma_mpt_set_chains.argtypes = [C.c_void_p, _dp, _dp]
@@ -178,6 +179,10 @@ def _load():
                                             C.c_uint64, C.c_uint, _dp, _dp, _dp, _ip, _ip, C.c_int]
     L.carma_simulate_cond_car1.argtypes = [_dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_uint64, C.c_uint,
                                            _dp, _dp, _dp, _ip, _ip, C.c_int]
+    L.carma_smooth_carma.argtypes = [_dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, C.c_int,
+                                     _dp, _dp, _dp, _dp, _ip, _ip, C.c_int]
+    L.carma_smooth_car1.argtypes = [_dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
+                                    C.c_int]
     L.carma_sigma_noise_batch.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int]
     L.carma_psd_band.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int]
     L.carma_mpsd_band.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_long), C.c_int, _dp, C.c_int, _dp, C.c_int, _dp,
@@ -229,14 +234,14 @@ EXPORTS = [
     "carma_ctx_n", "carma_ctx_dim", "carma_ctx_get_data", "carma_ctx_get_prior", "carma_ctx_set_prior",
     "carma_logdensity_batch", "carma_logdensity_batch_dev", "carma_logdensity_kernel_name", "carma_logprior", "carma_mle_batched", "carma_kfilter_carma", "carma_kfilter_batch_carma",
     "carma_kfilter_car1", "carma_predict_carma", "carma_predict_car1", "carma_normalize_roots", "carma_kf_create_carma", "carma_kf_create_car1",
-    "carma_kf_destroy", "carma_kf_n", "carma_kf_filter", "carma_kf_predict", "carma_simulate_carma", "carma_simulate_car1", "carma_simulate_cond_carma", "carma_simulate_cond_car1", "carma_sigma_noise_batch", "carma_psd_band", "carma_pt_run", "carma_pt_create", "carma_pt_shard", "carma_pt_bind_state",
+    "carma_kf_destroy", "carma_kf_n", "carma_kf_filter", "carma_kf_predict", "carma_simulate_carma", "carma_simulate_car1", "carma_simulate_cond_carma", "carma_simulate_cond_car1", "carma_smooth_carma", "carma_smooth_car1", "carma_sigma_noise_batch", "carma_psd_band", "carma_pt_run", "carma_pt_create", "carma_pt_shard", "carma_pt_bind_state",
     "carma_pt_start", "carma_pt_set_chains", "carma_pt_get_chains", "carma_pt_iterate", "carma_pt_sample",
     "carma_pt_stats", "carma_pt_iterations_done", "carma_comm_unique_id", "carma_comm_create", "carma_comm_destroy",
     "carma_comm_rank", "carma_comm_size", "carma_pt_iterate_sharded", "carma_pt_sample_sharded", "carma_pt_boundary_stats",
     "carma_pt_boundary_check", "carma_pt_sweep", "carma_pt_kernel_in_use", "carma_pt_row_pipeline", "carma_pt_debug_draws", "carma_pt_get_factor",
     "carma_pt_set_factor", "carma_tune_set", "carma_mctx_create", "carma_mctx_destroy", "carma_mctx_nseries", "carma_mctx_dim",
     "carma_mctx_n", "carma_mctx_get_data", "carma_mctx_get_prior", "carma_mlogdensity_batch", "carma_mlogdensity_kernel_name",
-    "carma_mle_batched_ms", "carma_mkfilter", "carma_mpredict", "carma_mpt_create", "carma_mpt_start", "carma_mpt_set_chains",
+    "carma_mle_batched_ms", "carma_mkfilter", "carma_mpredict", "carma_msmooth", "carma_mpt_create", "carma_mpt_start", "carma_mpt_set_chains",
     "carma_mpt_get_chains", "carma_mpt_get_factor", "carma_mpt_set_factor", "carma_mpt_iterate", "carma_mpt_sample",
     "carma_mpt_stats", "carma_mpt_iterations_done", "carma_mpt_logdensity", "carma_mpt_kernel_name", "carma_mpt_run",
     "carma_mpsd_band", "carma_mpsd_fused_max", "carma_mpsd_freq_tile", "carma_chain_diag", "carma_chain_diag_dmax", "carma_chain_diag_kernel_ms",
@@ -244,7 +249,7 @@ EXPORTS = [
 
 
 def tune_set(name, value):
-    """Move a launch-shape switch ("WIN_ROWS", "WIN2_EVALS", "PT_ROW_WIN", "CSIM_CHUNK_PATHS": carma_tune_set; measurements and
+    """Move a launch-shape switch ("WIN_ROWS", "WIN2_EVALS", "PT_ROW_WIN", "CSIM_CHUNK_PATHS", "SMOOTH_CHUNK_MODELS": carma_tune_set; measurements and
     parity tests).
     value None: back to the library's default."""
     check(lib.carma_tune_set(str(name).encode(), -2 ** 63 if value is None else int(value)), "carma_tune_set")
@@ -252,7 +257,7 @@ def tune_set(name, value):
 
 def tune_reset():
     """Every switch back to what the environment said when the library read it (CARMA_TUNE_<name>), or to the default."""
-    for name in ("WIN_ROWS", "WIN2_EVALS", "PT_ROW_WIN", "CSIM_CHUNK_PATHS"):
+    for name in ("WIN_ROWS", "WIN2_EVALS", "PT_ROW_WIN", "CSIM_CHUNK_PATHS", "SMOOTH_CHUNK_MODELS"):
         e = os.environ.get("CARMA_TUNE_" + name)
         tune_set(name, None if e is None else int(e))
 
@@ -784,6 +789,30 @@ class MultiContext:
                              % np.flatnonzero(sing)[:8].tolist())
         return [pm[toff[i]:toff[i + 1]] for i in range(M)], [pv[toff[i]:toff[i + 1]] for i in range(M)]
 
+    def smooth(self, which, sigsqr, roots, ma, times, mu=None, return_singular=False):
+        """The interpolated light curve of M items in one call (carma_msmooth): arguments and return values as predict, the
+        numbers those of predict to rounding -- but from ONE forward and ONE backward pass over an item's series and times
+        (O((n + M_i) p^2) per item instead of O(M_i n p^2)): the route for dense curves.  Items that share a series and a list
+        of times share waves; an item's outputs have the bits smooth_carma / smooth_car1 gives for it on its series alone."""
+        M, w, sig, om, ma_, nma, mu_ = self._items(which, sigsqr, roots, ma, mu, "MultiContext.smooth")
+        times = [as_f64(np.atleast_1d(t)).ravel() for t in times]
+        if len(times) != M:
+            raise ValueError("MultiContext.smooth: times must hold one array per item (%d), got %d" % (M, len(times)))
+        toff = np.zeros(M + 1, dtype=np.int64)
+        toff[1:] = np.cumsum([t.size for t in times])
+        tp = as_f64(np.concatenate(times)) if toff[-1] else np.zeros(1)
+        pm, pv = np.empty(max(int(toff[-1]), 1)), np.empty(max(int(toff[-1]), 1))
+        sing = np.zeros(M, dtype=np.int32)
+        check(lib.carma_msmooth(self._h, w.ctypes.data_as(_ip), M, ptr(sig), ptr(om), ptr(ma_), nma,
+                                ptr(mu_) if mu_ is not None else None, ptr(tp), toff.ctypes.data_as(C.POINTER(C.c_long)), ptr(pm),
+                                ptr(pv), sing.ctypes.data_as(_ip)), "carma_msmooth")
+        if return_singular:
+            return ([pm[toff[i]:toff[i + 1]] for i in range(M)], [pv[toff[i]:toff[i + 1]] for i in range(M)], sing.astype(bool))
+        if sing.any():
+            raise CarmaError("KalmanFilterp: singular eigenvector matrix (solve failed) for item(s) %s"
+                             % np.flatnonzero(sing)[:8].tolist())
+        return [pm[toff[i]:toff[i + 1]] for i in range(M)], [pv[toff[i]:toff[i + 1]] for i in range(M)]
+
     def mle_batched(self, x0, which, lo, hi, maxiter=2000, mem=8, ftol=2.220446049250313e-09, gtol=1e-5, fd_step=1e-6,
                     ignore_prior=True):
         """carma_mle_batched_ms: Context.mle_batched with start i on series which[i] and its own box lo[i], hi[i] ([B, d],
@@ -1051,6 +1080,63 @@ def simulate_cond_car1(time, y, yerr, sigsqr, omega, mu, tsim, seed=0, path0=0, 
         raise ValueError("simulate_cond_car1: sigsqr and omega must describe the same number of paths")
     return _simulate_cond(lib.carma_simulate_cond_car1, "carma_simulate_cond_car1", time, y, yerr, K,
                           (K, ptr(sig), ptr(om)), mu, tsim, seed, path0, return_parts, return_singular, device)
+
+
+def _smooth(call, what, time, y, yerr, K, model_args, mu, tout, band, return_singular, device):
+    time, y, yerr = as_f64(time), as_f64(y), as_f64(yerr)
+    tp = as_f64(np.atleast_1d(tout))
+    mu_ = None if mu is None else as_f64(np.atleast_1d(mu))
+    if mu_ is not None and mu_.size != K:
+        raise ValueError("%s: mu must have one entry per model" % what)
+    if band not in (False, True, "only"):
+        raise ValueError("%s: band must be False, True or 'only'" % what)
+    M = tp.size
+    samples = band != "only"
+    mean = np.empty((K, M)) if samples else None
+    var = np.empty((K, M)) if samples else None
+    bm = np.empty(M) if band else None
+    bv = np.empty(M) if band else None
+    sing = np.zeros(K, dtype=np.int32)
+    nout = C.c_int(0)
+    rc = call(ptr(time), ptr(y), ptr(yerr), time.size, *model_args, ptr(mu_) if mu_ is not None else None, ptr(tp), M,
+              ptr(mean) if samples else None, ptr(var) if samples else None, ptr(bm) if band else None,
+              ptr(bv) if band else None, sing.ctypes.data_as(_ip), C.byref(nout), default_device() if device is None else device)
+    check(rc, what)
+    sing = sing.astype(bool)
+    if sing.any() and not return_singular:
+        raise CarmaError("%s: repeated AR root (singular eigenvector matrix) in model %d" % (what, int(np.argmax(sing))))
+    res = ((mean, var) if samples else ()) + ((bm, bv) if band else ()) + ((sing,) if return_singular else ())
+    return res
+
+
+def smooth_carma(time, y, yerr, sigsqr, omega, ma, mu, tout, band=False, return_singular=False, device=None):
+    """The interpolated light curve at `tout` under K models at once, in ONE forward and ONE backward pass over the series per
+    model (carma_smooth_carma): model k = (sigsqr[k], omega[k] complex [p], ma[k], mu[k]; mu None: 0)
+    -> (mean [K][M], var [K][M]) in the order of tout: what predict_carma gives per model, for O((n + M) p^2) instead of
+    O(M n p^2).  band=True: also (band_mean [M], band_var [M]), the moment-matched Gaussian mixture over the models that are not
+    singular; band="only": just those two (the K x M arrays never leave the device).  return_singular: also the flags [K] of
+    models with a repeated AR root (otherwise such a model raises); a flagged model is left out of the band.  The variance is
+    returned as computed (a difference: see include/carma_mi355.h), never clipped."""
+    omega = np.atleast_2d(np.asarray(omega, dtype=complex))
+    K, p = omega.shape
+    om = as_f64(np.stack([omega.real, omega.imag], axis=-1))
+    ma = as_f64(np.atleast_2d(ma))
+    sig = as_f64(np.atleast_1d(sigsqr))
+    if ma.shape[0] != K or sig.size != K:
+        raise ValueError("smooth_carma: sigsqr, omega and ma must describe the same number of models")
+    return _smooth(lib.carma_smooth_carma, "carma_smooth_carma", time, y, yerr, K, (p, K, ptr(sig), ptr(om), ptr(ma), ma.shape[1]),
+                   mu, tout, band, return_singular, device)
+
+
+def smooth_car1(time, y, yerr, sigsqr, omega, mu, tout, band=False, return_singular=False, device=None):
+    """smooth_carma for CAR(1) models: sigsqr [K], omega [K] = 1 / tau (carma_smooth_car1)."""
+    sig = as_f64(np.atleast_1d(sigsqr))
+    om = as_f64(np.atleast_1d(omega))
+    K = sig.size
+    if om.size != K:
+        raise ValueError("smooth_car1: sigsqr and omega must describe the same number of models")
+    return _smooth(lib.carma_smooth_car1, "carma_smooth_car1", time, y, yerr, K, (K, ptr(sig), ptr(om)), mu, tout, band,
+                   return_singular, device)
 
 
 def sigma_noise_batch(ar_roots, ma_coefs, var, device=None):

@@ -542,6 +542,48 @@ class CarmaSample(MCMCSample):
         m, v = kf.PredictBatch(np.atleast_1d(time))
         return (m[0] + mu, v[0]) if scalar else (m + mu, v)
 
+    def smooth(self, time, bestfit="map"):
+        """predict(time, bestfit) by the one-pass smoother: the same expected value and variance (to rounding) from ONE forward
+        and ONE backward pass over the data and the requested times, O((n + M) p^2), where predict filters the series once per
+        time, O(M n p^2).  predict stays the default, and for ONE model it is also the faster route on an MI355X at every M
+        measured (tools/smooth_probe.py, profiles/smooth/README.md; CARMA(5,3), n = 270: 0.28 ms for any M <= 1000 against 0.6
+        ms at M = 64, 2 ms at M = 1000 and 6 ms at M = 4000): its M filter runs are M lane groups side by side on an otherwise
+        empty chip, the smoother is one wave's serial chain of 2 (n + M) steps.  The crossing lies where MANY models are smoothed
+        at once -- predict_band, MultiContext.smooth, smooth_carma: with 256 models the smoother is ahead from M ~ 256 (2.5 x at M
+        = 1000), with 1024 models at every M (2 x at M = 64, 6 x at M = 1000; n = 3000, M = 1000: 7 x).  The variance is returned
+        as computed -- a difference that can come out <= 0 by rounding where ysig is tiny against the process.
+        Returns (yhat, yhat_var)."""
+        scalar = np.isscalar(time)
+        kf, mu = self.makeKalmanFilter(bestfit)
+        m, v = kf.SmoothBatch(np.atleast_1d(time))
+        return (m[0] + mu, v[0]) if scalar else (m + mu, v)
+
+    def _smooth_models(self, sigsqr, mu, rest, time, band):
+        return carmcmcLib.smooth_carma(self.time, self.y, self.ysig, sigsqr, rest[0], rest[1], mu, time, band=band,
+                                       return_singular=True)
+
+    def predict_band(self, time, nsamples=None, seed=None, return_samples=False):
+        """The interpolated light curve MARGINALISED over the posterior samples instead of under one point estimate: per time the
+        mean and variance of the equal-weight mixture of the samples' predictive distributions,
+            mean = (1/K) sum_k m_k,    var = (1/K) sum_k (v_k + (m_k - mean)^2),
+        every sample smoothed in one pass and the mixture formed on the device (carma_smooth_*).  What the reference's users
+        loop `sample.predict(time, bestfit=i)` for.  nsamples: use that many samples -- evenly spaced as plot_power_spectrum
+        picks them, or, with a seed, drawn without replacement from np.random.RandomState(seed); None: all.  Samples with a
+        repeated AR root are left out.  Returns (mean, var); return_samples: also the K x M means and variances of the samples
+        and their indices."""
+        time = np.atleast_1d(np.asarray(time, dtype=float))
+        nall = self._samples["sigma"].shape[0]
+        if seed is not None and nsamples is not None and nsamples < nall:
+            index = np.sort(np.random.RandomState(seed).choice(nall, int(nsamples), replace=False))
+        else:
+            index = self._subsample(nsamples, nall)
+        sigsqr, mu, rest = self._path_models(index)
+        res = self._smooth_models(sigsqr, mu, rest, time, True if return_samples else "only")
+        if return_samples:
+            m, v, bm, bv, _ = res
+            return bm, bv, m, v, index
+        return res[0], res[1]
+
     def simulate(self, time, bestfit="map"):
         """Random draw of the process at `time` conditional on the data (reference :807-837)."""
         kf, mu = self.makeKalmanFilter(bestfit)
@@ -624,6 +666,9 @@ class Car1Sample(CarmaSample):
 
     def _simulate_cond(self, sigsqr, mu, omega, time, seed):
         return carmcmcLib.simulate_cond_car1(self.time, self.y, self.ysig, sigsqr, omega, mu, time, seed=seed)
+
+    def _smooth_models(self, sigsqr, mu, omega, time, band):
+        return carmcmcLib.smooth_car1(self.time, self.y, self.ysig, sigsqr, omega, mu, time, band=band, return_singular=True)
 
     # (the spectrum sigma^2 / (omega^2 + (2 pi f)^2) of the reference (:1004-1013) is the general formula with
     # alpha(s) = s + omega, delta = 1 -- the arrays generate_from_trace stores -- so CarmaSample's device path serves it)
@@ -1076,6 +1121,22 @@ class CarmaModelSet(object):
         mean, var = [None] * self.nseries, [None] * self.nseries
         for (p, q), (idx, sig, roots, ma, mu) in self._fit_items(fits, orders).items():
             pm, pv = self.context(p, q).predict(idx, sig, roots, ma, [tlist[s] for s in idx], mu=mu)
+            for k, s in enumerate(idx):
+                mean[s], var[s] = pm[k], pv[k]
+        return mean, var
+
+    def smooth(self, times, fits, orders=None):
+        """predict(times, fits, orders) by the one-pass smoother (CarmaSample.smooth of every series at its fitted model;
+        MultiContext.smooth): arguments and return values as predict, one call per order present."""
+        if isinstance(times, (list, tuple)) and len(times) and not np.isscalar(times[0]):
+            tlist = [np.atleast_1d(np.asarray(t, dtype=float)).ravel() for t in times]
+            if len(tlist) != self.nseries:
+                raise ValueError("times must be one array, or one per series (%d), got %d" % (self.nseries, len(tlist)))
+        else:
+            tlist = [np.atleast_1d(np.asarray(times, dtype=float)).ravel()] * self.nseries
+        mean, var = [None] * self.nseries, [None] * self.nseries
+        for (p, q), (idx, sig, roots, ma, mu) in self._fit_items(fits, orders).items():
+            pm, pv = self.context(p, q).smooth(idx, sig, roots, ma, [tlist[s] for s in idx], mu=mu)
             for k, s in enumerate(idx):
                 mean[s], var[s] = pm[k], pv[k]
         return mean, var

@@ -704,7 +704,7 @@ static long p3l_max_rows()
 enum class LdShape { P3L, PC1, PC2, PLAIN1, PLAIN4, LANE, LPC, WIN, WIN2 };
 // The launch-shape switches (carma_launch.h): environment read once, atomics afterwards.
 static const char* const TUNE_NAMES[TUNE_COUNT] = {"CARMA_TUNE_WIN_ROWS", "CARMA_TUNE_WIN2_EVALS", "CARMA_TUNE_PT_ROW_WIN",
-                                                    "CARMA_TUNE_CSIM_CHUNK_PATHS"};
+                                                    "CARMA_TUNE_CSIM_CHUNK_PATHS", "CARMA_TUNE_SMOOTH_CHUNK_MODELS"};
 static std::atomic<long> g_tune[TUNE_COUNT];
 static std::atomic<int> g_tune_init{0};
 static void tune_init()

@@ -22,10 +22,11 @@ int device_cus();
 // first launch asks (CARMA_TUNE_WIN_ROWS, CARMA_TUNE_WIN2_EVALS, CARMA_TUNE_PT_ROW_WIN), held in atomics, and moved afterwards through
 // carma_tune_set only -- no getenv() in the launch path (it raced with setenv() in multi-threaded callers).  TUNE_UNSET: the default.
 // CARMA_TUNE_CSIM_CHUNK_PATHS: paths per chunk of the conditional simulation (carma_csim.hip; 0 or unset: as many as its scratch cap holds).
-enum { TUNE_WIN_ROWS = 0, TUNE_WIN2_EVALS = 1, TUNE_PT_ROW_WIN = 2, TUNE_CSIM_CHUNK_PATHS = 3, TUNE_COUNT = 4 };
+// CARMA_TUNE_SMOOTH_CHUNK_MODELS: models per chunk of the one-pass smoother (carma_smooth.hip; 0 or unset: as many whole waves as its scratch cap holds).
+enum { TUNE_WIN_ROWS = 0, TUNE_WIN2_EVALS = 1, TUNE_PT_ROW_WIN = 2, TUNE_CSIM_CHUNK_PATHS = 3, TUNE_SMOOTH_CHUNK_MODELS = 4, TUNE_COUNT = 5 };
 constexpr long TUNE_UNSET = -0x7fffffffffffffffL - 1;
 long tune_get(int which);                    // TUNE_UNSET or the override
-int tune_set(const char* name, long value);  // "WIN_ROWS" / "WIN2_EVALS" / "PT_ROW_WIN" / "CSIM_CHUNK_PATHS" (or the full CARMA_TUNE_ name); 0 or -1
+int tune_set(const char* name, long value);  // "WIN_ROWS" / "WIN2_EVALS" / "PT_ROW_WIN" / "CSIM_CHUNK_PATHS" / "SMOOTH_CHUNK_MODELS" (or the full CARMA_TUNE_ name); 0 or -1
 
 // repeated_dt: a good part of the series' time steps equal their predecessor (regular cadence): the throughput kernels
 // then run the variant that re-uses the transition factors of such steps (carma_core.h, RhoInline DTC)

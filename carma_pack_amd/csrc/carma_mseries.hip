@@ -44,6 +44,8 @@
 #include "carma_lane.h"
 #include "carma_predict.h"
 #include "carma_pt_sched.h"
+#include "carma_smooth.h"
+#include "carma_smooth_plan.h"
 
 namespace carma {
 
@@ -387,6 +389,73 @@ static hipError_t upload(DevMem& b, const std::vector<T>& v, hipStream_t st)
     hipError_t e = b.need(sizeof(T) * v.size());
     if (e == hipSuccess) e = hipMemcpyAsync(b.as<void>(), v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, st);
     return e;
+}
+
+// ---- the one-pass smoother over many (series, model) items (carma_msmooth) -----------------------------------------------
+// A JOB is a (series, list of requested times) pair with its merged grid (carma_smooth_plan.h); the items that share a job fill
+// waves of E = 64 / G groups (CAR(1): 64 lanes), so that a wave's loop over the grid is uniform; other items get waves of their
+// own.  Wave w0 + blockIdx.x of the plan: job wave_job[w]; slot e of it: item slot_item[w E + e] (-1: idle, repeats the wave's
+// first item and stores no output), outputs at slot_out[w E + e]; its scratch starts wave_pts[w] grid points into the chunk's.
+// The device functions and the series records are those of carma_smooth_*: an item gets the bits of that call on its series.
+struct MsmoothTabs {
+    const int *wave_job, *job_series, *job_ng, *slot_item, *src;
+    const long *job_goff, *slot_out, *wave_pts;
+    const double* grid;
+};
+
+template <int P, int G>
+__global__ __launch_bounds__(64) void k_msmooth_carma(const double* __restrict__ par, const double4* __restrict__ records,
+                                                      const long* __restrict__ off, MsmoothTabs tb, long w0,
+                                                      double4* __restrict__ rec, double4* __restrict__ grp,
+                                                      double* __restrict__ mean, double* __restrict__ var,
+                                                      int* __restrict__ singular)
+{
+    __shared__ double4 xch[64];
+    __shared__ double2 xch2[64];
+    constexpr int E = 64 / G;
+    const int tid = threadIdx.x;
+    Grp<G> g{xch, tid & 63, xch2};
+    const long w = w0 + blockIdx.x;
+    const int j = tb.wave_job[w];
+    const double4* series = records + off[tb.job_series[j]];
+    const int ng = tb.job_ng[j];
+    const double* grid = tb.grid + tb.job_goff[j];
+    const int* src = tb.src + tb.job_goff[j];
+    const int e = tid / G;
+    int item = tb.slot_item[w * E + e];
+    const bool live = item >= 0;
+    if (!live) item = tb.slot_item[w * E];                    // (slot 0 of a wave is always live)
+    const double* pm = par + (long)item * (3 * P + 2);
+    Model<P> m;
+    model_from_roots<P, G>(g, pm, pm + 2 * P, pm[3 * P], m);
+    const double mu = pm[3 * P + 1];
+    FilterConsts<P> fc;
+    filter_reset<P, G>(g, m, fc);
+    double4* myrec = rec + (size_t)tb.wave_pts[w] * 64 + tid;
+    double4* mygrp = grp + (size_t)tb.wave_pts[w] * E + e;
+    smooth_forward<P, G>(g, m, fc, series, grid, src, ng, mu, myrec, 64, mygrp, E);
+    __syncthreads();                                          // lane 0 wrote the group records, every lane of the group reads them
+    const long o = tb.slot_out[w * E + e];
+    smooth_backward<P, G>(g, fc, src, ng, mu, myrec, 64, mygrp, E, live ? mean + o : nullptr, live ? var + o : nullptr);
+    if (live && g.lane() == 0) singular[item] = fc.sing ? 1 : 0;
+}
+
+// CAR(1): one lane per item; the wave's scratch is five planes of ng x 64 doubles
+__global__ __launch_bounds__(64) void k_msmooth_car1(const double* __restrict__ par, const double4* __restrict__ records,
+                                                     const long* __restrict__ off, MsmoothTabs tb, long w0, double* __restrict__ sc,
+                                                     double* __restrict__ mean, double* __restrict__ var)
+{
+    const long w = w0 + blockIdx.x;
+    const int j = tb.wave_job[w];
+    const double4* series = records + off[tb.job_series[j]];
+    const int ng = tb.job_ng[j];
+    int item = tb.slot_item[w * 64 + threadIdx.x];
+    const bool live = item >= 0;
+    if (!live) item = tb.slot_item[w * 64];
+    const double* pm = par + 3L * item;
+    const long o = tb.slot_out[w * 64 + threadIdx.x];
+    smooth_car1(pm[0], pm[1], pm[2], series, tb.grid + tb.job_goff[j], tb.src + tb.job_goff[j], ng,
+                sc + (size_t)tb.wave_pts[w] * 64 * 5 + threadIdx.x, 64, 64L * ng, live ? mean + o : nullptr, live ? var + o : nullptr);
 }
 
 // ---- the sampler over many series -------------------------------------------------------------------------------------
@@ -924,6 +993,178 @@ int carma_mpredict(carma_mctx* h, const int* series, int M, const double* sigsqr
     const hipError_t es = hipStreamSynchronize(st);
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return hip_fail(e, "carma_mpredict");
+    if (singular) std::memcpy(singular, sing.data(), sizeof(int) * (size_t)M);
+    return CARMA_OK;
+}
+
+int carma_msmooth(carma_mctx* h, const int* series, int M, const double* sigsqr, const double* omega_re_im, const double* ma,
+                  int nma, const double* mu, const double* tout, const long* toff, double* mean, double* var, int* singular)
+{
+    static const char* const who = "carma_msmooth";
+    if (!h || !toff) {
+        set_error("%s: bad argument (null context or toff)", who);
+        return CARMA_EINVAL;
+    }
+    Mctx* c = reinterpret_cast<Mctx*>(h);
+    const int p = c->p;
+    std::vector<double> par;
+    int rc = pack_items(c, who, series, M, sigsqr, omega_re_im, ma, nma, mu, par);
+    if (rc != CARMA_OK) return rc;
+    if (toff[0] < 0) {
+        set_error("%s: toff[0] = %ld is negative", who, toff[0]);
+        return CARMA_EINVAL;
+    }
+    for (int i = 0; i < M; i++)
+        if (toff[i + 1] < toff[i]) {
+            set_error("%s: item %d: toff must be non-decreasing (toff[%d]=%ld > toff[%d]=%ld)", who, i, i, toff[i], i + 1, toff[i + 1]);
+            return CARMA_EINVAL;
+        }
+    const long t0 = toff[0], T = toff[M] - t0;
+    if (T > 0 && (!tout || !mean || !var)) {
+        set_error("%s: bad argument (null tout, mean or var)", who);
+        return CARMA_EINVAL;
+    }
+    for (int i = 0; i < M; i++)
+        for (long o = toff[i]; o < toff[i + 1]; o++)
+            if (!std::isfinite(tout[o])) {
+                set_error("%s: item %d: tout[%ld] is not finite", who, i, o);
+                return CARMA_EINVAL;
+            }
+    if (singular) std::fill(singular, singular + M, 0);
+    if (T == 0) return CARMA_OK;
+    // launch plan (host): the items with times sorted by (series, time list); a run of equal keys is a job
+    const int G = p > 1 ? group_of(p) : 0, E = G ? 64 / G : 64;
+    auto len = [&](int i) { return toff[i + 1] - toff[i]; };
+    auto cmp = [&](int a, int b) {                            // <0, 0, >0
+        if (series[a] != series[b]) return series[a] < series[b] ? -1 : 1;
+        if (len(a) != len(b)) return len(a) < len(b) ? -1 : 1;
+        for (long k = 0; k < len(a); k++) {
+            const double x = tout[toff[a] + k], y = tout[toff[b] + k];
+            if (x != y) return x < y ? -1 : 1;
+        }
+        return 0;
+    };
+    std::vector<int> ord;
+    for (int i = 0; i < M; i++)
+        if (len(i) > 0) ord.push_back(i);
+    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return cmp(a, b) < 0; });
+    std::vector<int> wave_job, job_series, job_ng, slot_item, srcs;
+    std::vector<long> job_goff, slot_out;
+    std::vector<double> grids;
+    for (size_t k = 0; k < ord.size();) {
+        size_t k1 = k + 1;
+        while (k1 < ord.size() && cmp(ord[k], ord[k1]) == 0) k1++;
+        const int i0 = ord[k], s = series[i0], job = (int)job_series.size();
+        const SmoothGrid sg = smooth_merge(c->t.data() + c->hoff[s], c->n[s], tout + toff[i0], (int)len(i0));
+        job_series.push_back(s);
+        job_ng.push_back(sg.ng);
+        job_goff.push_back((long)grids.size());
+        grids.insert(grids.end(), sg.grid.begin(), sg.grid.end());
+        srcs.insert(srcs.end(), sg.src.begin(), sg.src.end());
+        for (size_t a = k; a < k1; a += E) {
+            wave_job.push_back(job);
+            for (size_t b = a; b < a + E; b++) {
+                slot_item.push_back(b < k1 ? ord[b] : -1);
+                slot_out.push_back(b < k1 ? toff[ord[b]] - t0 : 0L);
+            }
+        }
+        k = k1;
+    }
+    const long W = (long)wave_job.size(), J = (long)job_series.size();
+    // chunks of consecutive waves under the scratch cap ("SMOOTH_CHUNK_MODELS": that many models' waves); wave_pts: grid points
+    // of the waves before w in its chunk
+    const long forced = tune_get(TUNE_SMOOTH_CHUNK_MODELS);
+    const long wmax = (forced != TUNE_UNSET && forced > 0) ? (forced + E - 1) / E : W;
+    std::vector<long> wave_pts((size_t)W), chunk0;
+    size_t pts_max = 0;
+    {
+        size_t pts = 0;
+        long nw = 0;
+        for (long w = 0; w < W; w++) {
+            const size_t ng = (size_t)job_ng[wave_job[w]];
+            if (w == 0 || nw >= wmax || smooth_wave_bytes(G, 1) * (pts + ng) > SMOOTH_SCRATCH_CAP) {
+                chunk0.push_back(w);
+                pts = 0;
+                nw = 0;
+            }
+            wave_pts[w] = (long)pts;
+            pts += ng;
+            nw++;
+            pts_max = std::max(pts_max, pts);
+        }
+        chunk0.push_back(W);
+    }
+    // tables: ints [wave_job W][job_series J][job_ng J][slot_item W E][src], longs [job_goff J][slot_out W E][wave_pts W]
+    std::vector<int> tint;
+    tint.insert(tint.end(), wave_job.begin(), wave_job.end());
+    tint.insert(tint.end(), job_series.begin(), job_series.end());
+    tint.insert(tint.end(), job_ng.begin(), job_ng.end());
+    tint.insert(tint.end(), slot_item.begin(), slot_item.end());
+    tint.insert(tint.end(), srcs.begin(), srcs.end());
+    std::vector<long> tlong;
+    tlong.insert(tlong.end(), job_goff.begin(), job_goff.end());
+    tlong.insert(tlong.end(), slot_out.begin(), slot_out.end());
+    tlong.insert(tlong.end(), wave_pts.begin(), wave_pts.end());
+    hipError_t e = hipSetDevice(c->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    hipStream_t st = c->stream;
+    std::vector<int> sing((size_t)M, 0);
+    const size_t npar = par.size();
+    e = c->k_par.need(sizeof(double) * (npar + grids.size()));
+    if (e == hipSuccess) e = hipMemcpyAsync(c->k_par.as<void>(), par.data(), sizeof(double) * npar, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(c->k_par.as<double>() + npar, grids.data(), sizeof(double) * grids.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = upload(c->k_int, tint, st);
+    if (e == hipSuccess) e = upload(c->k_long, tlong, st);
+    if (e == hipSuccess) e = c->k_tile.need(smooth_wave_bytes(G, 1) * pts_max);
+    if (e == hipSuccess) e = c->k_res.need(sizeof(double) * 2 * (size_t)T);
+    if (e == hipSuccess) e = c->k_sing.need(sizeof(int) * (size_t)M);
+    if (e == hipSuccess) e = hipMemsetAsync(c->k_sing.as<int>(), 0, sizeof(int) * (size_t)M, st);
+    if (e == hipSuccess) {
+        (void)hipGetLastError();
+        const double* d_par = c->k_par.as<double>();
+        const int* di = c->k_int.as<int>();
+        const long* dl = c->k_long.as<long>();
+        MsmoothTabs tb;
+        tb.wave_job = di;
+        tb.job_series = di + W;
+        tb.job_ng = tb.job_series + J;
+        tb.slot_item = tb.job_ng + J;
+        tb.src = tb.slot_item + W * E;
+        tb.job_goff = dl;
+        tb.slot_out = dl + J;
+        tb.wave_pts = tb.slot_out + W * E;
+        tb.grid = d_par + npar;
+        double *d_m = c->k_res.as<double>(), *d_v = d_m + T;
+        // a chunk's scratch: the lane records of its waves, then their group records
+        double4* rec = c->k_tile.as<double4>();
+        double4* grp = rec + pts_max * 64;
+        for (size_t ci = 0; ci + 1 < chunk0.size() && e == hipSuccess; ci++) {
+            const long w0 = chunk0[ci];
+            const dim3 grid((unsigned)(chunk0[ci + 1] - w0)), block(64);
+            switch (p) {
+                case 1:
+                    hipLaunchKernelGGL(k_msmooth_car1, grid, block, 0, st, d_par, c->rec(), c->offs(), tb, w0, c->k_tile.as<double>(),
+                                       d_m, d_v);
+                    break;
+#define CARMA_MSM(N)                                                                                                              \
+    case N:                                                                                                                       \
+        hipLaunchKernelGGL((k_msmooth_carma<N, GroupOf<N>::value>), grid, block, 0, st, d_par, c->rec(), c->offs(), tb, w0, rec,   \
+                           grp, d_m, d_v, c->k_sing.as<int>());                                                                   \
+        break;
+                    CARMA_MSM(2) CARMA_MSM(3) CARMA_MSM(4) CARMA_MSM(5) CARMA_MSM(6) CARMA_MSM(7)
+#undef CARMA_MSM
+                default: return CARMA_EINVAL;
+            }
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(mean + t0, d_m, sizeof(double) * (size_t)T, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(var + t0, d_v, sizeof(double) * (size_t)T, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(sing.data(), c->k_sing.as<int>(), sizeof(int) * (size_t)M, hipMemcpyDeviceToHost, st);
+    }
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return hip_fail(e, who);
     if (singular) std::memcpy(singular, sing.data(), sizeof(int) * (size_t)M);
     return CARMA_OK;
 }

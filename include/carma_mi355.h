@@ -108,7 +108,8 @@ int carma_logdensity_kernel_name(const carma_ctx* h, int B, char* buf, int len);
 /* Launch-shape switches for measurements and the parity tests (no counterpart in the reference): "WIN_ROWS", "WIN2_EVALS",
  * "PT_ROW_WIN" -- the CARMA_TUNE_* environment variables of the same names give their initial values, read once when the first
  * launch asks; afterwards only this call moves them (process-wide, thread-safe).  CARMA_EINVAL for an unknown name.
- * "CSIM_CHUNK_PATHS": paths per chunk of carma_simulate_cond_* (0: as many as its scratch cap holds; results do not depend on it). */
+ * "CSIM_CHUNK_PATHS": paths per chunk of carma_simulate_cond_* (0: as many as its scratch cap holds; results do not depend on it).
+ * "SMOOTH_CHUNK_MODELS": models per chunk of carma_smooth_* (0: as many whole waves as its scratch cap holds; results do not depend on it). */
 int carma_tune_set(const char* name, long value);
 
 /*
@@ -141,6 +142,11 @@ int carma_tune_set(const char* name, long value);
  *   non-decreasing; an item without times is legal); pmean / pvar are indexed as tpred.  One lane group per (item, time)
  *   (CAR(1): one lane): the bits of carma_predict_carma / carma_predict_car1 on the series centred by mu, plus mu.
  *   singular as above, set by an item's predictions (an item without times reports 0).
+ * carma_msmooth: the interpolated light curve of the same kind of items, arguments and outputs as carma_mpredict, by the
+ *   one-pass smoother of carma_smooth_* (below): O((n_i + M_i) p^2) per item instead of O(M_i n_i p^2).  A wave takes items that
+ *   share (series, list of times), so that its loop over the merged grid is uniform; other items get waves of their own; idle
+ *   groups repeat the wave's first item and write nothing.  An item's outputs have the bits carma_smooth_carma /
+ *   carma_smooth_car1 gives for that model on that series alone.  Also CARMA_EINVAL: a time that is not finite (item named).
  *   Both: a series index out of range, roots not closed under conjugation, nma outside 1..p, M < 1 and a decreasing toff are
  *   CARMA_EINVAL before any device work, with the item's index in carma_last_error(); the context stays usable.  The
  *   per-call device buffers belong to the context and grow on demand.
@@ -165,6 +171,10 @@ int carma_mpredict(carma_mctx* h, const int* series /* [M] */, int M, const doub
                    const double* omega_re_im /* [M][p][2] */, const double* ma /* [M][nma] */, int nma,
                    const double* mu /* [M] or NULL */, const double* tpred, const long* toff /* [M+1] */, double* pmean,
                    double* pvar, int* singular /* [M] or NULL */);
+int carma_msmooth(carma_mctx* h, const int* series /* [M] */, int M, const double* sigsqr /* [M] */,
+                  const double* omega_re_im /* [M][p][2] */, const double* ma /* [M][nma] */, int nma,
+                  const double* mu /* [M] or NULL */, const double* tout, const long* toff /* [M+1] */, double* mean,
+                  double* var, int* singular /* [M] or NULL */);
 int carma_mle_batched_ms(carma_mctx* h, const double* x0 /* [B][d] */, const int* series /* [B] */, int B,
                          const double* lo /* [B][d] */, const double* hi /* [B][d] */, int maxiter, int mem, double ftol,
                          double gtol, double fd_step, int ignore_prior, double* x, double* fun, int* nit, int* nfev,
@@ -324,6 +334,36 @@ int carma_simulate_cond_car1(const double* time, const double* y, const double* 
                              const double* sigsqr, const double* omega, const double* mu, const double* tsim, int M,
                              uint64_t seed, unsigned path0, double* out, double* uncond, double* noise, int* singular,
                              int* n_out, int device);
+
+/*
+ * The INTERPOLATED LIGHT CURVE in one pass, for nmodels models on ONE series: mean and variance of the noise-free process at
+ * the M times tout given all the data -- what carma_predict_* returns, which filters the whole series again for every time
+ * (O(M n p^2)); here a fixed-interval smoother (modified Bryson-Frazier) walks the merged grid of data and requested times once
+ * forward and once backward, O((n + M) p^2) per model.  The series is sorted and deduplicated as carma_kf_create_* does (n_out
+ * data remain, one is enough); tout in any order, repeats allowed, finite; outputs in the CALLER's order of tout.
+ * omega_re_im = [nmodels][p][2], roots in any order but closed under conjugation; ma = [nmodels][nma], 1 <= nma <= p, zero
+ * padded inside; mu = [nmodels] or NULL (0): subtracted from y, added back to the mean (skipped for mu = 0).
+ * Outputs, each pair optional (NULL, NULL to skip) but one at least:
+ *   mean, var = [nmodels][M]   per model.  The variance is a difference (prior variance minus what the data explain) and is
+ *                              returned as computed, never clipped: it loses log10(prior / smoothed variance) digits and can come
+ *                              out <= 0 by rounding where yerr is tiny against the process.
+ *   band_mean, band_var = [M]  the moment-matched Gaussian mixture over the models that are not singular:
+ *                              band_mean = (1/K') sum_k mean_k, band_var = (1/K') sum_k (var_k + (mean_k - band_mean)^2), summed
+ *                              in ascending k on the device (when only the band is asked for, the [nmodels][M] arrays stay there).
+ * singular = [nmodels] or NULL: 1 where a model has a repeated AR root (its rows are not meaningful, it is left out of the band;
+ * other models are not affected); returns 1 if any model is singular and singular is NULL.  A model's outputs depend neither on
+ * the other models of the call nor on how it is cut into chunks (scratch: 32 G + 32 bytes per grid point and model, G = 2, 4, 8
+ * lanes for p <= 2, 4, 7; capped at 256 MiB a chunk; "SMOOTH_CHUNK_MODELS" of carma_tune_set forces a chunk size).
+ * CARMA_EINVAL, before any device work and with the offending model in carma_last_error() where one is at fault: nmodels < 1,
+ * M < 1, n < 1, nma outside 1..p, roots not closed under conjugation, sigsqr (omega) not positive, a tout that is not finite.
+ * CAR(1): omega[k] = 1 / tau_k.
+ */
+int carma_smooth_carma(const double* time, const double* y, const double* yerr, int n, int p, int nmodels, const double* sigsqr,
+                       const double* omega_re_im, const double* ma, int nma, const double* mu, const double* tout, int M,
+                       double* mean, double* var, double* band_mean, double* band_var, int* singular, int* n_out, int device);
+int carma_smooth_car1(const double* time, const double* y, const double* yerr, int n, int nmodels, const double* sigsqr,
+                      const double* omega, const double* mu, const double* tout, int M, double* mean, double* var,
+                      double* band_mean, double* band_var, int* singular, int* n_out, int device);
 
 /*
  * CarmaSample post-processing (src/carmcmc/carma_pack.py), one launch per quantity instead of a
