@@ -199,24 +199,16 @@ static hipError_t launch_csim_p(const CsimArgs& a)
 static hipError_t launch_csim(int p, const CsimArgs& a)
 {
     (void)hipGetLastError();   // HIP's last-error is sticky: drop anything left by earlier calls
-    switch (p) {
-        case 1: {
-            hipLaunchKernelGGL(k_csim_paths_car1, dim3((unsigned)(((long)a.kc + 63) / 64)), dim3(64), 0, nullptr, a.par, a.kc,
-                               a.series, a.yerr, a.n, a.grid, a.ng, a.dpos, a.seed0, a.seed1, a.path0, a.uncond, a.resid, a.noise);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(k_csim_predict_car1, dim3((unsigned)(((long)a.kc * a.M + 63) / 64)), dim3(64), 0, nullptr, a.par,
-                               a.kc, a.resid, a.n, a.tsim, a.spos, a.M, a.uncond, a.ng, a.out);
-            return hipGetLastError();
-        }
-        case 2: return launch_csim_p<2>(a);
-        case 3: return launch_csim_p<3>(a);
-        case 4: return launch_csim_p<4>(a);
-        case 5: return launch_csim_p<5>(a);
-        case 6: return launch_csim_p<6>(a);
-        case 7: return launch_csim_p<7>(a);
-        default: return hipErrorInvalidValue;
+    if (p == 1) {
+        hipLaunchKernelGGL(k_csim_paths_car1, dim3((unsigned)(((long)a.kc + 63) / 64)), dim3(64), 0, nullptr, a.par, a.kc, a.series,
+                           a.yerr, a.n, a.grid, a.ng, a.dpos, a.seed0, a.seed1, a.path0, a.uncond, a.resid, a.noise);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_csim_predict_car1, dim3((unsigned)(((long)a.kc * a.M + 63) / 64)), dim3(64), 0, nullptr, a.par, a.kc,
+                           a.resid, a.n, a.tsim, a.spos, a.M, a.uncond, a.ng, a.out);
+        return hipGetLastError();
     }
+    return for_order(p, hipErrorInvalidValue, [&](auto P) { return launch_csim_p<decltype(P)::value>(a); });
 }
 
 // paths per chunk: the "CSIM_CHUNK_PATHS" switch, or as many as keep the scratch under the cap

@@ -16,7 +16,7 @@
 namespace carma {
 
 // What both parallel-tempering samplers hold: an ensemble of R ladders of T chains (chain = ladder * T + temperature) with its
-// buffers.  carma_pt_* (PtState below): the R replicas of one series; carma_mpt_* (MptState, carma_mseries.hip): the ladders of
+// buffers.  carma_pt_* (PtState below): the R replicas of one series; carma_mpt_* (MptState, carma_mseries.h): the ladders of
 // all runs of a call.  The pt_ens_* functions (carma_pt_host.hip) work on this part alone.
 struct PtEnsemble {
     int T = 0, R = 0;                  // temperatures of a ladder, ladders (what PtLaunch::T and ::R receive)

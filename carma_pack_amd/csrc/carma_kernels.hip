@@ -963,31 +963,17 @@ static int logdens_name_p(long B, int n, char* buf, int len, int series_flags)
 
 int logdens_kernel_name(int p, long B, int n, char* buf, int len, int series_flags)
 {
-    switch (p) {
-        case 1: return snprintf(buf, len, "k_logdens_car1");     // (or its parallel-in-time form: launch_logdens_car1)
-        case 2: return logdens_name_p<2>(B, n, buf, len, series_flags);
-        case 3: return logdens_name_p<3>(B, n, buf, len, series_flags);
-        case 4: return logdens_name_p<4>(B, n, buf, len, series_flags);
-        case 5: return logdens_name_p<5>(B, n, buf, len, series_flags);
-        case 6: return logdens_name_p<6>(B, n, buf, len, series_flags);
-        case 7: return logdens_name_p<7>(B, n, buf, len, series_flags);
-        default: return -1;
-    }
+    if (p == 1) return snprintf(buf, len, "k_logdens_car1");     // (or its parallel-in-time form: launch_logdens_car1)
+    return for_order(p, -1, [&](auto P) { return logdens_name_p<decltype(P)::value>(B, n, buf, len, series_flags); });
 }
 
 hipError_t launch_logdens_carma(int p, const double* theta, int B, int d, int q, const double4* series, int n,
                                 const Prior& pr, int ignore_prior, double* out, hipStream_t st, int series_flags)
 {
     (void)hipGetLastError();   // HIP's last-error is sticky: drop anything left by earlier calls
-    switch (p) {
-        case 2: return launch_logdens_p<2>(theta, B, d, q, series, n, pr, ignore_prior, out, st, series_flags);
-        case 3: return launch_logdens_p<3>(theta, B, d, q, series, n, pr, ignore_prior, out, st, series_flags);
-        case 4: return launch_logdens_p<4>(theta, B, d, q, series, n, pr, ignore_prior, out, st, series_flags);
-        case 5: return launch_logdens_p<5>(theta, B, d, q, series, n, pr, ignore_prior, out, st, series_flags);
-        case 6: return launch_logdens_p<6>(theta, B, d, q, series, n, pr, ignore_prior, out, st, series_flags);
-        case 7: return launch_logdens_p<7>(theta, B, d, q, series, n, pr, ignore_prior, out, st, series_flags);
-        default: return hipErrorInvalidValue;
-    }
+    return for_order(p, hipErrorInvalidValue, [&](auto P) {
+        return launch_logdens_p<decltype(P)::value>(theta, B, d, q, series, n, pr, ignore_prior, out, st, series_flags);
+    });
 }
 
 hipError_t launch_logdens_car1(const double* theta, int B, const double4* series, int n, const Prior& pr, double* out,
@@ -1024,15 +1010,9 @@ hipError_t launch_kfilter_carma(int p, const double* om, const double* ma, doubl
                                 double* mean, double* var, int* singular, hipStream_t st)
 {
     (void)hipGetLastError();   // HIP's last-error is sticky: drop anything left by earlier calls
-    switch (p) {
-        case 2: return launch_kfilter_p<2>(om, ma, sigsqr, series, n, mean, var, singular, st);
-        case 3: return launch_kfilter_p<3>(om, ma, sigsqr, series, n, mean, var, singular, st);
-        case 4: return launch_kfilter_p<4>(om, ma, sigsqr, series, n, mean, var, singular, st);
-        case 5: return launch_kfilter_p<5>(om, ma, sigsqr, series, n, mean, var, singular, st);
-        case 6: return launch_kfilter_p<6>(om, ma, sigsqr, series, n, mean, var, singular, st);
-        case 7: return launch_kfilter_p<7>(om, ma, sigsqr, series, n, mean, var, singular, st);
-        default: return hipErrorInvalidValue;
-    }
+    return for_order(p, hipErrorInvalidValue, [&](auto P) {
+        return launch_kfilter_p<decltype(P)::value>(om, ma, sigsqr, series, n, mean, var, singular, st);
+    });
 }
 
 hipError_t launch_kfilter_batch(int p, const double* par, int B, const double4* series, int n, double* mv, int* singular,
@@ -1040,14 +1020,10 @@ hipError_t launch_kfilter_batch(int p, const double* par, int B, const double4* 
 {
     (void)hipGetLastError();
     const unsigned blocks = (unsigned)(((long)B + 63) / 64);
-    switch (p) {
-#define CARMA_KFB(N) \
-    case N: hipLaunchKernelGGL((k_kfilter_carma_lane<N>), dim3(blocks), dim3(64), 0, st, par, B, series, n, mv, singular); break;
-        CARMA_KFB(2) CARMA_KFB(3) CARMA_KFB(4) CARMA_KFB(5) CARMA_KFB(6) CARMA_KFB(7)
-#undef CARMA_KFB
-        default: return hipErrorInvalidValue;
-    }
-    hipError_t e = hipGetLastError();
+    const hipError_t e = for_order(p, hipErrorInvalidValue, [&](auto P) {
+        hipLaunchKernelGGL((k_kfilter_carma_lane<decltype(P)::value>), dim3(blocks), dim3(64), 0, st, par, B, series, n, mv, singular);
+        return hipGetLastError();
+    });
     if (e != hipSuccess) return e;
     const long ld = (long)B + 64;
     const dim3 grid((unsigned)((B + 31) / 32), (unsigned)((n + 31) / 32));
@@ -1071,15 +1047,9 @@ hipError_t launch_predict_carma(int p, const double* om, const double* ma, doubl
                                 const double* tpred, int M, double* pmean, double* pvar, int* singular, hipStream_t st)
 {
     (void)hipGetLastError();   // HIP's last-error is sticky: drop anything left by earlier calls
-    switch (p) {
-        case 2: return launch_predict_p<2>(om, ma, sigsqr, series, n, tpred, M, pmean, pvar, singular, st);
-        case 3: return launch_predict_p<3>(om, ma, sigsqr, series, n, tpred, M, pmean, pvar, singular, st);
-        case 4: return launch_predict_p<4>(om, ma, sigsqr, series, n, tpred, M, pmean, pvar, singular, st);
-        case 5: return launch_predict_p<5>(om, ma, sigsqr, series, n, tpred, M, pmean, pvar, singular, st);
-        case 6: return launch_predict_p<6>(om, ma, sigsqr, series, n, tpred, M, pmean, pvar, singular, st);
-        case 7: return launch_predict_p<7>(om, ma, sigsqr, series, n, tpred, M, pmean, pvar, singular, st);
-        default: return hipErrorInvalidValue;
-    }
+    return for_order(p, hipErrorInvalidValue, [&](auto P) {
+        return launch_predict_p<decltype(P)::value>(om, ma, sigsqr, series, n, tpred, M, pmean, pvar, singular, st);
+    });
 }
 
 template <int P>
@@ -1098,15 +1068,9 @@ hipError_t launch_simulate_carma(int p, const double* om, const double* ma, doub
                                  hipStream_t st)
 {
     (void)hipGetLastError();
-    switch (p) {
-        case 2: return launch_simulate_p<2>(om, ma, sigsqr, times, n, npaths, seed0, seed1, path0, out, singular, st);
-        case 3: return launch_simulate_p<3>(om, ma, sigsqr, times, n, npaths, seed0, seed1, path0, out, singular, st);
-        case 4: return launch_simulate_p<4>(om, ma, sigsqr, times, n, npaths, seed0, seed1, path0, out, singular, st);
-        case 5: return launch_simulate_p<5>(om, ma, sigsqr, times, n, npaths, seed0, seed1, path0, out, singular, st);
-        case 6: return launch_simulate_p<6>(om, ma, sigsqr, times, n, npaths, seed0, seed1, path0, out, singular, st);
-        case 7: return launch_simulate_p<7>(om, ma, sigsqr, times, n, npaths, seed0, seed1, path0, out, singular, st);
-        default: return hipErrorInvalidValue;
-    }
+    return for_order(p, hipErrorInvalidValue, [&](auto P) {
+        return launch_simulate_p<decltype(P)::value>(om, ma, sigsqr, times, n, npaths, seed0, seed1, path0, out, singular, st);
+    });
 }
 
 hipError_t launch_simulate_car1(double sigsqr, double omega, const double* times, int n, int npaths, unsigned seed0,

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <functional>
+#include <type_traits>
 
 #include "carma_types.h"
 
@@ -14,6 +15,22 @@ template <int P>
 struct GroupOf {
     static constexpr int value = group_of(P);
 };
+
+// run-time order -> template argument: f(std::integral_constant<int, P>{}) for p = P in 2 ... 7 (CARMA_PMAX), `bad` for any other p.
+// CAR(1) has kernels and argument lists of its own and stays with the caller.
+template <class R, class F>
+inline R for_order(int p, R bad, F&& f)
+{
+    switch (p) {
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+        default: return bad;
+    }
+}
 
 // compute units of the current device (cached per device)
 int device_cus();

@@ -632,15 +632,7 @@ static const void* pt_row_fn(int minw, bool win = false, bool two = false, bool 
 
 static const void* pt_row_fn_p(int p, int minw)
 {
-    switch (p) {
-        case 2: return pt_row_fn<2>(minw);
-        case 3: return pt_row_fn<3>(minw);
-        case 4: return pt_row_fn<4>(minw);
-        case 5: return pt_row_fn<5>(minw);
-        case 6: return pt_row_fn<6>(minw);
-        case 7: return pt_row_fn<7>(minw);
-        default: return nullptr;
-    }
+    return for_order(p, (const void*)nullptr, [&](auto P) { return pt_row_fn<decltype(P)::value>(minw); });
 }
 
 long pt_row_capacity(int p, int d, int T, int n)
@@ -742,15 +734,9 @@ hipError_t launch_pt_row(int p, const PtLaunch& L, const PtRowSync& S, const dou
                          unsigned* nswap, double* samples, double* sample_lp, hipStream_t st)
 {
     (void)hipGetLastError();   // HIP's last-error is sticky: drop anything left by earlier calls
-    switch (p) {
-        case 2: return launch_pt_row_p<2>(L, S, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st);
-        case 3: return launch_pt_row_p<3>(L, S, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st);
-        case 4: return launch_pt_row_p<4>(L, S, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st);
-        case 5: return launch_pt_row_p<5>(L, S, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st);
-        case 6: return launch_pt_row_p<6>(L, S, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st);
-        case 7: return launch_pt_row_p<7>(L, S, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st);
-        default: return hipErrorInvalidValue;
-    }
+    return for_order(p, hipErrorInvalidValue, [&](auto P) {
+        return launch_pt_row_p<decltype(P)::value>(L, S, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st);
+    });
 }
 
 hipError_t launch_pt(int p, const PtLaunch& L, const double4* series, const Prior& pr, const double* temps,
@@ -758,16 +744,10 @@ hipError_t launch_pt(int p, const PtLaunch& L, const double4* series, const Prio
                      double* sample_lp, hipStream_t st)
 {
     (void)hipGetLastError();   // HIP's last-error is sticky: drop anything left by earlier calls
-    switch (p) {
-        case 1: return launch_pt_p<1>(L, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st);
-        case 2: return launch_pt_p<2>(L, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st);
-        case 3: return launch_pt_p<3>(L, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st);
-        case 4: return launch_pt_p<4>(L, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st);
-        case 5: return launch_pt_p<5>(L, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st);
-        case 6: return launch_pt_p<6>(L, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st);
-        case 7: return launch_pt_p<7>(L, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st);
-        default: return hipErrorInvalidValue;
-    }
+    if (p == 1) return launch_pt_p<1>(L, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st);
+    return for_order(p, hipErrorInvalidValue, [&](auto P) {
+        return launch_pt_p<decltype(P)::value>(L, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st);
+    });
 }
 
 }  // namespace carma

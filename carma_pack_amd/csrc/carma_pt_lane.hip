@@ -352,7 +352,7 @@ static hipError_t ram_launch_d(int d, F&& f)
 // chain-major copy is NOT written back here -- pt_lane_store_factor does that for whoever wants to read it.
 // K1 is the caller's: k1(thn [nc][d], nc, ll [nc], st) enqueues the log-densities of the nc proposals.  The bookkeeping kernels never
 // touch a series, so whoever supplies K1 decides what a chain is evaluated on (launch_pt_lane below: one series for all chains;
-// carma_mseries.hip: every ladder on a series of its own).
+// carma_mpt.hip: every ladder on a series of its own).
 hipError_t launch_pt_lane_k1(int p, const PtLaunch& L, double* scratch, const PtLaneK1& k1, const double* temps, double* theta,
                              double* logpost, double* chol, unsigned* naccept, unsigned* nswap, double* samples, double* sample_lp,
                              bool load_factor, hipStream_t st)

@@ -1,5 +1,5 @@
 // carma_pt_sched.h -- what the parallel-tempering samplers decide on the host, host C++ only: no HIP, nothing but the standard
-// library and carma_types.h.  One copy for carma_pt_* (carma_pt_host.hip: one series) and carma_mpt_* (carma_mseries.hip: many):
+// library and carma_types.h.  One copy for carma_pt_* (carma_pt_host.hip: one series) and carma_mpt_* (carma_mpt.hip: many):
 // the default ladder, the initial proposal factor, the length of the next launch, the starting-value draws and the search for
 // finite starting values.  tests/ptsched/ compiles it with a plain C++ compiler.
 #ifndef CARMA_PT_SCHED_H

@@ -124,19 +124,12 @@ static hipError_t launch_smooth_p(const SmoothArgs& a)
 static hipError_t launch_smooth(int p, const SmoothArgs& a)
 {
     (void)hipGetLastError();   // HIP's last-error is sticky: drop anything left by earlier calls
-    switch (p) {
-        case 1:
-            hipLaunchKernelGGL(k_smooth_car1, dim3((unsigned)((a.kc + 63) / 64)), dim3(64), 0, nullptr, a.par, a.kc, a.series,
-                               a.grid, a.src, a.ng, a.M, reinterpret_cast<double*>(a.rec), a.mean, a.var);
-            return hipGetLastError();
-        case 2: return launch_smooth_p<2>(a);
-        case 3: return launch_smooth_p<3>(a);
-        case 4: return launch_smooth_p<4>(a);
-        case 5: return launch_smooth_p<5>(a);
-        case 6: return launch_smooth_p<6>(a);
-        case 7: return launch_smooth_p<7>(a);
-        default: return hipErrorInvalidValue;
+    if (p == 1) {
+        hipLaunchKernelGGL(k_smooth_car1, dim3((unsigned)((a.kc + 63) / 64)), dim3(64), 0, nullptr, a.par, a.kc, a.series, a.grid,
+                           a.src, a.ng, a.M, reinterpret_cast<double*>(a.rec), a.mean, a.var);
+        return hipGetLastError();
     }
+    return for_order(p, hipErrorInvalidValue, [&](auto P) { return launch_smooth_p<decltype(P)::value>(a); });
 }
 
 // par = [K][pw] rows as the kernels read them (validated, roots normalised); p == 1: pw = 3

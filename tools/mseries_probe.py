@@ -1,4 +1,4 @@
-"""Many series per launch (carma_mseries.hip) against the single-series lane kernel and against a loop over contexts.
+"""Many series per launch (carma_mseries.hip, its launch plan in carma_mseries_plan.h) against the single-series lane kernel and against a loop over contexts.
 One JSON line per case on stdout (and appended to the file MSERIES_PROBE_OUT names, when it is set):
   equal    S = 4096 series x 256 evaluations of CARMA(5,3), n = 270 each (2^20 evaluations)
   ragged   the same with n log-uniform in 50 .. 5000
