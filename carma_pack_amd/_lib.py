@@ -138,6 +138,19 @@ def _load():
                                        C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]
     L.carma_msmooth.argtypes = [C.c_void_p, _ip, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, C.POINTER(C.c_long), _dp, _dp, _ip]
+    L.carma_bands_create.restype = C.c_void_p
+    L.carma_bands_create.argtypes = [_dp, _dp, _dp, C.POINTER(C.c_long), C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_int]
+    L.carma_bands_destroy.argtypes = [C.c_void_p]
+    L.carma_bands_destroy.restype = None
+    L.carma_bands_dim.argtypes = [C.c_void_p]
+    L.carma_bands_nbands.argtypes = [C.c_void_p]
+    L.carma_bands_n.argtypes = [C.c_void_p, C.c_int]
+    L.carma_bands_get_prior.argtypes = [C.c_void_p, _dp]
+    L.carma_bands_logdensity_batch.argtypes = [C.c_void_p, _dp, C.c_int, C.c_int, _dp]
+    L.carma_bands_logdensity_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.carma_bands_mle_batched.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                          C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
     L.carma_mpt_create.argtypes = [C.c_void_p, _ip, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_uint64]
     L.carma_mpt_start.argtypes = [C.c_void_p, _dp]
     L.carma_mpt_set_chains.argtypes = [C.c_void_p, _dp, _dp]
@@ -245,6 +258,8 @@ EXPORTS = [
     "carma_mpt_get_chains", "carma_mpt_get_factor", "carma_mpt_set_factor", "carma_mpt_iterate", "carma_mpt_sample",
     "carma_mpt_stats", "carma_mpt_iterations_done", "carma_mpt_logdensity", "carma_mpt_kernel_name", "carma_mpt_run",
     "carma_mpsd_band", "carma_mpsd_fused_max", "carma_mpsd_freq_tile", "carma_chain_diag", "carma_chain_diag_dmax", "carma_chain_diag_kernel_ms",
+    "carma_bands_create", "carma_bands_destroy", "carma_bands_dim", "carma_bands_nbands", "carma_bands_n", "carma_bands_get_prior",
+    "carma_bands_logdensity_batch", "carma_bands_logdensity_batch_dev", "carma_bands_mle_batched",
 ]
 
 
@@ -939,6 +954,110 @@ class MultiContext:
         self._mpt_shape = (int(w.size), int(nreplicas), int(ntemps))
         self._mpt_series = w
         return samples, logposts
+
+
+class BandsContext:
+    """Owns one carma_bands: K bands of ONE process resident in HBM, band b seen as a_b x(t - lag_b) + mu_b.
+
+    bands: a list of (t, y, yerr), band 0 the reference band; lag_bounds: [K - 1] pairs (lo, hi), the box of every lag.  The
+    parameter vector is Context's (d entries) followed by (lag_b, log a_b, mu_b) for b = 1 ... K - 1: dx entries."""
+
+    def __init__(self, bands, p, q=0, lag_bounds=None, max_stdev=None, device=None):
+        bands = list(bands)
+        if not bands:
+            raise ValueError("BandsContext needs at least one band")
+        ts, ys, es = [], [], []
+        for b, item in enumerate(bands):
+            if len(item) != 3:
+                raise ValueError("band %d: expected (t, y, yerr)" % b)
+            t, y, e = (as_f64(a).ravel() for a in item)
+            if not (t.size == y.size == e.size):
+                raise ValueError("band %d: time, y, yerr must have the same length" % b)
+            ts.append(t)
+            ys.append(y)
+            es.append(e)
+        K = len(bands)
+        lb = np.zeros((0, 2)) if lag_bounds is None else as_f64(lag_bounds).reshape(-1, 2)
+        if lb.shape[0] != K - 1:
+            raise ValueError("lag_bounds must hold one (lo, hi) pair for each of the %d bands after the first" % (K - 1))
+        lo, hi = as_f64(lb[:, 0]), as_f64(lb[:, 1])
+        if max_stdev is None:
+            max_stdev = 10.0 * np.sqrt(np.var(ys[0], ddof=1)) if ys[0].size > 1 else 0.0
+        offsets = np.zeros(K + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([t.size for t in ts])
+        t_all, y_all, e_all = (as_f64(np.concatenate(a)) for a in (ts, ys, es))
+        self.device = default_device() if device is None else int(device)
+        self._h = lib.carma_bands_create(ptr(t_all), ptr(y_all), ptr(e_all), offsets.ctypes.data_as(C.POINTER(C.c_long)), K,
+                                         int(p), int(q), ptr(lo) if K > 1 else None, ptr(hi) if K > 1 else None,
+                                         float(max_stdev), self.device)
+        if not self._h:
+            msg = "carma_bands_create failed: " + last_error()
+            if "no HIP device" in msg:
+                raise CarmaDeviceError(msg)
+            raise ValueError(msg)
+        self.p, self.q = int(p), int(q)
+        self.nbands = lib.carma_bands_nbands(self._h)
+        self.dx = lib.carma_bands_dim(self._h)
+        self.d = self.dx - 3 * (self.nbands - 1)
+        self.n = np.array([lib.carma_bands_n(self._h, b) for b in range(self.nbands)], dtype=np.int64)
+        self.lag_bounds = lb.copy()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.carma_bands_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def prior(self):
+        out = np.empty(3)
+        check(lib.carma_bands_get_prior(self._h, ptr(out)), "carma_bands_get_prior")
+        return tuple(out)
+
+    def logdensity(self, thetas, ignore_prior=False):
+        thetas = as_f64(thetas)
+        one = thetas.ndim == 1
+        thetas = thetas.reshape(-1, self.dx)
+        out = np.empty(thetas.shape[0])
+        check(lib.carma_bands_logdensity_batch(self._h, ptr(thetas), thetas.shape[0], int(bool(ignore_prior)), ptr(out)),
+              "carma_bands_logdensity_batch")
+        return float(out[0]) if one else out
+
+    def logdensity_dev(self, d_theta_ptr, B, d_out_ptr, ignore_prior=False, stream=0):
+        """Enqueue on `stream` (a hipStream_t as int); pointers are device addresses."""
+        check(lib.carma_bands_logdensity_batch_dev(self._h, C.c_void_p(d_theta_ptr), int(B), int(bool(ignore_prior)),
+                                                   C.c_void_p(d_out_ptr), C.c_void_p(stream)),
+              "carma_bands_logdensity_batch_dev")
+
+    def mle_batched(self, x0, lo=None, hi=None, fixed_lag=None, maxiter=2000, mem=8, ftol=2.220446049250313e-09, gtol=1e-5,
+                    fd_step=1e-6, ignore_prior=True):
+        """carma_bands_mle_batched: lock-step bounded L-BFGS from every row of x0 [B, dx] on -LogDensity.  lo / hi: [dx] (None
+        or non-finite = unbounded; lags stay in their boxes).  fixed_lag [B, K - 1]: the lags of start i are held at
+        fixed_lag[i] and come back unchanged in x.  Returns (x [B, dx], fun [B], nit [B], nfev [B], status [B])."""
+        x0 = np.ascontiguousarray(np.atleast_2d(np.asarray(x0, dtype=np.float64)))
+        B, dx = x0.shape
+        if dx != self.dx:
+            raise ValueError("x0 must be [B, %d]" % self.dx)
+        lo = np.full(dx, -np.inf) if lo is None else as_f64(lo).reshape(dx)
+        hi = np.full(dx, np.inf) if hi is None else as_f64(hi).reshape(dx)
+        fl = None
+        if fixed_lag is not None:
+            fl = as_f64(fixed_lag).reshape(B, self.nbands - 1)
+        x, fun = np.empty((B, dx)), np.empty(B)
+        nit, nfev, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        check(lib.carma_bands_mle_batched(self._h, ptr(x0), B, ptr(lo), ptr(hi), None if fl is None else ptr(fl), int(maxiter),
+                                          int(mem), float(ftol), float(gtol), float(fd_step), 1 if ignore_prior else 0, ptr(x),
+                                          ptr(fun), nit.ctypes.data_as(C.c_void_p), nfev.ctypes.data_as(C.c_void_p),
+                                          status.ctypes.data_as(C.c_void_p)), "carma_bands_mle_batched")
+        return x, fun, nit, nfev, status
 
 
 def kfilter_car1(time, y, yerr, sigsqr, omega, device=None):

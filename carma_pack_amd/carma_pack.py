@@ -15,7 +15,7 @@ from scipy.optimize import minimize
 
 from . import _carmcmc as carmcmcLib
 
-__all__ = ["CarmaModel", "CarmaModelSet", "CarmaSample", "Car1Sample", "MCMCSample", "get_ar_roots", "power_spectrum",
+__all__ = ["CarmaModel", "CarmaModelSet", "CarmaBandsModel", "CarmaSample", "Car1Sample", "MCMCSample", "get_ar_roots", "power_spectrum",
            "carma_variance", "car1_process", "carma_process", "carma_process_batch", "car1_process_batch", "mle_to_model"]
 
 
@@ -1161,3 +1161,143 @@ class CarmaModelSet(object):
                 acf = acf / acf[0]                            # (by its own lag 0, not np.sum(r0 * r0): resid_acf[0] is exactly 1)
                 out[s] = dict(time=grids[k], mean=pm[k], var=pv[k], std_resid=resid, resid_acf=acf)
         return out
+
+
+# ------------------------------------------------------------------------------------------------
+class CarmaBandsModel(object):
+    """ONE CARMA(p,q) process observed in several bands with a lag between them (no counterpart in the reference): several
+    filters of a survey, the images of a lensed quasar, the continuum and a delayed line of a reverberation campaign.  Band
+    b sees  y = a_b x(t - lag_b) + mu_b + noise;  band 0 is the reference band (lag 0, a = 1, mu = theta[2]).
+
+    bands: a list of (time, y, ysig), each sorted and deduplicated as CarmaModel does; lag_bounds: one (lo, hi) pair for each
+    band after the first (one pair alone for two bands): the box of that band's lag; None: +- half the time all bands span.
+    The parameter vector is CarmaModel's (ysigma, measerr_scale, mu, log-quadratic AR parameters, MA parameters) followed
+    by (lag_b, log a_b, mu_b) for b = 1 ... K - 1.  Every log-density is one lane of k_logdens_carma_mband, which merges the
+    bands in the order that vector's lags give."""
+
+    def __init__(self, bands, p=1, q=0, lag_bounds=None):
+        bands = list(bands)
+        if not bands:
+            raise ValueError("CarmaBandsModel needs at least one band")
+        if not p > q:
+            raise ValueError("Order of AR polynomial, p, must be larger than order of MA polynomial, q.")
+        self.bands = []
+        for b, item in enumerate(bands):
+            if len(item) != 3:
+                raise ValueError("band %d: expected (time, y, ysig)" % b)
+            t, y, e = (np.asarray(a, dtype=float).ravel() for a in item)
+            if not (t.size == y.size == e.size) or t.size < 1:
+                raise ValueError("band %d: time, y, ysig must have the same length, at least 1" % b)
+            _, idx = np.unique(t, return_index=True)         # sorted, first occurrence of each time
+            self.bands.append((t[idx], y[idx], e[idx]))
+        self.K = len(self.bands)
+        self.p, self.q = int(p), int(q)
+        self.d = 3 + self.p + self.q
+        self.dx = self.d + 3 * (self.K - 1)
+        if lag_bounds is None:
+            span = max(t.max() for t, _, _ in self.bands) - min(t.min() for t, _, _ in self.bands)
+            lag_bounds = [(-0.5 * span, 0.5 * span)] * (self.K - 1)
+        self.lag_bounds = np.asarray(lag_bounds, dtype=float).reshape(-1, 2)
+        if self.lag_bounds.shape[0] != self.K - 1:
+            raise ValueError("lag_bounds must hold one (lo, hi) pair for each band after the first")
+        self._ctx = None
+
+    def context(self):
+        """The BandsContext of the model (created once; max_stdev as the samplers that provide get_mle's starts set it)."""
+        if self._ctx is None:
+            from ._lib import BandsContext
+            self._ctx = BandsContext(self.bands, self.p, self.q, lag_bounds=self.lag_bounds,
+                                     max_stdev=carmcmcLib._pop_max_stdev(self.bands[0][1]))
+        return self._ctx
+
+    def _lag_cols(self):
+        return self.d + 3 * np.arange(self.K - 1)
+
+    def loglik(self, theta):
+        """-f of get_mle's objective: the log-density of the extended vector(s) with the prior bounds of the MLE (SetMLE(true)
+        for p > 1: neither the CARMA bounds nor the lag boxes are tested).  theta: [dx] or [B, dx], one launch."""
+        return self.context().logdensity(theta, ignore_prior=self.p > 1)
+
+    def logpost(self, theta):
+        """The log-posterior: -inf outside the prior bounds of the CARMA part (band 0's) or a lag box."""
+        return self.context().logdensity(theta, ignore_prior=False)
+
+    def _starts(self, ntrials, seed):
+        """([ntrials, dx] starts, lo [dx], hi [dx]): the CARMA part as CarmaModel._mle_problem draws it on band 0, lags
+        uniform in their boxes, log a_b = log(std y_b / std y_0), mu_b = mean y_b."""
+        t0, y0, e0 = self.bands[0]
+        _, st, bnds = CarmaModel(t0, y0, e0, p=self.p, q=self.q)._mle_problem(self.p, self.q, ntrials, seed)
+        rng = np.random.default_rng(seed)
+        x0 = np.empty((st.shape[0], self.dx))
+        x0[:, :self.d] = st
+        s0 = y0.std()
+        for b in range(1, self.K):
+            yb = self.bands[b][1]
+            c = self.d + 3 * (b - 1)
+            x0[:, c] = rng.uniform(self.lag_bounds[b - 1, 0], self.lag_bounds[b - 1, 1], st.shape[0])
+            x0[:, c + 1] = np.log(yb.std() / s0) if yb.std() > 0 and s0 > 0 else 0.0
+            x0[:, c + 2] = yb.mean()
+        lo = np.array([-np.inf if b[0] is None else b[0] for b in bnds] + [-np.inf] * (3 * (self.K - 1)))
+        hi = np.array([np.inf if b[1] is None else b[1] for b in bnds] + [np.inf] * (3 * (self.K - 1)))
+        return x0, lo, hi
+
+    @staticmethod
+    def _results(xs, fs, nits, nfevs, sts):
+        return [BatchResult(xs[i].copy(), float(fs[i]), int(nits[i]), int(nfevs[i]), int(sts[i]) < 2, STATUS_TEXT[int(sts[i])])
+                for i in range(xs.shape[0])]
+
+    def get_mle(self, ntrials=100, seed=None, return_all=False):
+        """Best of `ntrials` bounded quasi-Newton fits of the extended vector, all advanced in lock-step
+        (carma_bands_mle_batched); the lags stay inside their boxes.  Returns an object with .x, .fun (= -loglik), .message
+        (return_all: the list of all ntrials results, in the order of the starts)."""
+        x0, lo, hi = self._starts(ntrials, seed)
+        results = self._results(*self.context().mle_batched(x0, lo, hi, ignore_prior=self.p > 1))
+        if return_all:
+            return results
+        results = [r for r in results if np.isfinite(r.fun) and r.fun < 1e299] or results
+        return min(results, key=lambda r: r.fun)
+
+    def lag_profile(self, lags, ntrials=8, seed=None):
+        """The profile log-likelihood over the lags: at each of the L rows of `lags` ([L] for two bands, else [L, K - 1]) the
+        other parameters are optimised from `ntrials` starts with the lags held fixed -- all L x ntrials starts in ONE
+        lock-step run.  Returns (loglik [L], x [L, dx]): the best log-likelihood at each row and the optimum that reaches it,
+        whose lag entries are the given lags unchanged."""
+        if self.K < 2:
+            raise ValueError("lag_profile needs at least two bands")
+        lags = np.asarray(lags, dtype=float)
+        lags = lags.reshape(-1, 1) if self.K == 2 and lags.ndim == 1 else np.atleast_2d(lags)
+        if lags.shape[1] != self.K - 1:
+            raise ValueError("lags must be [L] for two bands or [L, %d]" % (self.K - 1))
+        if not np.all((lags >= self.lag_bounds[:, 0]) & (lags <= self.lag_bounds[:, 1])):
+            raise ValueError("every lag must lie inside its box (lag_bounds)")
+        L = lags.shape[0]
+        x0, lo, hi = self._starts(ntrials, seed)
+        nt = x0.shape[0]
+        fixed = np.repeat(lags, nt, axis=0)
+        xs, fs, nits, nfevs, sts = self.context().mle_batched(np.tile(x0, (L, 1)), lo, hi, fixed_lag=fixed,
+                                                              ignore_prior=self.p > 1)
+        fs = np.where(np.isfinite(fs), fs, 1e300).reshape(L, nt)
+        best = fs.argmin(axis=1)
+        return -fs[np.arange(L), best], xs.reshape(L, nt, self.dx)[np.arange(L), best]
+
+    def merged(self, theta):
+        """The single light curve the bands make at theta, in the units of band 0: (time, y, ysig, band) with
+        time = t - lag_b, y = (y_b - mu_b) / a_b + mu_0, ysig = ysig_b / a_b, sorted by time (equal times: the lower band
+        first), band = the band each datum came from.  Host numpy.  CarmaModel(time, y, ysig, p, q) on it gives the sampler, the
+        smoother and the power spectrum at the fitted lag -- but CarmaModel DROPS data with equal times (it keeps the first
+        of each), which the multi-band likelihood keeps."""
+        theta = np.asarray(theta, dtype=float).reshape(self.dx)
+        ts, ys, es, bs = [], [], [], []
+        for b, (t, y, e) in enumerate(self.bands):
+            if b == 0:
+                lag, a, mu = 0.0, 1.0, theta[2]
+            else:
+                c = self.d + 3 * (b - 1)
+                lag, a, mu = theta[c], np.exp(theta[c + 1]), theta[c + 2]
+            ts.append(t - lag)
+            ys.append((y - mu) / a + theta[2])
+            es.append(e / a)
+            bs.append(np.full(t.size, b, dtype=np.int64))
+        t, y, e, band = (np.concatenate(a) for a in (ts, ys, es, bs))
+        order = np.lexsort((band, t))
+        return t[order], y[order], e[order], band[order]

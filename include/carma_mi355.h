@@ -181,6 +181,46 @@ int carma_mle_batched_ms(carma_mctx* h, const double* x0 /* [B][d] */, const int
                          int* status);
 
 /*
+ * ONE PROCESS IN SEVERAL BANDS, with a lag between them (no counterpart in the reference): K bands observe one latent
+ * CARMA(p,q) process x(t); band b sees  y = a_b x(t - lag_b) + mu_b + noise,  noise variance measerr_scale yerr^2.  Band 0 is
+ * the reference band (lag 0, a = 1, mu = theta[2]).  The parameter vector is theta of carma_ctx (d = 3 + p + q entries; p = 1:
+ * ysigma, measerr_scale, mu, log omega) followed by (lag_b, log a_b, mu_b) for b = 1 ... K - 1: dx = d + 3 (K - 1) entries.
+ * The log-density is that of the merged series t - lag_b in time order (equal shifted times are legal), plus the prior of the
+ * CARMA part with the bounds of band 0; lag_b is flat inside [lag_lo_b, lag_hi_b] and -inf outside (not tested with
+ * ignore_prior), log a_b and mu_b are flat, a non-finite band parameter gives -inf.  p = 1 keeps the CAR(1) bounds with
+ * ignore_prior, as carma_logdensity_batch does.
+ *
+ * carma_bands_create: band b is time / y / yerr [offsets[b], offsets[b+1]) (offsets[0] = 0, every band holds at least one
+ *   datum, at least 2 in all), sorted and de-duplicated per band as carma_ctx_create does; 1 <= nbands <= CARMA_KBANDS_MAX;
+ *   lag_lo / lag_hi = [nbands - 1], finite (may be NULL for one band); max_stdev bounds ysigma.  Band 0 sets max_freq and
+ *   min_freq (SetPrior on its times): with a single datum in band 0 no parameter vector lies inside those bounds and only
+ *   ignore_prior evaluations are finite.  All argument errors are reported before any device work.  Returns NULL on error.
+ * carma_bands_logdensity_batch: B evaluations, theta = [B][dx], out = [B]; one evaluation per lane (k_logdens_carma_mband), each
+ *   lane merging the bands in the order ITS lags give.  _dev: device pointers, enqueued on `stream`, no synchronisation.
+ * carma_bands_mle_batched: carma_mle_batched on the extended vector: x0 = [B][dx], lo / hi = [dx] (NULL or non-finite entries =
+ *   unbounded; the lag entries are cut to the lag boxes of the handle).  fixed_lag = [B][nbands - 1] or NULL: with it the
+ *   optimiser runs on the dx - (nbands - 1) other variables and every evaluation of start i is made at the lags fixed_lag[i]
+ *   (the lag entries of x0, lo and hi are not read); x = [B][dx] carries those lags unchanged.  status as carma_mle_batched.
+ */
+#define CARMA_KBANDS_MAX 8
+typedef struct carma_bands carma_bands;
+carma_bands* carma_bands_create(const double* time, const double* y, const double* yerr, const long* offsets /* [K+1] */,
+                                int nbands, int p, int q, const double* lag_lo /* [K-1] */, const double* lag_hi /* [K-1] */,
+                                double max_stdev, int device);
+void carma_bands_destroy(carma_bands* h);
+int carma_bands_dim(const carma_bands* h);              /* dx */
+int carma_bands_nbands(const carma_bands* h);
+int carma_bands_n(const carma_bands* h, int b);         /* length of band b after sort/dedup */
+int carma_bands_get_prior(const carma_bands* h, double* out3 /* max_stdev, max_freq, min_freq */);
+int carma_bands_logdensity_batch(carma_bands* h, const double* theta /* [B][dx] */, int B, int ignore_prior, double* out);
+int carma_bands_logdensity_batch_dev(carma_bands* h, const double* d_theta, int B, int ignore_prior, double* d_out,
+                                     void* stream);
+int carma_bands_mle_batched(carma_bands* h, const double* x0 /* [B][dx] */, int B, const double* lo /* [dx] */,
+                            const double* hi /* [dx] */, const double* fixed_lag /* [B][K-1] or NULL */, int maxiter, int mem,
+                            double ftol, double gtol, double fd_step, int ignore_prior, double* x, double* fun, int* nit,
+                            int* nfev, int* status);
+
+/*
  * The parallel-tempering sampler over MANY SERIES (the carma_pt_* set on a carma_mctx).  A RUN is one sampler -- nreplicas
  * independent ladders of ntemps chains -- on one series of the context; a call takes M runs, series = [M] (an index may repeat,
  * any order).  All runs advance in the same launches: one chain per lane, the bookkeeping kernels of the large-ensemble sampler
