@@ -201,12 +201,25 @@ __global__ __launch_bounds__(256) void k_logdens_carma_w(const double* __restric
 // The TWO-SIDED window pipeline (round 6): an evaluation takes TWO DPP rows -- the even row filters the first half of the series
 // forward, the odd row the second half backward (carma_pipew.h, TS), and the two states are merged at the meeting time -- so the
 // serial chain of kfilter.cpp:189-215 is half as long.  Two evaluations per workgroup.
-// Which wave plays which part: as k_logdens_carma_w.  (Measured and dropped, profiles/r06/w2_check_v2.txt: with two workgroups per
-// CU, two producer waves per workgroup on the SIMDs without a recursion wave and the set-up wave idle -- one producer then makes two
-// passes per chunk, and the recursion wave waits for it: 28.0 against 25.1 us per 1024 evaluations.)
+// Which wave plays which part: as k_logdens_carma_w.
 // HO: the producers' schedule hand-over (carma_pipew.h, SSCHED) -- launches of more than one workgroup per CU.
 // SL: the series in LDS (up to W2_MAX_N data); without, a longer series is read from global memory through the rows' register windows.
-template <int P, bool HO, bool SL = true>
+// FOLD (odd orders, launches of more than one and at most two workgroups per CU): with two workgroups on a CU the launch runs out of
+// VALU issue slots on the SIMDs that hold a recursion wave, whose chunk time is set by what shares its SIMD -- and with three
+// producer passes per chunk that was a whole pass of the other workgroup.  (First attempt, measured and dropped,
+// profiles/r06/w2_check_v2.txt: two producer waves per workgroup on the SIMDs without a recursion wave and the set-up wave idle --
+// one producer then made two of the three passes, and the recursion wave waited for it: 28.0 against 25.1 us per 1024 evaluations.
+// The blocker was the pass count, not the placement.)  Now the single real root rides in the lane of the slot's last pair
+// (carma_pipew.h, FOLD), two passes cover a chunk, and a workgroup is: recursion wave, a LIGHT wave (schedule, data slots, header;
+// prior at the end) and two producers of one pass each.  The waves of a workgroup go to SIMDs (s, s + 2, s + 1, s + 3) and the CU's
+// second workgroup starts one place further on in that sequence (profiles/r08/wave_placement.txt): wave i of the second shares a
+// SIMD with wave i + 1 of the first, so with parts 0, 1, 2, 3 (0xE4) in the first and 0, 2, 3, 1 (0x78) in the second each recursion
+// wave sits beside the OTHER workgroup's light wave and the two remaining SIMDs hold one producer of each: 21.28 -> 20.54 us per 1024
+// evaluations at p = 5, 24.77 -> 23.73 at p = 7 (profiles/r08/README.md).  What remains: three workgroups per CU keep the three-pass
+// form -- with three recursion waves on four SIMDs one of them has heavy company: the third workgroup's recursion wave beside two
+// folded passes (its table 0xE4 again) took 29.1 against 27.9 us per 1280 evaluations, beside a recursion and a light wave (0x4E)
+// 28.2 against 28.0 -- and so do p = 3 (below the bar, w2_fold_order) and the even orders, where there is no single root to fold.
+template <int P, bool HO, bool SL = true, bool FOLD = false>
 __global__ __launch_bounds__(256) void k_logdens_carma_w2(const double* __restrict__ theta, int B, int d, int q,
                                                           const double4* __restrict__ series, int n, Prior pr,
                                                           int ignore_prior, double* __restrict__ out, int ncu)
@@ -214,7 +227,7 @@ __global__ __launch_bounds__(256) void k_logdens_carma_w2(const double* __restri
     extern __shared__ double4 smem4[];
     const int tid = threadIdx.x, lane64 = tid & 63;
     const int round = (blockIdx.x >= (unsigned)ncu) + (blockIdx.x >= 2u * (unsigned)ncu);
-    const int wave = ((round == 0 ? 0xE4 : round == 1 ? 0xD2 : 0x36) >> (2 * (tid >> 6))) & 3;
+    const int wave = ((FOLD ? (round == 0 ? 0xE4 : 0x78) : (round == 0 ? 0xE4 : round == 1 ? 0xD2 : 0x36)) >> (2 * (tid >> 6))) & 3;
     Grp<16> g{nullptr, lane64, nullptr};
     double2* ring = reinterpret_cast<double2*>(smem4);
     long e = ((long)blockIdx.x * 64 + lane64) / 32;
@@ -271,24 +284,24 @@ __global__ __launch_bounds__(256) void k_logdens_carma_w2(const double* __restri
     }
     if (wave >= 2) {
 #if defined(CARMA_STAMPS)
-        pipew_produce<P, true, SL, HO>(g, wave - 2, th, series, n, ring, [](int) {}, mark_, lds_t, lds_yz);
+        pipew_produce<P, true, SL, HO, FOLD>(g, wave - 2, th, series, n, ring, [](int) {}, mark_, lds_t, lds_yz);
         CARMA_MARK_DUMP("two-sided producer: barrier 1 arrival, passed, chunk 0 done, barrier passed, chunk 1 done, chunk 2 done", wave - 2);
 #else
-        pipew_produce<P, true, SL, HO>(g, wave - 2, th, series, n, ring, [](int) {}, nullptr, lds_t, lds_yz);
+        pipew_produce<P, true, SL, HO, FOLD>(g, wave - 2, th, series, n, ring, [](int) {}, nullptr, lds_t, lds_yz);
 #endif
         __syncthreads();                                      // (the set-up wave's hand-over, below)
         return;
     }
     Model<P> m;
     if (wave == 1) {
-        // the third producer FIRST -- prior bounds and log prior (carpack.hpp:118-126, 178-191; carpack.cpp:314-374) are wanted at the
+        // the third producer (FOLD: the light wave) FIRST -- prior bounds and log prior (carpack.hpp:118-126, 178-191; carpack.cpp:314-374) are wanted at the
         // very end only, and in front of the pipeline they kept the first chunk waiting (the other waves were at the first barrier
         // 3.5 k cycles before this one: profiles/r06/w2_stamps_v3.txt); now they run while the recursion wave merges
 #if defined(CARMA_STAMPS)
-        pipew_produce<P, true, SL, HO>(g, 2, th, series, n, ring, [](int) {}, mark_, lds_t, lds_yz);
+        pipew_produce<P, true, SL, HO, FOLD>(g, 2, th, series, n, ring, [](int) {}, mark_, lds_t, lds_yz);
         CARMA_MARK_DUMP("two-sided set-up wave: barrier 1 arrival, passed, chunk 0 done, barrier passed, chunk 1 done, chunk 2 done", 2);
 #else
-        pipew_produce<P, true, SL, HO>(g, 2, th, series, n, ring, [](int) {}, nullptr, lds_t, lds_yz);
+        pipew_produce<P, true, SL, HO, FOLD>(g, 2, th, series, n, ring, [](int) {}, nullptr, lds_t, lds_yz);
 #endif
         model_from_theta<P, 16, MODEL_FLAGS>(g, th, q, pr, ignore_prior, m);
         const double lpri = log_prior(m.scale, pr.measerr_dof);
@@ -759,6 +772,10 @@ static long win2_max_evals()
 static bool win_forced() { return tune_get(TUNE_WIN_ROWS) != TUNE_UNSET; }
 // longest series the two-sided kernel keeps in LDS beside its rings (24 bytes a datum; 5000: 137 KiB, one workgroup per CU)
 constexpr int W2_MAX_N = 5000;
+// Orders whose two-workgroups-per-CU launches take the folded two-pass form of the two-sided kernel (k_logdens_carma_w2, FOLD).
+// p = 3 folds as well (one lane per slot, one pass covers the chunk) and was 0.44 us ahead at 1024 evaluations, 17.09 -> 16.64 us --
+// short of five times the runs' own spread of 0.09 us, so it keeps the three-pass form.
+constexpr bool w2_fold_order(int p) { return p == 5 || p == 7; }
 // smallest launch that takes one evaluation per lane (measured: tools/tput_probe.py; CARMA_TUNE_LANE_MIN overrides, read once)
 static long lane_min_evals(int p = 5)
 {
@@ -891,7 +908,12 @@ static hipError_t launch_logdens_p(const double* theta, int B, int d, int q, con
                 return hipGetLastError();
             };
             if (!sl) return go(&k_logdens_carma_w2<P, false, false>);
-            return wgs > device_cus() ? go(&k_logdens_carma_w2<P, true>) : go(&k_logdens_carma_w2<P, false>);
+            if (wgs <= device_cus()) return go(&k_logdens_carma_w2<P, false>);
+            // two workgroups per CU, odd orders: two folded producer passes and a light wave beside the neighbour's recursion wave
+            if constexpr (w2_fold_order(P)) {
+                if (wgs <= 2L * device_cus()) return go(&k_logdens_carma_w2<P, true, true, true>);
+            }
+            return go(&k_logdens_carma_w2<P, true>);
         }
         case LdShape::PC1: return launch_pc(&k_logdens_carma_pc<P, G, 1>, waves, 1);
         case LdShape::PC2: return launch_pc(&k_logdens_carma_pc<P, G, 2>, waves, 2);

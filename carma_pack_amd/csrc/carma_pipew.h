@@ -88,7 +88,35 @@ struct PipeWGeom {
 // SLDS (the two-sided log-density kernel): the series is in LDS -- times lds_t[n_all], {y, yerr^2} lds_yz[n_all], copied by the kernel,
 // visible behind the first barrier -- and a chunk's records are read where they are needed; elsewhere each row keeps a window of 64
 // records in registers (below).
-template <int P, bool TS = false, bool SLDS = false, bool HANDOVER = false, class Tail>
+// FOLD (odd P, the two-sided log-density kernel where two workgroups share a CU): without it the third "pair" lane of a slot holds the
+// single real root and runs a whole exp + sincos stream for one entry, which makes PPL = 5 slots per pass at P = 5 and three passes for
+// the chunk's ND + 1 = 12 slots.  With it the lane of a slot's LAST pair takes the single root as well (exp_step_tab_exact below: the
+// same operations on the same operands as that lane performed, so every entry keeps its bits), a slot is P / 2 lanes, and TWO passes
+// cover the chunk: pw 0 and 1 produce one pass each, pw 2 is a LIGHT wave -- the schedule and its hand-over, the data slots, the
+// header, the virtual lanes' constant entries -- which is what the kernel puts beside the other workgroup's recursion wave.
+//
+// The single root's exponential: the REAL half of cexp_step_tab_impl<false, true> (carma_math.h) -- what that function returns in *re
+// when b = 0, where its cosine is exactly 1; its *im is then e * (+0), formed by the caller.  (A wave whose ballot sends it through
+// cexp_step_tab_impl<true, true> performs these operations as well on a lane with b = 0: the result does not depend on the ballot.)
+CARMA_DEV double exp_step_tab_exact(double a, double dt, const double* tab)
+{
+    const double x = a * dt;
+    const double n1 = rint(x * INV_LN2_32);
+    double r = fma3(-n1, LN2_32_HI, x);
+    r = fma3(-n1, LN2_32_LO, r);
+    r += fma3(a, dt, -x);
+    const int i1 = (int)fmin(fmax(n1, -70400.0), 70400.0);
+    const double e0 = tab[i1 & 31];
+    double pe = 1.0 / 720.0;
+    pe = fma3(pe, r, 1.0 / 120.0);
+    pe = fma3(pe, r, 1.0 / 24.0);
+    pe = fma3(pe, r, 1.0 / 6.0);
+    pe = fma3(pe, r, 0.5);
+    pe = fma3(pe, r, 1.0);
+    return ldexp(fma3(e0, pe * r, e0), i1 >> 5);
+}
+
+template <int P, bool TS = false, bool SLDS = false, bool HANDOVER = false, bool FOLD = false, class Tail>
 __device__ __forceinline__ void pipew_produce(const Grp<16>& g, int pw, const double* __restrict__ theta,
                                               const double4* __restrict__ series, int n_all, double2* __restrict__ ring, Tail&& tail,
                                               long long* mk = nullptr, const double* __restrict__ lds_t = nullptr,
@@ -97,18 +125,21 @@ __device__ __forceinline__ void pipew_produce(const Grp<16>& g, int pw, const do
     using Geo = PipeWGeom<P>;
     constexpr int ND = Geo::ND, NB = Geo::NB, ENT = Geo::ENT;
     if (CARMA_PRIO_P != 0) __builtin_amdgcn_s_setprio(CARMA_PRIO_P);
-    // a lane works on a conjugate PAIR of roots (jr, jr + 1) of one slot: both share |E|, cos and sin
-    constexpr int NPAIR = (P + 1) / 2, PPL = 16 / NPAIR;
-    constexpr int NPROD = Geo::NPROD;
+    static_assert(!FOLD || ((P & 1) && P >= 3 && TS && SLDS && HANDOVER), "the folded form: odd orders of the two-sided kernel with the hand-over");
+    // a lane works on a conjugate PAIR of roots (jr, jr + 1) of one slot: both share |E|, cos and sin (FOLD: the last pair's lane on the single root too)
+    constexpr int NPAIR = FOLD ? P / 2 : (P + 1) / 2, PPL = 16 / NPAIR;
+    constexpr int NPROD = FOLD ? 2 : Geo::NPROD;              // (FOLD: the waves that make a pass; pw = 2 makes none)
     // which producer forms the data slots {scale yerr^2, y - mu}: in the two-sided log-density kernel the third one -- the set-up wave,
     // which has nothing else in front of the pipeline there -- so that producer 0 (header, the virtual lanes' constant entries) is
     // not the one the others wait for; elsewhere producer 0
     constexpr int PWD = TS ? 2 : 0;
+    constexpr int PWH = FOLD ? 2 : 0;                         // header and the virtual lanes' constant entries (FOLD: the light wave's)
     constexpr int NIT = (ND + 1 + NPROD * PPL - 1) / (NPROD * PPL);   // slot ND is the re-base rotation
     const double* tab = reinterpret_cast<const double*>(ring + Geo::TAB_OFF);
     const int lane = g.lane64, l = lane & 15, rowb = lane & ~15, q = lane >> 4;
     const int sub = l / NPAIR, jr = 2 * (l - sub * NPAIR);
-    const bool worker = sub < PPL, two = jr + 1 < P;
+    const bool worker = sub < PPL, two = FOLD ? true : jr + 1 < P;     // (FOLD: every lane has a pair)
+    const bool fold = FOLD && jr == P - 3;                    // the lane of the slot's last pair: the single root is its as well
     // the part of the series this row works on
     const bool bwd = TS && (q & 1);
     const int nfwd = (n_all + 1) / 2;
@@ -153,6 +184,11 @@ __device__ __forceinline__ void pipew_produce(const Grp<16>& g, int pw, const do
         w.im = -w.im;
         w1.im = -w1.im;
     }
+    Cx ws = {0.0, 0.0};                                       // FOLD: the single root
+    if constexpr (FOLD) {
+        ws = own_ar_root<P>(theta, P - 1);
+        if (bwd) ws.im = -ws.im;
+    }
     int esig = 0;                                             // binary exponent of sigma_y (rescaling, carma_pipe3l.h)
     {
         const double sg = fabs(theta[0]);
@@ -162,7 +198,7 @@ __device__ __forceinline__ void pipew_produce(const Grp<16>& g, int pw, const do
     const double mu = theta[2], scale = theta[1];
     const bool realpair = two && w.im == 0.0;
     // the virtual lanes' entries never change: hh = e_s, c~ = 0, {1, 0} in the data slot
-    if (pw == 0 && l >= ND) {
+    if (pw == PWH && l >= ND) {
 #pragma unroll
         for (int b = 0; b < NB; b++) {
 #pragma unroll
@@ -173,6 +209,11 @@ __device__ __forceinline__ void pipew_produce(const Grp<16>& g, int pw, const do
     // grid of this evaluation's re-base schedule (carma_pipe3l.h): cells of width 2^-ex
     double wl = fmax(fmax(fabs(w.re), fabs(w1.re)) * (1.0 / Geo::LIM_RE), fabs(w.im) * (1.0 / Geo::LIM_IM));
     wl = (wl < 1e12) ? wl : ((wl == wl && wl < 1.0 / 0.0) ? 1e12 : 0.0);
+    if constexpr (FOLD) {                                     // (what the single root's own lane brought to the maximum)
+        double wls = fmax(fabs(ws.re) * (1.0 / Geo::LIM_RE), fabs(ws.im) * (1.0 / Geo::LIM_IM));
+        wls = (wls < 1e12) ? wls : ((wls == wls && wls < 1.0 / 0.0) ? 1e12 : 0.0);
+        wl = fmax(wl, wls);
+    }
     wl = Grp<16>::max(wl);
     int wex;
     (void)frexp(wl, &wex);
@@ -184,6 +225,8 @@ __device__ __forceinline__ void pipew_produce(const Grp<16>& g, int pw, const do
         rg1 = exp_neg(w1.re * halfw);
         g1 = recip(rg1);
     }
+    double gS = 1.0;
+    if constexpr (FOLD) gS = recip(exp_neg(ws.re * halfw));
     // schedule state of this row (row-uniform)
     int j0 = 0;
     double base = t_first;                                    // (SLDS: read behind the first barrier, below)
@@ -205,6 +248,7 @@ __device__ __forceinline__ void pipew_produce(const Grp<16>& g, int pw, const do
     double2 dslot = make_double2(1.0, 0.0);                   // {scale yerr^2, y - mu} of this lane's datum (producer PWD)
     unsigned long long rbits = 0ull;
     double ecv[NIT], esv[NIT], e1v[NIT];
+    double exv[NIT];                                          // (FOLD: the single root's)
     auto sched = [&](bool finflag) __attribute__((always_inline)) {
         // --- schedule of this row's chunk: lane s looks at datum j0 + s
         jc = j0;
@@ -287,7 +331,10 @@ __device__ __forceinline__ void pipew_produce(const Grp<16>& g, int pw, const do
         dt_rot = s1.x;
     };
     auto exps = [&]() __attribute__((always_inline)) {
-        if (pw == 0) rbits = __ballot(rot);
+        if (pw == PWH) rbits = __ballot(rot);
+        if constexpr (FOLD) {
+            if (pw >= NPROD) return;                          // (wave-uniform: the light wave makes no pass)
+        }
 #pragma unroll
         for (int it = 0; it < NIT; it++) {
             const int slot = it * NPROD * PPL + pw * PPL + sub;
@@ -307,6 +354,7 @@ __device__ __forceinline__ void pipew_produce(const Grp<16>& g, int pw, const do
             ecv[it] = ec;
             esv[it] = es;
             e1v[it] = e1;
+            if constexpr (FOLD) exv[it] = (fold && live) ? exp_step_tab_exact(ws.re, dt, tab) : 1.0;
         }
     };
     PIPEW_MARK(1);
@@ -316,9 +364,18 @@ __device__ __forceinline__ void pipew_produce(const Grp<16>& g, int pw, const do
         base = tsgn * lds_t[sidx(0)];
         t_meet = tsgn * lds_t[nfwd - 1];
     }
-    double2 hc_own, hc_par;
+    double2 hc_own, hc_par, hc_s = make_double2(0.0, 0.0);
     {
         const double2* cst = ring + Geo::CONST_OFF + rowb;
+        if constexpr (FOLD) {                                 // the single root's (its partner is the idle lane P: zeros, |h_own| alone sets the power of two)
+            hc_s = cst[P - 1];
+            const double ms = fabs(hc_s.x);
+            int es_;
+            (void)frexp(ms, &es_);
+            if (!(ms > 0.0 && ms < 1.0 / 0.0)) es_ = 0;
+            hc_s = make_double2(ldexp(hc_s.x, esig - es_), ldexp(hc_s.y, es_ - esig));
+            if (bwd) hc_s = make_double2(hc_s.y, hc_s.x);
+        }
         hc_own = cst[jr];
         hc_par = cst[jr + 1 < 16 ? jr + 1 : 15];
         // every coordinate rescaled by an exact power of two so that |h_r| ~ sigma_y (carma_pipe3l.h)
@@ -352,10 +409,11 @@ __device__ __forceinline__ void pipew_produce(const Grp<16>& g, int pw, const do
             sched_get(b);
         exps();
         // --- the chunk's header, data slots and entries
-        if (pw == 0 && lane == 0)
+        if (pw == PWH && lane == 0)
             reinterpret_cast<unsigned long long*>(ring + Geo::HDR_OFF)[b] =
                 ((rbits & 1ull) | ((rbits >> 15) & 2ull) | ((rbits >> 30) & 4ull) | ((rbits >> 45) & 8ull)) | ((TS ? fin : last) ? 256ull : 0ull);
         if (pw == PWD && l < ND) ring[Geo::RING_OFF + (b * ENT + P) * 64 + lane] = dslot;
+        if (!FOLD || pw < NPROD) {
 #pragma unroll
         for (int it = 0; it < NIT; it++) {
             const int slot = it * NPROD * PPL + pw * PPL + sub;
@@ -377,6 +435,18 @@ __device__ __forceinline__ void pipew_produce(const Grp<16>& g, int pw, const do
                     const double cp = fma(gc1, hc_par.y, -gs1 * hc_own.y) * inv1;
                     dst[64] = live ? make_double2(hp, cp) : make_double2(0.0, 0.0);
                 }
+                if constexpr (FOLD) {
+                    // the single root: (ex, ex * 0) is what cexp_step_tab<true> gave its lane -- the sine exactly +0 -- and the idle lane
+                    // P's constants, its "partner", are zeros; the expressions of a pair's first member above, operand by operand
+                    if (fold) {
+                        const double ex = exv[it], ez = ex * 0.0;
+                        const double gcs = ex * gS, gss = ez * gS;
+                        const double invs = recip(fma(gcs, gcs, gss * gss));
+                        const double hts = fma(gcs, hc_s.x, gss * 0.0);
+                        const double cts = fma(gcs, hc_s.y, gss * 0.0) * invs;
+                        dst[128] = live ? make_double2(hts, cts) : make_double2(0.0, 0.0);
+                    }
+                }
             }
             if (worker && is_rot) {                           // rotation over the closing window (identity when there is none)
                 double2* dst = ring + Geo::ROT_OFF + (b * P + jr) * 4 + q;
@@ -384,7 +454,15 @@ __device__ __forceinline__ void pipew_produce(const Grp<16>& g, int pw, const do
                 const double f0 = fin ? g0 : 1.0, f1 = fin ? g1 : 1.0;
                 dst[0] = make_double2(ec * f0, es * f0);
                 if (two) dst[4] = make_double2(e1 * f1, -es * f1);
+                if constexpr (FOLD) {
+                    if (fold) {
+                        const double ex = exv[it], ez = ex * 0.0;
+                        const double fS = fin ? gS : 1.0;
+                        dst[8] = make_double2(ex * fS, ez * fS);
+                    }
+                }
             }
+        }
         }
 #if defined(CARMA_WIN_STAMPS)
         WIN_STAMP(ps_t1);
