@@ -196,14 +196,6 @@ void set_prior_bounds(Prior& pr, const double* t, long n, double max_stdev)
     pr.min_freq = 1.0 / (*std::max_element(t, t + n) - *std::min_element(t, t + n));
 }
 
-// SERIES_REPEATED_DT of packed records (pack_series): >= 25 % of the time steps equal their predecessor
-bool series_repeated_dt(const double* packed, long n)
-{
-    long rep = 0;
-    for (long k = 2; k < n; k++) rep += (packed[4 * (size_t)k] == packed[4 * (size_t)(k - 1)]);
-    return n > 8 && 4 * rep >= n;
-}
-
 int select_device(int device)
 {
     int cnt = 0;
@@ -293,24 +285,7 @@ carma_ctx* carma_ctx_create(const double* time, const double* y, const double* y
     c->pr.measerr_dof = 50.0;   // src/include/carpack.hpp:63
     carma_ctx_set_prior(reinterpret_cast<carma_ctx*>(c), max_stdev);
     std::vector<double> s = pack_series(c->t, c->y, c->yerr);
-    c->repeated_dt = series_repeated_dt(s.data(), c->n);
-    if (p >= 2) {
-        // SERIES_WINDOW_OK (carma_types.h): spans of 16 - p consecutive data against the shortest window the prior admits
-        const int ND = 16 - p;
-        const double wmin = 0.5 * 600.0 / (6.283185307179586 * c->pr.max_freq);       // Pipe3LGeom::LIM_RE; the grid halves it at worst
-        long over = 0, tot = 0;
-        for (int k = 0; k + ND - 1 < c->n; k++, tot++) over += (c->t[k + ND - 1] - c->t[k]) > wmin;
-        c->window_ok = tot > 0 && 10 * over <= tot;
-        // SERIES_WINDOW2_OK / _SMALL: chunks of the row with the shortest window against ceil(n / ND)
-        long chunks = 0;
-        for (int k = 0; k < c->n; chunks++) {
-            int j = k;
-            while (j + 1 < c->n && j + 1 - k < ND && c->t[j + 1] - c->t[k] <= wmin) j++;
-            k = j + 1;
-        }
-        const double r = (double)chunks / (double)((c->n + ND - 1) / ND);
-        c->window2 = r <= 2.0 ? 2 : (r <= 3.5 ? 1 : 0);
-    }
+    c->sflags = series_flags(c->t.data(), c->n, p, c->pr.max_freq);
     hipError_t e = dev_malloc(&c->d_series, sizeof(double) * s.size());
     if (e == hipSuccess) e = hipMemcpy(c->d_series, s.data(), sizeof(double) * s.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);

@@ -62,14 +62,8 @@ struct Ctx {
     int p = 0, q = 0, d = 0, n = 0;
     std::vector<double> t, y, yerr;   // after sort/dedup
     Prior pr{};
-    bool repeated_dt = false;         // >= 25 % of the time steps equal their predecessor (regular cadence)
-    bool window_ok = false;           // the series suits the windowed wave pipeline (carma_capi.hip, carma_ctx_create)
-    int window2 = 0;                  // the TWO-SIDED window pipeline: 2 = suits it, 1 = with a CU per workgroup only (carma_types.h)
-    int series_flags() const
-    {
-        return (repeated_dt ? SERIES_REPEATED_DT : 0) | (window_ok ? SERIES_WINDOW_OK : 0) | (window2 == 2 ? SERIES_WINDOW2_OK : 0) |
-               (window2 >= 1 ? SERIES_WINDOW2_SMALL : 0);
-    }
+    int sflags = 0;                   // SERIES_* of the series under the prior (series_flags, carma_shape_plan.h)
+    int series_flags() const { return sflags; }
     double* d_series = nullptr;       // records {dt, y, yerr^2, t}[n + 16 pads], then yerr^2[n + 16], y[n + 16] (carma_types.h)
     double* d_theta = nullptr;        // staging for the host-pointer entry points
     double* d_out = nullptr;
@@ -85,7 +79,6 @@ void set_error(const char* fmt, ...);
 void sort_dedup(std::vector<double>& t, std::vector<double>& y, std::vector<double>& e);
 std::vector<double> pack_series(const std::vector<double>& t, const std::vector<double>& y, const std::vector<double>& e);
 void set_prior_bounds(Prior& pr, const double* t, long n, double max_stdev);
-bool series_repeated_dt(const double* packed, long n);
 int hip_fail(hipError_t e, const char* what);
 int select_device(int device);
 void pt_state_free(Ctx* c);

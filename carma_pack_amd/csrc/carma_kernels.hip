@@ -702,22 +702,19 @@ int device_cus()
     return n;
 }
 
-// Largest launch (in workgroups of four evaluations) that takes the wave pipeline of carma_pipe3l.h: three workgroups
-// per CU (measured, tools/tput_probe.py).  CARMA_TUNE_P3L_ROWS overrides it for such measurements; read once.
-static long p3l_max_rows()
-{
-    static const long tune = [] {
-        const char* e = getenv("CARMA_TUNE_P3L_ROWS");
-        return e ? atol(e) : -1L;
-    }();
-    return tune >= 0 ? tune : 3L * device_cus();      // three workgroups per CU (registers and LDS allow exactly that)
-}
-
-// Launch shape for B evaluations of order P (one table for the launcher and for carma_logdensity_kernel_name)
-enum class LdShape { P3L, PC1, PC2, PLAIN1, PLAIN4, LANE, LPC, WIN, WIN2 };
 // The launch-shape switches (carma_launch.h): environment read once, atomics afterwards.
-static const char* const TUNE_NAMES[TUNE_COUNT] = {"CARMA_TUNE_WIN_ROWS", "CARMA_TUNE_WIN2_EVALS", "CARMA_TUNE_PT_ROW_WIN",
-                                                    "CARMA_TUNE_CSIM_CHUNK_PATHS", "CARMA_TUNE_SMOOTH_CHUNK_MODELS"};
+enum TuneParse { TP_DEC, TP_HEX, TP_FLAG };
+struct TuneEntry {
+    const char* env;             // the environment variable; carma_tune_set takes it whole or from `skip` on
+    int skip;
+    TuneParse parse;
+};
+static const TuneEntry TUNE_TAB[TUNE_COUNT] = {
+    {"CARMA_TUNE_WIN_ROWS", 11, TP_DEC},          {"CARMA_TUNE_WIN2_EVALS", 11, TP_DEC},          {"CARMA_TUNE_PT_ROW_WIN", 11, TP_DEC},
+    {"CARMA_TUNE_CSIM_CHUNK_PATHS", 11, TP_DEC},  {"CARMA_TUNE_SMOOTH_CHUNK_MODELS", 11, TP_DEC}, {"CARMA_TUNE_P3L_ROWS", 11, TP_DEC},
+    {"CARMA_TUNE_LANE_MIN", 11, TP_DEC},          {"CARMA_TUNE_LPC_MIN", 11, TP_DEC},             {"CARMA_TUNE_LPC_MAX", 11, TP_DEC},
+    {"CARMA_TUNE_LPC_ROT", 11, TP_DEC},           {"CARMA_TUNE_CAR1_SCAN_MAX", 11, TP_DEC},       {"CARMA_TUNE_PT_ROW_WGS_PER_CU", 11, TP_DEC},
+    {"CARMA_TUNE_PT_ROW_ROT", 11, TP_HEX},        {"CARMA_TUNE_PT_ROW_XCD_MAP", 11, TP_DEC},      {"CARMA_PT_PLAIN", 6, TP_FLAG}};
 static std::atomic<long> g_tune[TUNE_COUNT];
 static std::atomic<int> g_tune_init{0};
 static void tune_init()
@@ -726,8 +723,10 @@ static void tune_init()
     int expect = 0;
     if (g_tune_init.compare_exchange_strong(expect, 1)) {
         for (int i = 0; i < TUNE_COUNT; i++) {
-            const char* e = getenv(TUNE_NAMES[i]);
-            g_tune[i].store(e ? atol(e) : TUNE_UNSET, std::memory_order_relaxed);
+            const char* e = getenv(TUNE_TAB[i].env);
+            const TuneParse ps = TUNE_TAB[i].parse;
+            const long v = !e ? TUNE_UNSET : ps == TP_HEX ? strtol(e, nullptr, 16) : ps == TP_FLAG ? (e[0] == '1' ? 1L : 0L) : atol(e);
+            g_tune[i].store(v, std::memory_order_relaxed);
         }
         g_tune_init.store(2, std::memory_order_release);
     } else {
@@ -744,94 +743,36 @@ int tune_set(const char* name, long value)
     if (!name) return -1;
     tune_init();
     for (int i = 0; i < TUNE_COUNT; i++)
-        if (!strcmp(name, TUNE_NAMES[i]) || !strcmp(name, TUNE_NAMES[i] + 11)) {       // (+ 11: behind "CARMA_TUNE_")
+        if (!strcmp(name, TUNE_TAB[i].env) || !strcmp(name, TUNE_TAB[i].env + TUNE_TAB[i].skip)) {   // (+ skip: behind "CARMA_TUNE_")
             g_tune[i].store(value, std::memory_order_relaxed);
             return 0;
         }
     return -1;
 }
-// Largest launch (in workgroups of four evaluations) that takes the windowed wave pipeline (carma_pipew.h): one workgroup per CU
-// (measured per order at 1024 evaluations, profiles/r05/window_pipeline_v1.txt: 1-10 % ahead of the one-datum pipeline; with two
-// or three workgroups per CU that one is ahead).  CARMA_TUNE_WIN_ROWS overrides (0: never, also for the two-sided kernel), so that
-// one test process can run both pipelines (carma_tune_set).
-static long win_max_rows()
+ShapeSwitches shape_switches()
 {
-    const long v = tune_get(TUNE_WIN_ROWS);
-    return v != TUNE_UNSET ? v : (long)device_cus();
+    tune_init();
+    auto v = [](int i) { return g_tune[i].load(std::memory_order_relaxed); };
+    ShapeSwitches sw;
+    sw.win_rows = v(TUNE_WIN_ROWS), sw.win2_evals = v(TUNE_WIN2_EVALS), sw.pt_row_win = v(TUNE_PT_ROW_WIN);
+    sw.p3l_rows = v(TUNE_P3L_ROWS), sw.lane_min = v(TUNE_LANE_MIN), sw.lpc_min = v(TUNE_LPC_MIN), sw.lpc_max = v(TUNE_LPC_MAX);
+    sw.lpc_rot = v(TUNE_LPC_ROT), sw.car1_scan_max = v(TUNE_CAR1_SCAN_MAX), sw.pt_row_wgs_per_cu = v(TUNE_PT_ROW_WGS_PER_CU);
+    sw.pt_row_rot = v(TUNE_PT_ROW_ROT), sw.pt_row_xcd_map = v(TUNE_PT_ROW_XCD_MAP), sw.pt_plain = v(TUNE_PT_PLAIN);
+    return sw;
 }
-// Largest launch (in EVALUATIONS) that takes the two-sided window pipeline: three workgroups of two evaluations per CU (measured
-// per order, profiles/r06/w2_sizes_v1.txt: p = 5 at 1280 / 1536 evaluations 29.6 us against the one-datum pipeline's 35.3 / 35.4,
-// p = 7 34.4 against 37.4, p = 3 23.6 against 26.9; at 2048 -- four per CU -- 38.2 against 35.5, 47.8 against 37.5, 31.3 against 27.0).
-// CARMA_TUNE_WIN2_EVALS overrides (0: never).
-static long win2_max_evals()
-{
-    const long v = tune_get(TUNE_WIN2_EVALS);
-    return v != TUNE_UNSET ? v : 6L * device_cus();
-}
-// (an override of CARMA_TUNE_WIN_ROWS also lifts the series criterion: the tests force the window pipelines onto series that fail it)
-static bool win_forced() { return tune_get(TUNE_WIN_ROWS) != TUNE_UNSET; }
-// longest series the two-sided kernel keeps in LDS beside its rings (24 bytes a datum; 5000: 137 KiB, one workgroup per CU)
-constexpr int W2_MAX_N = 5000;
-// Orders whose two-workgroups-per-CU launches take the folded two-pass form of the two-sided kernel (k_logdens_carma_w2, FOLD).
-// p = 3 folds as well (one lane per slot, one pass covers the chunk) and was 0.44 us ahead at 1024 evaluations, 17.09 -> 16.64 us --
-// short of five times the runs' own spread of 0.09 us, so it keeps the three-pass form.
-constexpr bool w2_fold_order(int p) { return p == 5 || p == 7; }
-// smallest launch that takes one evaluation per lane (measured: tools/tput_probe.py; CARMA_TUNE_LANE_MIN overrides, read once)
-static long lane_min_evals(int p = 5)
-{
-    static const long tune = [] {
-        const char* e = getenv("CARMA_TUNE_LANE_MIN");
-        return e ? atol(e) : -1L;
-    }();
-    if (tune >= 0) return tune;
-    // (p = 7, one producer-wave workgroup per CU: the lane-group kernel keeps 16 385 ... 28 671 evaluations -- 257 us at 24 576
-    // against 309 for the lone wave; 374 against 323 at 32 768: profiles/r04/lpc_orders_v1.txt)
-    if (p == 7) return 112L * device_cus();
-    return 64L * 4 * device_cus() * 3 / 8;  // 3/8 of a wave per SIMD (24 576 on 256 CUs): 206 vs 212-236 us there
-}
-// Launches (lpc_min, lpc_max] take the lane kernel with producer waves, k_logdens_carma_lpc<P,3> (measured per order:
-// tools/lpc_probe.sh, profiles/r03/lpc_orders_v1.txt).  Below, the lane-group kernels still have at most one wave per SIMD
-// and are faster; above -- more than three workgroups per CU, or more than the registers allow (two at p = 5, 6, one at
-// p = 7) -- the SIMDs are full either way and the plain lane kernel does the same work without the LDS traffic.
-// CARMA_TUNE_LPC_MIN / _MAX override (read once).
-static long lpc_tune(const char* name, long dflt)
-{
-    const char* e = getenv(name);
-    return e ? atol(e) : dflt;
-}
-static int lpc_rot()
-{
-    static const long v = lpc_tune("CARMA_TUNE_LPC_ROT", 0x0202);
-    return (int)v;
-}
+
+// What logdens_plan needs to know about the current device: its CUs and the workgroups of k_logdens_carma_lpc<P,3> a CU holds
+// (registers, LDS), cached per device like device_cus()
 template <int P>
-static long lpc_min_evals()
+static DeviceFacts logdens_facts()
 {
-    static const long v = lpc_tune("CARMA_TUNE_LPC_MIN", -1);
-    if (v >= 0) return v;
-    // Measured per order (profiles/r04/lpc_orders_v1.txt, round 4: with the table-based exp / sincos and the one-basic-block step
-    // the consumer's stream is short enough that for the low orders this kernel wins right above the wave pipeline's range):
-    //   p = 2, 3   from 12 x #CUs evaluations (3073):  50 / 62 us flat up to 16 384 against 62-68 / 67-89 (pair kernel, lane groups)
-    //   p = 4      from 32 x #CUs (8193):              88 us against 90-93
-    //   p >= 5     from 32 x #CUs (8193), as in round 3: below, the lane-group kernel's 104-112 us are ahead of 107-160
-    // Round 5, the consumer takes a ring buffer as one basic block (LaneFactorsRing, UNROLLED: 110 -> 92 us at p = 5):
-    //   p = 5      from 16 x #CUs (4097): 89-90 us flat against 99-103 for the lane groups (8192: 8.0 -> 9.1e7 evals/s)
-    //   p = 4, 6, 7  as before (72 against 71-73; 118 against 104-106; 142 against 109-113: profiles/r05/lpc_min_probe_v1.txt)
-    if (P <= 3) return 12L * device_cus();
-    if (P == 5) return 16L * device_cus();
-    return 32L * device_cus();
-}
-template <int P>
-static long lpc_max_evals()
-{
-    static const long v = lpc_tune("CARMA_TUNE_LPC_MAX", -1);
-    if (v >= 0) return v;
-    // workgroups of this kernel a CU holds (registers, LDS), cached per device like device_cus()
+    DeviceFacts f;
+    f.cus = device_cus();
     static std::atomic<int> blocks[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
         (void)hipGetLastError();
-        return 64L * device_cus();
+        return f;
     }
     int nb = blocks[dev].load(std::memory_order_relaxed);
     if (nb <= 0) {
@@ -842,151 +783,69 @@ static long lpc_max_evals()
         }
         blocks[dev].store(nb, std::memory_order_relaxed);
     }
-    return 64L * (nb < 3 ? nb : 3) * device_cus();
-}
-template <int P>
-static LdShape logdens_shape(long B, int n, int series_flags)
-{
-    constexpr int EPW = 64 / GroupOf<P>::value;       // evaluations per wave of the G-lane kernels
-    const long waves = (B + EPW - 1) / EPW;
-    const long rows = (B + 3) / 4;                    // workgroups with one evaluation per 16-lane DPP row
-    const bool w2ok = (series_flags & SERIES_WINDOW2_OK) || ((series_flags & SERIES_WINDOW2_SMALL) && B <= 2L * device_cus());
-    if (B <= win2_max_evals() && win_max_rows() > 0 && n >= 16 && (w2ok || win_forced()))
-        return LdShape::WIN2;                         // (CARMA_TUNE_WIN_ROWS = 0: no window pipeline of either kind)
-    if (rows <= win_max_rows() && n >= 8 && ((series_flags & SERIES_WINDOW_OK) || win_forced())) return LdShape::WIN;
-    if (rows <= p3l_max_rows() && n >= 8) return LdShape::P3L;
-    if (B > lpc_min_evals<P>() && B <= lpc_max_evals<P>() && n >= 8) return LdShape::LPC;
-    if (B >= lane_min_evals(P)) return LdShape::LANE;
-    // few evaluations in flight: one wave's instruction stream is the run time, so split it (consumer + rho producer,
-    // carma_ring.h).  Beyond 512 waves (two rounds of workgroups) the plain kernel with pair-shared exp/sincos is
-    // ahead: 104 vs 111 us at 6144 evaluations (tools/midrange_probe.py)
-    if (waves <= 256 && n >= 8) return LdShape::PC1;
-    if (waves <= 512 && n >= 8) return LdShape::PC2;
-    return waves <= 2048 ? LdShape::PLAIN1 : LdShape::PLAIN4;
+    f.lpc_blocks = nb;
+    return f;
 }
 
+// logdens_plan (carma_shape_plan.h) decides; this names the instantiation and launches it
 template <int P>
 static hipError_t launch_logdens_p(const double* theta, int B, int d, int q, const double4* series, int n,
                                    const Prior& pr, int ignore_prior, double* out, hipStream_t st, int series_flags)
 {
-    const bool repeated_dt = (series_flags & SERIES_REPEATED_DT) != 0;
     constexpr int G = GroupOf<P>::value;
-    constexpr int EPW = 64 / G;   // evaluations per wave
-    const long waves = ((long)B + EPW - 1) / EPW;
-    const long rows = ((long)B + 3) / 4;
-    auto launch_pc = [&](auto kern, long npairs, int pairs) -> hipError_t {
-        const size_t lds = (size_t)pairs * (128 * sizeof(double4) + RingGeom<P>::BYTES);
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            160 * 1024);
-        if (ea != hipSuccess) return ea;
-        hipLaunchKernelGGL(kern, dim3((unsigned)((npairs + pairs - 1) / pairs)), dim3(128 * pairs), lds, st, theta, B, d, q,
-                           series, n, pr, ignore_prior, out);
+    const DeviceFacts f = logdens_facts<P>();
+    const LdPlan pl = logdens_plan(P, B, n, series_flags, f, shape_switches());
+    const dim3 grid((unsigned)pl.grid), block((unsigned)pl.block);
+    // LDS beyond 64 KiB (and the pair kernels' whatever its size): the kernel's limit is raised before every launch -- once per
+    // process is not enough
+    auto go = [&](auto kern, size_t lds, auto... more) -> hipError_t {
+        if (lds > 64 * 1024 || pl.shape == LdShape::PC) {
+            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (ea != hipSuccess) return ea;
+        }
+        hipLaunchKernelGGL(kern, grid, block, lds, st, theta, B, d, q, series, n, pr, ignore_prior, out, more...);
         return hipGetLastError();
     };
-    switch (logdens_shape<P>(B, n, series_flags)) {
+    switch (pl.shape) {
         case LdShape::P3L:
-            // covariance wave + mean wave + two producer waves per four evaluations, co-rotating frame
-            // (carma_pipe3l.h); 42 KiB of LDS: up to three workgroups per CU
-            hipLaunchKernelGGL((k_logdens_carma_p3l<P>), dim3((unsigned)rows), dim3(256), Pipe3LGeom<P>::BYTES, st, theta, B, d, q,
-                               series, n + p3l_pad(n), pr, ignore_prior, out, device_cus(), p3l_pad(n));
+            hipLaunchKernelGGL((k_logdens_carma_p3l<P>), grid, block, Pipe3LGeom<P>::BYTES, st, theta, B, d, q, series, n + p3l_pad(n), pr,
+                               ignore_prior, out, f.cus, p3l_pad(n));
             return hipGetLastError();
-        case LdShape::WIN:
-            hipLaunchKernelGGL((k_logdens_carma_w<P>), dim3((unsigned)rows), dim3(256), PipeWGeom<P>::BYTES, st, theta, B, d, q,
-                               series, n, pr, ignore_prior, out, device_cus());
-            return hipGetLastError();
+        case LdShape::WIN: return go(&k_logdens_carma_w<P>, PipeWGeom<P>::BYTES, f.cus);
         case LdShape::WIN2:
-        {
-            const bool sl = n <= W2_MAX_N;                     // (longer: from global memory, the rings alone in LDS)
-            const size_t lds = sl ? PipeWGeom<P>::bytes_with_series(n) : PipeWGeom<P>::BYTES;
-            const long wgs = ((long)B + 1) / 2;
-            auto go = [&](auto kern) -> hipError_t {
-                if (lds > 64 * 1024) {
-                    hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                    if (ea != hipSuccess) return ea;
-                }
-                hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(256), lds, st, theta, B, d, q, series, n, pr, ignore_prior, out, device_cus());
-                return hipGetLastError();
-            };
-            if (!sl) return go(&k_logdens_carma_w2<P, false, false>);
-            if (wgs <= device_cus()) return go(&k_logdens_carma_w2<P, false>);
-            // two workgroups per CU, odd orders: two folded producer passes and a light wave beside the neighbour's recursion wave
+            if (!pl.sl) return go(&k_logdens_carma_w2<P, false, false>, PipeWGeom<P>::BYTES, f.cus);
+            if (!pl.ho) return go(&k_logdens_carma_w2<P, false>, PipeWGeom<P>::bytes_with_series(n), f.cus);
             if constexpr (w2_fold_order(P)) {
-                if (wgs <= 2L * device_cus()) return go(&k_logdens_carma_w2<P, true, true, true>);
+                if (pl.fold) return go(&k_logdens_carma_w2<P, true, true, true>, PipeWGeom<P>::bytes_with_series(n), f.cus);
             }
-            return go(&k_logdens_carma_w2<P, true>);
+            return go(&k_logdens_carma_w2<P, true>, PipeWGeom<P>::bytes_with_series(n), f.cus);
+        case LdShape::PC: {
+            const size_t lds = (size_t)pl.pairs * (128 * sizeof(double4) + RingGeom<P>::BYTES);
+            return pl.pairs == 1 ? go(&k_logdens_carma_pc<P, G, 1>, lds) : go(&k_logdens_carma_pc<P, G, 2>, lds);
         }
-        case LdShape::PC1: return launch_pc(&k_logdens_carma_pc<P, G, 1>, waves, 1);
-        case LdShape::PC2: return launch_pc(&k_logdens_carma_pc<P, G, 2>, waves, 2);
-        case LdShape::PLAIN1:
-            // spread the waves over as many CUs as possible (1 wave per workgroup) until the chip is covered
-            if (repeated_dt)
-                hipLaunchKernelGGL((k_logdens_carma<P, G, 1, true>), dim3((unsigned)waves), dim3(64), 0, st, theta, B, d, q, series,
-                                   n, pr, ignore_prior, out);
-            else
-                hipLaunchKernelGGL((k_logdens_carma<P, G, 1>), dim3((unsigned)waves), dim3(64), 0, st, theta, B, d, q, series, n,
-                                   pr, ignore_prior, out);
-            return hipGetLastError();
-        case LdShape::LANE:
-            // (half-filled waves -- 32 evaluations per wave, twice the waves -- are no faster per wave: an FP64 instruction
-            // takes its four cycles whatever the execution mask; 65 536 evaluations 344 vs 233 us)
-            if (repeated_dt)
-                hipLaunchKernelGGL((k_logdens_carma_lane<P, true>), dim3((unsigned)(((long)B + 63) / 64)), dim3(64), 0, st, theta, B, d, q,
-                                   series, n, pr, ignore_prior, out);
-            else
-                hipLaunchKernelGGL((k_logdens_carma_lane<P>), dim3((unsigned)(((long)B + 63) / 64)), dim3(64), 0, st, theta, B, d, q,
-                                   series, n, pr, ignore_prior, out);
-            return hipGetLastError();
+        case LdShape::PLAIN:
+            if (pl.waves == 1) return pl.repeated_dt ? go(&k_logdens_carma<P, G, 1, true>, 0) : go(&k_logdens_carma<P, G, 1>, 0);
+            return pl.repeated_dt ? go(&k_logdens_carma<P, G, 4, true>, 0) : go(&k_logdens_carma<P, G, 4>, 0);
+        case LdShape::LANE: return pl.repeated_dt ? go(&k_logdens_carma_lane<P, true>, 0) : go(&k_logdens_carma_lane<P>, 0);
         case LdShape::LPC: {
             using Geo = LaneRingGeom<P, 3>;
             static_assert(Geo::BYTES <= 64 * 1024, "within the LDS a launch may ask for without raising the kernel's limit");
-            if (repeated_dt)
-                hipLaunchKernelGGL((k_logdens_carma_lpc<P, 3, true>), dim3((unsigned)(((long)B + 63) / 64)), dim3(256), Geo::BYTES, st, theta,
-                                   B, d, q, series, n, pr, ignore_prior, out, device_cus(), lpc_rot());
-            else if ((long)B <= 64L * device_cus())
-                hipLaunchKernelGGL((k_logdens_carma_lpc<P, 3, false, true>), dim3((unsigned)(((long)B + 63) / 64)), dim3(256), Geo::BYTES,
-                                   st, theta, B, d, q, series, n, pr, ignore_prior, out, device_cus(), lpc_rot());
-            else
-                hipLaunchKernelGGL((k_logdens_carma_lpc<P, 3>), dim3((unsigned)(((long)B + 63) / 64)), dim3(256), Geo::BYTES, st, theta, B, d,
-                                   q, series, n, pr, ignore_prior, out, device_cus(), lpc_rot());
-            return hipGetLastError();
+            if (pl.repeated_dt) return go(&k_logdens_carma_lpc<P, 3, true>, Geo::BYTES, f.cus, pl.rot);
+            if (pl.unrolled) return go(&k_logdens_carma_lpc<P, 3, false, true>, Geo::BYTES, f.cus, pl.rot);
+            return go(&k_logdens_carma_lpc<P, 3>, Geo::BYTES, f.cus, pl.rot);
         }
-        case LdShape::PLAIN4:
-            if (repeated_dt)
-                hipLaunchKernelGGL((k_logdens_carma<P, G, 4, true>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, theta, B,
-                                   d, q, series, n, pr, ignore_prior, out);
-            else
-                hipLaunchKernelGGL((k_logdens_carma<P, G, 4>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, theta, B, d, q,
-                                   series, n, pr, ignore_prior, out);
-            return hipGetLastError();
+        default: break;
     }
     return hipErrorInvalidValue;
 }
 
-template <int P>
-static int logdens_name_p(long B, int n, char* buf, int len, int series_flags)
-{
-    const bool repeated_dt = (series_flags & SERIES_REPEATED_DT) != 0;
-    const char* dtc = repeated_dt ? ",true" : "";
-    constexpr int G = GroupOf<P>::value;
-    switch (logdens_shape<P>(B, n, series_flags)) {
-        case LdShape::WIN: return snprintf(buf, len, "k_logdens_carma_w<%d>", P);
-        case LdShape::WIN2: return snprintf(buf, len, "k_logdens_carma_w2<%d>", P);
-        case LdShape::P3L: return snprintf(buf, len, "k_logdens_carma_p3l<%d>", P);
-        case LdShape::PC1: return snprintf(buf, len, "k_logdens_carma_pc<%d,%d,1>", P, G);
-        case LdShape::PC2: return snprintf(buf, len, "k_logdens_carma_pc<%d,%d,2>", P, G);
-        case LdShape::PLAIN1: return snprintf(buf, len, "k_logdens_carma<%d,%d,1%s>", P, G, dtc);
-        case LdShape::PLAIN4: return snprintf(buf, len, "k_logdens_carma<%d,%d,4%s>", P, G, dtc);
-        case LdShape::LANE: return snprintf(buf, len, "k_logdens_carma_lane<%d%s>", P, dtc);
-        // (up to one workgroup per CU its UNROLLED instantiation, <P,3,false,true>: the same kernel, the same bits)
-        case LdShape::LPC: return snprintf(buf, len, "k_logdens_carma_lpc<%d,3%s>", P, dtc);
-    }
-    return -1;
-}
-
 int logdens_kernel_name(int p, long B, int n, char* buf, int len, int series_flags)
 {
-    if (p == 1) return snprintf(buf, len, "k_logdens_car1");     // (or its parallel-in-time form: launch_logdens_car1)
-    return for_order(p, -1, [&](auto P) { return logdens_name_p<decltype(P)::value>(B, n, buf, len, series_flags); });
+    const ShapeSwitches sw = shape_switches();
+    if (p == 1) return logdens_plan_name(logdens_plan_car1(B, n, device_cus(), sw), buf, len);
+    return for_order(p, -1, [&](auto P) {
+        return logdens_plan_name(logdens_plan(p, B, n, series_flags, logdens_facts<decltype(P)::value>(), sw), buf, len);
+    });
 }
 
 hipError_t launch_logdens_carma(int p, const double* theta, int B, int d, int q, const double4* series, int n,
@@ -1002,20 +861,12 @@ hipError_t launch_logdens_car1(const double* theta, int B, const double4* series
                                hipStream_t st)
 {
     (void)hipGetLastError();   // HIP's last-error is sticky: drop anything left by earlier calls
-    // up to 48 evaluations per CU the series is cut across a wave's lanes (k_logdens_car1_scan); beyond, the lanes are worth more
-    // as evaluations (CARMA_TUNE_CAR1_SCAN_MAX overrides: measured, tools/car1_probe.py)
-    static const long scan_max = [] {
-        const char* e = getenv("CARMA_TUNE_CAR1_SCAN_MAX");
-        return e ? atol(e) : -1L;
-    }();
-    const long smax = scan_max >= 0 ? scan_max : 48L * device_cus();   // (n = 270: 39 against 45 us at 12 288, 52 against 45 at 16 384)
-    // (both forms' times are proportional to the series' length: the break-even does not move with it)
-    if (B <= smax && n >= 64) {
-        hipLaunchKernelGGL(k_logdens_car1_scan, dim3((unsigned)B), dim3(64), 0, st, theta, B, series, n, pr, out);
-        return hipGetLastError();
-    }
-    const unsigned blocks = (unsigned)(((long)B + 63) / 64);
-    hipLaunchKernelGGL(k_logdens_car1, dim3(blocks), dim3(64), 0, st, theta, B, series, n, pr, out);
+    const LdPlan pl = logdens_plan_car1(B, n, device_cus(), shape_switches());
+    const dim3 grid((unsigned)pl.grid), block((unsigned)pl.block);
+    if (pl.shape == LdShape::CAR1_SCAN)
+        hipLaunchKernelGGL(k_logdens_car1_scan, grid, block, 0, st, theta, B, series, n, pr, out);
+    else
+        hipLaunchKernelGGL(k_logdens_car1, grid, block, 0, st, theta, B, series, n, pr, out);
     return hipGetLastError();
 }
 

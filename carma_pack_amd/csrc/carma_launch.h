@@ -5,15 +5,14 @@
 #include <functional>
 #include <type_traits>
 
+#include "carma_shape_plan.h"
 #include "carma_types.h"
 
 namespace carma {
 
-// lanes of the group that holds one evaluation in the lane-group kernels (a row of the state per lane)
-constexpr int group_of(int p) { return p <= 2 ? 2 : (p <= 4 ? 4 : 8); }
 template <int P>
 struct GroupOf {
-    static constexpr int value = group_of(P);
+    static constexpr int value = group_of(P);        // (carma_shape_plan.h)
 };
 
 // run-time order -> template argument: f(std::integral_constant<int, P>{}) for p = P in 2 ... 7 (CARMA_PMAX), `bad` for any other p.
@@ -35,15 +34,20 @@ inline R for_order(int p, R bad, F&& f)
 // compute units of the current device (cached per device)
 int device_cus();
 
-// Launch-shape switches that measurements and the parity tests move: read from the environment ONCE, when the
-// first launch asks (CARMA_TUNE_WIN_ROWS, CARMA_TUNE_WIN2_EVALS, CARMA_TUNE_PT_ROW_WIN), held in atomics, and moved afterwards through
-// carma_tune_set only -- no getenv() in the launch path (it raced with setenv() in multi-threaded callers).  TUNE_UNSET: the default.
+// Launch-shape switches that measurements and the parity tests move: ONE table, read from the environment ONCE,
+// when the first caller asks, held in atomics, and moved afterwards through carma_tune_set only -- no getenv() in the launch path (it
+// raced with setenv() in multi-threaded callers).  TUNE_UNSET (carma_shape_plan.h): the default.  Every entry is CARMA_TUNE_<name>
+// and parsed by atol, but PT_ROW_ROT (hexadecimal) and PT_PLAIN (CARMA_PT_PLAIN: "first character is 1").
 // CARMA_TUNE_CSIM_CHUNK_PATHS: paths per chunk of the conditional simulation (carma_csim.hip; 0 or unset: as many as its scratch cap holds).
 // CARMA_TUNE_SMOOTH_CHUNK_MODELS: models per chunk of the one-pass smoother (carma_smooth.hip; 0 or unset: as many whole waves as its scratch cap holds).
-enum { TUNE_WIN_ROWS = 0, TUNE_WIN2_EVALS = 1, TUNE_PT_ROW_WIN = 2, TUNE_CSIM_CHUNK_PATHS = 3, TUNE_SMOOTH_CHUNK_MODELS = 4, TUNE_COUNT = 5 };
-constexpr long TUNE_UNSET = -0x7fffffffffffffffL - 1;
+enum {
+    TUNE_WIN_ROWS = 0, TUNE_WIN2_EVALS, TUNE_PT_ROW_WIN, TUNE_CSIM_CHUNK_PATHS, TUNE_SMOOTH_CHUNK_MODELS,
+    TUNE_P3L_ROWS, TUNE_LANE_MIN, TUNE_LPC_MIN, TUNE_LPC_MAX, TUNE_LPC_ROT, TUNE_CAR1_SCAN_MAX,
+    TUNE_PT_ROW_WGS_PER_CU, TUNE_PT_ROW_ROT, TUNE_PT_ROW_XCD_MAP, TUNE_PT_PLAIN, TUNE_COUNT
+};
 long tune_get(int which);                    // TUNE_UNSET or the override
 int tune_set(const char* name, long value);  // "WIN_ROWS" / "WIN2_EVALS" / "PT_ROW_WIN" / "CSIM_CHUNK_PATHS" / "SMOOTH_CHUNK_MODELS" (or the full CARMA_TUNE_ name); 0 or -1
+ShapeSwitches shape_switches();              // the planners' switches (carma_shape_plan.h) as the table holds them now
 
 // repeated_dt: a good part of the series' time steps equal their predecessor (regular cadence): the throughput kernels
 // then run the variant that re-uses the transition factors of such steps (carma_core.h, RhoInline DTC)
@@ -80,10 +84,10 @@ hipError_t launch_simulate_car1(double sigsqr, double omega, const double* times
 hipError_t launch_pt(int p, const PtLaunch& L, const double4* series, const Prior& pr, const double* temps,
                      double* theta, double* logpost, double* chol, unsigned* naccept, unsigned* nswap, double* samples,
                      double* sample_lp, hipStream_t st);
-size_t pt_lds_bytes(int P, int d, int T, int* nthreads_out, int* pc_out);
-// row variant (one chain per 16-lane DPP row, ladders spread over several workgroups): number of
-// workgroups that can be resident at once for this (p, d, T), 0 if the variant does not apply
-long pt_row_capacity(int p, int d, int T, int n);
+size_t pt_lds_bytes(int P, int d, int T, int* nthreads_out);
+// row variant (one chain per 16-lane DPP row, ladders spread over several workgroups): workgroups of it a CU holds for this
+// (p, d, T) as the runtime counts them (DeviceFacts::row_per_cu), 0 if the variant does not apply
+int pt_row_per_cu(int p, int d, int T);
 int pt_row_last_pipeline();     // 0 / 1 / 2 as carma_pt_row_pipeline (include/carma_mi355.h); -1 before the first launch
 hipError_t launch_pt_row(int p, const PtLaunch& L, const PtRowSync& S, const double4* series, const Prior& pr,
                          const double* temps, double* theta, double* logpost, double* chol, unsigned* naccept,

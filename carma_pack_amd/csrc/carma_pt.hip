@@ -156,21 +156,12 @@ __global__ __launch_bounds__(MAXT) void k_pt(PtLaunch L, const double4* __restri
     if (active && !producer && g.lane() == 0) naccept[b * T + c] += nacc;
 }
 
-// LDS bytes and threads of one workgroup; *pc_out tells whether the producer/consumer variant fits
-// (and pays: it needs p >= 2 and a series long enough to amortise the chunk barriers).
-size_t pt_lds_bytes(int P, int d, int T, int* nthreads_out, int* pc_out)
+// LDS bytes and threads of the largest workgroup a ladder of T temperatures may ask for (pt_ladder_plan, carma_shape_plan.h)
+size_t pt_lds_bytes(int P, int d, int T, int* nthreads_out)
 {
-    const int G = P <= 1 ? 4 : (P <= 2 ? 2 : (P <= 4 ? 4 : 8));
-    const int nthr_c = ((T * G + 63) / 64) * 64;
-    const size_t per = 4 * (size_t)d + (size_t)d * d;
-    const size_t state = ((size_t)T * per + 4 * (size_t)T + (size_t)T * d) * 8 + (size_t)T * 8 + 16;
-    const size_t plain = (size_t)nthr_c * 48 + state;
-    const size_t ring_bytes = RingGeom<2>::BYTES;            // same for every P
-    const size_t with_ring = plain + (size_t)(nthr_c / 64) * ring_bytes;
-    const bool pc = P >= 2 && 2 * nthr_c <= 1024 && with_ring <= 150 * 1024;
-    if (pc_out) *pc_out = pc ? 1 : 0;
-    if (nthreads_out) *nthreads_out = pc ? 2 * nthr_c : nthr_c;
-    return pc ? with_ring : plain;
+    const PtLadderPlan pl = pt_ladder_plan(P, d, T, 0, 0, 1, RingGeom<2>::BYTES, ShapeSwitches{});
+    if (nthreads_out) *nthreads_out = pl.nthr_fit;
+    return pl.lds_fit;
 }
 
 template <int P, int G, int MAXT, bool PC>
@@ -187,41 +178,19 @@ static hipError_t launch_pt_k(const PtLaunch& L, int nthr, size_t lds, const dou
     return hipGetLastError();
 }
 
+// pt_ladder_plan (carma_shape_plan.h) decides; this names the instantiation
 template <int P>
 static hipError_t launch_pt_p(const PtLaunch& L, const double4* series, const Prior& pr, const double* temps,
                               double* theta, double* logpost, double* chol, unsigned* naccept, unsigned* nswap,
                               double* samples, double* sample_lp, hipStream_t st)
 {
     constexpr int G = PtGroupOf<P>::value;
-    int nthr = 0, pc = 0;
-    const size_t lds = pt_lds_bytes(P, L.d, L.T, &nthr, &pc);
+    const PtLadderPlan pl = pt_ladder_plan(P, L.d, L.T, L.R, L.n, device_cus(), RingGeom<2>::BYTES, shape_switches());
+    auto go = [&](auto kern) { return kern(L, pl.nthr, pl.lds, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st); };
     if constexpr (P >= 2) {
-        // The producer/consumer variant halves the instruction stream of the chain waves but doubles the wave count: it
-        // wins while a CU holds at most one ladder (12.3k vs 8.0k it/s at 16 x 256) and loses once the ladders queue up
-        // for the SIMDs (3.1k vs 4.0k it/s at 16 x 1024, tools/mcmc_bigR_probe.py; the plain chain waves share the
-        // exp/sincos inside root pairs, RhoPair).  CARMA_PT_PLAIN=0/1 overrides.
-        bool plain = L.R > (long)device_cus();
-        static const int force_plain = [] {                 // CARMA_PT_PLAIN=0/1, read once
-            const char* fp = getenv("CARMA_PT_PLAIN");
-            return fp ? (fp[0] == '1' ? 1 : 0) : -1;
-        }();
-        if (force_plain >= 0) plain = force_plain == 1;
-        if (pc && L.n >= 32 && !plain) {
-            if (nthr <= 256)
-                return launch_pt_k<P, G, 256, true>(L, nthr, lds, series, pr, temps, theta, logpost, chol, naccept, nswap,
-                                                    samples, sample_lp, st);
-            return launch_pt_k<P, G, 1024, true>(L, nthr, lds, series, pr, temps, theta, logpost, chol, naccept, nswap,
-                                                 samples, sample_lp, st);
-        }
+        if (pl.pc) return pl.maxt == 256 ? go(&launch_pt_k<P, G, 256, true>) : go(&launch_pt_k<P, G, 1024, true>);
     }
-    // plain variant: every chain wave computes its own rho
-    int nthr_plain = pc ? nthr / 2 : nthr;
-    const size_t lds_plain = pc ? lds - (size_t)(nthr_plain / 64) * RingGeom<2>::BYTES : lds;
-    if (nthr_plain <= 256)
-        return launch_pt_k<P, G, 256, false>(L, nthr_plain, lds_plain, series, pr, temps, theta, logpost, chol, naccept,
-                                             nswap, samples, sample_lp, st);
-    return launch_pt_k<P, G, 1024, false>(L, nthr_plain, lds_plain, series, pr, temps, theta, logpost, chol, naccept,
-                                          nswap, samples, sample_lp, st);
+    return pl.maxt == 256 ? go(&launch_pt_k<P, G, 256, false>) : go(&launch_pt_k<P, G, 1024, false>);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -620,25 +589,23 @@ static size_t pt_row_lds(int d, int T, int n_series = 0)
            (size_t)T * (PT_DMAX + 1) * 8;
 }
 
+// the instantiation of a row-sampler plan (carma_shape_plan.h)
 template <int P>
-static const void* pt_row_fn(int minw, bool win = false, bool two = false, bool ho = false, bool sl = true)
+static const void* pt_row_fn(const PtRowPlan& pl)
 {
-    // (HO: the two-sided form's schedule hand-over, where workgroups share a CU: carma_pipew.h SSCHED; !sl: the series stays in global memory)
-    if (two && minw < 3 && !sl) return reinterpret_cast<const void*>(&k_pt_row<P, 2, true, true, false, false>);
-    if (two && minw < 3) return ho ? reinterpret_cast<const void*>(&k_pt_row<P, 2, true, true, true>) : reinterpret_cast<const void*>(&k_pt_row<P, 2, true, true, false>);
-    if (win && minw < 3) return reinterpret_cast<const void*>(&k_pt_row<P, 2, true>);
-    return minw >= 3 ? reinterpret_cast<const void*>(&k_pt_row<P, 3>) : reinterpret_cast<const void*>(&k_pt_row<P, 2>);
+    // (!sl: the series stays in global memory)
+    if (pl.two && !pl.sl) return reinterpret_cast<const void*>(&k_pt_row<P, 2, true, true, false, false>);
+    if (pl.two) return pl.ho ? reinterpret_cast<const void*>(&k_pt_row<P, 2, true, true, true>) : reinterpret_cast<const void*>(&k_pt_row<P, 2, true, true, false>);
+    if (pl.win) return reinterpret_cast<const void*>(&k_pt_row<P, 2, true>);
+    return pl.minw >= 3 ? reinterpret_cast<const void*>(&k_pt_row<P, 3>) : reinterpret_cast<const void*>(&k_pt_row<P, 2>);
 }
 
-static const void* pt_row_fn_p(int p, int minw)
+int pt_row_per_cu(int p, int d, int T)
 {
-    return for_order(p, (const void*)nullptr, [&](auto P) { return pt_row_fn<decltype(P)::value>(minw); });
-}
-
-long pt_row_capacity(int p, int d, int T, int n)
-{
-    const void* fn = pt_row_fn_p(p, 3);
-    if (!fn || n < 32 || T < 1) return 0;
+    PtRowPlan three;
+    three.minw = 3;
+    const void* fn = for_order(p, (const void*)nullptr, [&](auto P) { return pt_row_fn<decltype(P)::value>(three); });
+    if (!fn || T < 1) return 0;
     const size_t lds = pt_row_lds(d, T);
     if (lds > 160 * 1024) return 0;
     if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return 0;
@@ -646,87 +613,37 @@ long pt_row_capacity(int p, int d, int T, int n)
     if (hipGetDevice(&dev) != hipSuccess) return 0;
     int coop = 0;
     if (hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev) != hipSuccess || !coop) return 0;
-    // Workgroups the device holds at once: what registers (168 -> three waves per SIMD) and LDS allow per CU, as the
-    // runtime counts them -- the cooperative launch (launch_pt_row_p) checks the same thing again.  Beyond that the
-    // ladder kernel (8 chains per wave) takes over.
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds) != hipSuccess || per_cu < 1) return 0;
-    static const long tune = [] {
-        const char* e = getenv("CARMA_TUNE_PT_ROW_WGS_PER_CU");      // measurements only; read once
-        return e ? atol(e) : 0L;
-    }();
-    if (tune > 0 && tune < per_cu) per_cu = (int)tune;
-    if (per_cu > 3) per_cu = 3;
-    return (long)device_cus() * per_cu;
+    return per_cu;
 }
 
 static std::atomic<int> g_row_pipeline{-1};
 int pt_row_last_pipeline() { return g_row_pipeline.load(std::memory_order_relaxed); }
 
+// pt_row_plan (carma_shape_plan.h) decides; this names the instantiation and launches it
 template <int P>
 static hipError_t launch_pt_row_p(const PtLaunch& L, const PtRowSync& S, const double4* series, const Prior& pr,
                                   const double* temps, double* theta, double* logpost, double* chol, unsigned* naccept,
                                   unsigned* nswap, double* samples, double* sample_lp, hipStream_t st)
 {
-    // the TWO-SIDED window pipeline (a chain = two rows, ceil(T / 2) workgroups a ladder) where the WHOLE ladder set's grid in that form
-    // is at most two workgroups per CU, the series suits the window pipeline and fits the LDS beside the rings; from T_global, so
-    // that a sharded ladder's blocks decide as the one-GPU run does.  CARMA_TUNE_PT_ROW_WIN = 0 / 1 (one-datum / one-sided window)
-    // or 2 (two-sided) overrides.
-    const long grid2_global = (long)L.R * (((long)L.T_global + 1) / 2);
-    const bool w2ok = (S.window_ok & SERIES_WINDOW2_OK) || ((S.window_ok & SERIES_WINDOW2_SMALL) && grid2_global <= (long)S.ncu);
-    // the series sits in LDS: up to 1024 data (24 KiB) two workgroups still share a CU; longer ones -- as long as the LDS holds them
-    // (~4800 data) -- where the ladder set leaves a CU to every workgroup, e.g. the single ladder of a run_mcmc call
-    // -- and any longer series from global memory through the rows' register windows (18.5 against 17.7 us per launch of the README
-    // series: the slower way to feed the producers, and the only one there)
-    // (from T_global, like every other choice here: a block of a sharded ladder holds fewer temperatures and would fit more)
-    const bool sl = L.n <= 1024 || (grid2_global <= (long)S.ncu && pt_row_lds(L.d, (int)L.T_global, L.n) <= 160 * 1024);
-    bool two = grid2_global <= 2L * S.ncu && w2ok && L.n >= 32;
-    if (const long ew = tune_get(TUNE_PT_ROW_WIN); ew != TUNE_UNSET) two = ew == 2 && grid2_global <= 2L * S.ncu && L.n >= 32;
-    const int wpl = two ? (L.T + 1) / 2 : S.wpl;
-    const size_t lds = pt_row_lds(L.d, L.T, two && sl ? L.n : 0);
-    const long grid = (long)L.R * wpl;
-    const int minw = grid > 2L * S.ncu ? 3 : 2;             // the 168-register build only where three workgroups share a CU
-    // the windowed pipeline where the WHOLE ladder's grid is at most one workgroup per CU (from T_global: a sharded ladder's blocks
-    // decide as the one-GPU run does, so both stay on one arithmetic); CARMA_TUNE_PT_ROW_WIN=0 / 1 overrides (carma_tune_set)
-    const long grid_global = (long)L.R * (((long)L.T_global + 3) / 4);
-    bool win = grid_global <= (long)S.ncu && (S.window_ok & SERIES_WINDOW_OK);       // (and the series suits it: carma_types.h)
-    if (const long ew = tune_get(TUNE_PT_ROW_WIN); ew != TUNE_UNSET) win = ew != 0 && minw < 3;
-    two = two && minw < 3;
-    const void* fn = pt_row_fn<P>(minw, win, two, grid > (long)S.ncu, sl);
-    g_row_pipeline.store(two ? 2 : (win && minw < 3 ? 1 : 0), std::memory_order_relaxed);
+    const PtRowPlan pl = pt_row_plan(L.R, L.T, (int)L.T_global, L.n, S.window_ok, S.ncu, pt_row_lds(L.d, (int)L.T_global, L.n), shape_switches());
+    const size_t lds = pt_row_lds(L.d, L.T, pl.two && pl.sl ? L.n : 0);
+    const void* fn = pt_row_fn<P>(pl);
+    g_row_pipeline.store(pl.pipeline, std::memory_order_relaxed);
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     PtLaunch La = L;
     PtRowSync Sa = S;
-    // Which wave plays which part in the workgroups that share a CU (i, i + ncu, i + 2 ncu).  An ordinary launch places
-    // them as k_logdens_carma_p3l's are placed (same tables); the workgroups of a COOPERATIVE launch all land with the
-    // same wave -> SIMD pattern (tools/ubench/wave_placement.hip with a second argument 1,
-    // profiles/r03/wave_placement_coop.txt), so the parts simply trade places: (cov, mean, P0, P1), (P0, P1, cov, mean),
-    // (mean, cov, P1, P0) -- every SIMD gets one covariance or mean wave of each kind at most.
-    static const long tune_rot = [] {
-        const char* e = getenv("CARMA_TUNE_PT_ROW_ROT");                        // measurements only; read once
-        return e ? strtol(e, nullptr, 16) : -1L;
-    }();
-    Sa.wpl = wpl;
-    Sa.rot = wpl == 1 ? 0x36D2 : 0xB14E;
-    if (tune_rot >= 0) Sa.rot = (int)tune_rot;
-    static const long tune_xcd = [] {
-        const char* e = getenv("CARMA_TUNE_PT_ROW_XCD_MAP");                    // measurements only; read once
-        return e ? atol(e) : -1L;
-    }();
-    Sa.xcd_map = (wpl > 1 && L.R % 8 == 0) ? 8 : 1;
-    if (tune_xcd >= 0) Sa.xcd_map = (tune_xcd > 1 && L.R % tune_xcd == 0) ? (int)tune_xcd : 1;
+    Sa.wpl = pl.wpl;
+    Sa.rot = pl.rot;
+    Sa.xcd_map = pl.xcd_map;
     Prior pra = pr;
     void* args[] = {&La, &Sa, (void*)&series, &pra, (void*)&temps, &theta, &logpost, &chol, &naccept, &nswap, &samples, &sample_lp};
-    if (wpl == 1)
-        // the whole ladder (block) in one workgroup: the rendezvous has a single participant, no co-residency needed --
-        // an ordinary launch (a cooperative one costs ~2 ms on this stack, which matters when the ladder is sharded
-        // across GPUs and every iteration is a launch of its own)
-        return hipLaunchKernel(fn, dim3((unsigned)grid), dim3(256), args, lds, st);
-    // COOPERATIVE launch: the swap step is a rendezvous of the ladder's workgroups through global memory, so the whole
-    // grid has to be resident at once.  The runtime checks that (hipErrorCooperativeLaunchTooLarge otherwise, and the
+    if (!pl.cooperative) return hipLaunchKernel(fn, dim3((unsigned)pl.grid), dim3(256), args, lds, st);
+    // The runtime checks that the whole grid is resident at once (hipErrorCooperativeLaunchTooLarge otherwise, and the
     // host falls back to the ladder kernel) and schedules the grid as a gang, instead of this code assuming it.
-    return hipLaunchCooperativeKernel(fn, dim3((unsigned)grid), dim3(256), args, (unsigned)lds, st);
+    return hipLaunchCooperativeKernel(fn, dim3((unsigned)pl.grid), dim3(256), args, (unsigned)lds, st);
 }
 
 hipError_t launch_pt_row(int p, const PtLaunch& L, const PtRowSync& S, const double4* series, const Prior& pr,

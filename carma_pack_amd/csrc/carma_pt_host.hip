@@ -337,7 +337,7 @@ int carma_pt_create(carma_ctx* h, int ntemps, int nreplicas, const double* tempe
     }
     Ctx* c = reinterpret_cast<Ctx*>(h);
     int nthr = 0;
-    const size_t lds = pt_lds_bytes(c->p, c->d, ntemps, &nthr, nullptr);
+    const size_t lds = pt_lds_bytes(c->p, c->d, ntemps, &nthr);
     if (nthr > 1024 || lds > 160 * 1024) {
         set_error("carma_pt_create: %d temperatures do not fit one workgroup (threads %d, LDS %zu B)", ntemps, nthr, lds);
         return CARMA_EINVAL;
@@ -359,57 +359,22 @@ int carma_pt_create(carma_ctx* h, int ntemps, int nreplicas, const double* tempe
     std::vector<double> chol(nchain * d * d);
     for (size_t k = 0; k < nchain; k++) std::memcpy(&chol[k * d * d], R0.data(), sizeof(double) * d * d);
     e = pt_ens_create(s, ntemps, nreplicas, d, temps, chol.data());
-    // Kernel choice.  The row variant needs every workgroup of the grid resident at the same time
-    // (its swap step is a cross-workgroup rendezvous); otherwise one workgroup per ladder (k_pt).
-    // CARMA_PT_KERNEL=ladder|row overrides (row only where it is safe).
-    // Large ensembles: ONE CHAIN PER LANE, an iteration as the batched log-density launch + a bookkeeping kernel
-    // (carma_pt_lane.hip).  Which path pays is measured, per order (tools/mcmc_lane_probe.py, profiles/r04/
-    // mcmc_lane_threshold_v*.txt; 16 temperatures, n = 270):
-    //   * the ladder kernel k_pt gives a ladder ceil(T G / 64) waves (G = 2 / 4 / 8 lanes per chain for p = 2 / 3-4 / 5-7); its
-    //     iteration takes twice as long once those are more than the chip has SIMDs -- p = 5: 8193 chains 245 us against 127,
-    //     p = 3: 32 768 chains 207 against 98 -- so from there on: one chain per lane, whatever the order;
-    //   * p <= 4, whose batched launch is the producer-wave kernel right above the wave pipeline's range (carma_kernels.hip,
-    //     lpc_min_evals): from 16 x #CUs chains (p = 3: 78 us flat up to 16 384 chains against 103-105, p = 4: 88-107 against
-    //     116; at 3200 ... 4096 chains the ladder kernel's 74 / 79 us are still ahead of 78 / 83), p = 2 from 12 x #CUs (64 us
-    //     flat against 73-96); p = 5 from 16 x #CUs as well since round 5 (below).
-    // CARMA_PT_KERNEL=lane forces it (T <= 64), CARMA_TUNE_PT_LANE_MIN = N replaces the table by "from N chains".
-    const char* force = getenv("CARMA_PT_KERNEL");
-    if (e == hipSuccess && ntemps <= 64) {
+    // Kernel choice: pt_family (carma_shape_plan.h).  CARMA_PT_KERNEL=ladder|row|lane and CARMA_TUNE_PT_LANE_MIN are read HERE, at
+    // every creation (callers set them between creations), and nowhere else.
+    if (e == hipSuccess) {
+        const char* force = getenv("CARMA_PT_KERNEL");
         const char* tv = getenv("CARMA_TUNE_PT_LANE_MIN");
-        const long cus = device_cus();
-        const int G = c->p == 2 ? 2 : (c->p <= 4 ? 4 : 8);
-        const long ladder_waves = (long)nreplicas * ((ntemps * G + 63) / 64);
-        bool pays = ladder_waves > 4 * cus;
-        // CAR(1): k_pt gives a chain ONE lane for the whole series (44 us per iteration at n = 270 whatever the ensemble), the batched
-        // launch cuts the series across a wave (k_logdens_car1_scan: 8 us for 1024 chains) -- 18.6 against 43.8 us per iteration
-        // at 16 x 64, 24.8 against 44.1 at 16 x 256, 59.7 against 73.9 at 16 x 2048; only where the parallel-in-time launch has
-        // just run out of waves (48 ... 64 x #CUs chains) the ladder kernel is ahead, 46.9 against 51.4 (car1_sampler_v1.txt)
-        // (evidence: n = 270, ensembles from 16 x 64.  Below 64 data the batched launch has no parallel-in-time scan -- one
-        // evaluation per lane, launch_logdens_car1 -- and a small ladder such as run_mcmc_car1's default ~10 chains would pay 2-3
-        // launches per iteration with nothing parallel to hide them: those keep the persistent k_pt.)
-        if (c->p == 1) pays = c->n >= 64 && (long)nchain >= 64 && !((long)nchain > 48 * cus && (long)nchain <= 64 * cus);
-        // (p = 3 from 12 x #CUs as well since round 5: 70 us against the ladder kernel's 72.6 at 3200 / 4096 chains; p = 4: 83 against 75,
-        // p = 6, 7 at 4608 ... 8192 chains: 150 / 172 against 130 / 138 -- mcmc_lane_threshold_v3.txt)
-        if (c->p == 2 || c->p == 3) pays = pays || (long)nchain > 12 * cus;
-        if (c->p == 4) pays = pays || (long)nchain > 16 * cus;
-        // p = 5 (round 5): its batched launch is the producer-wave kernel from 4 097 evaluations since the consumer takes a ring buffer
-        // at a time (89 us) -- 111-112 us per iteration flat for 4 352 ... 8 192 chains against the ladder kernel's 122-125 (which does
-        // 80 us up to 4 096 chains, against 91: profiles/r05/mcmc_lane_threshold_v1.txt, _v2.txt)
-        if (c->p == 5) pays = pays || (long)nchain > 16 * cus;
-        if (tv) pays = (long)nchain >= atol(tv);
-        const bool forced = force && std::strcmp(force, "lane") == 0;
-        if (forced || (!force && pays)) {
+        const PtForce forced = !force ? PtForce::NONE : !std::strcmp(force, "lane") ? PtForce::LANE : !std::strcmp(force, "ladder") ? PtForce::LADDER : PtForce::ROW;
+        DeviceFacts f;
+        f.cus = device_cus();
+        f.row_per_cu = pt_row_per_cu(c->p, d, ntemps);
+        const PtFamily fam = pt_family(c->p, ntemps, nreplicas, c->n, f, shape_switches(), forced, tv ? atol(tv) : TUNE_UNSET);
+        if (fam == PtFamily::LANE) {
             s->use_lane = true;
             e = dev_malloc(&s->d_scratch, sizeof(double) * pt_lane_scratch_doubles(d, (long)nchain));
-        }
-    }
-    if (e == hipSuccess && c->p >= 2 && !s->use_lane) {
-        const int wpl = (ntemps + 3) / 4;
-        const long cap = pt_row_capacity(c->p, d, ntemps, c->n);
-        const bool want = !(force && std::strcmp(force, "ladder") == 0);
-        if (want && cap >= (long)nreplicas * wpl) {
+        } else if (fam == PtFamily::ROW) {
             s->use_row = true;
-            s->wpl = wpl;
+            s->wpl = (ntemps + 3) / 4;
             // tagged staging: two buffers x two copies of (theta[d], log-posterior) per chain; zeroed once (an all-zero
             // pair of words never validates)
             e = dev_malloc(&s->d_stage, sizeof(unsigned long long) * 4 * nchain * (d + 1));

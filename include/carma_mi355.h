@@ -523,8 +523,8 @@ long carma_pt_iterations_done(const carma_ctx* h);
  * states): after a fall-back the chains are STATISTICALLY equivalent to, not bit-identical with, an uninterrupted run. */
 int carma_pt_kernel_in_use(const carma_ctx* h);
 /* which recursion the LAST k_pt_row launch of this process ran on: 0 = one-datum wave pipeline, 1 = windowed pipeline (one-sided),
- * 2 = two-sided windowed pipeline; -1 before the first such launch.  For tests and measurements: the choice (launch_pt_row_p in
- * carma_pt.hip) depends on the whole ladder set's grid, the series (SERIES_WINDOW2_OK) and its length. */
+ * 2 = two-sided windowed pipeline; -1 before the first such launch.  For tests and measurements: the choice (pt_row_plan in
+ * carma_shape_plan.h) depends on the whole ladder set's grid, the series (SERIES_WINDOW2_OK) and its length. */
 int carma_pt_row_pipeline(void);
 
 /*
