@@ -74,6 +74,8 @@ hipError_t carma_dev_malloc(void** p, size_t n)
     g_guard[*p] = a;
     return hipSuccess;
 }
+hipError_t carma_pinned_malloc(void** p, size_t n) { return hipHostMalloc(p, n, hipHostMallocDefault); }
+hipError_t carma_pinned_free(void* p) { return hipHostFree(p); }
 hipError_t carma_dev_free(void* p)
 {
     if (!p) return hipSuccess;
@@ -217,20 +219,19 @@ int select_device(int device)
 int Ctx::ensure_staging(int B)
 {
     if (B <= cap) return CARMA_OK;
-    if (d_theta) (void)dev_free(d_theta);
-    if (d_out) (void)dev_free(d_out);
-    if (h_stage) (void)hipHostFree(h_stage);
-    d_theta = d_out = h_stage = nullptr;
+    d_theta.release();
+    d_out.release();
+    h_stage.release();
     cap = 0;
     int newcap = std::max(B, 1024);
-    hipError_t e = dev_malloc(&d_theta, sizeof(double) * (size_t)newcap * d);
-    if (e != hipSuccess) return hip_fail(e, "dev_malloc(theta)");
-    e = dev_malloc(&d_out, sizeof(double) * (size_t)newcap);
-    if (e != hipSuccess) return hip_fail(e, "dev_malloc(out)");
+    hipError_t e = d_theta.alloc((size_t)newcap * d);
+    if (e != hipSuccess) return hip_fail(e, "device staging (theta)");
+    e = d_out.alloc((size_t)newcap);
+    if (e != hipSuccess) return hip_fail(e, "device staging (out)");
     // pinned, so that both copies are real asynchronous DMA transfers ordered on the stream (a copy from pageable memory
     // is staged by the runtime and synchronises)
-    e = hipHostMalloc(reinterpret_cast<void**>(&h_stage), sizeof(double) * (size_t)newcap * (d + 1), hipHostMallocDefault);
-    if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(staging)");
+    e = h_stage.alloc((size_t)newcap * (d + 1));
+    if (e != hipSuccess) return hip_fail(e, "pinned staging");
     cap = newcap;
     return CARMA_OK;
 }
@@ -286,7 +287,7 @@ carma_ctx* carma_ctx_create(const double* time, const double* y, const double* y
     carma_ctx_set_prior(reinterpret_cast<carma_ctx*>(c), max_stdev);
     std::vector<double> s = pack_series(c->t, c->y, c->yerr);
     c->sflags = series_flags(c->t.data(), c->n, p, c->pr.max_freq);
-    hipError_t e = dev_malloc(&c->d_series, sizeof(double) * s.size());
+    hipError_t e = c->d_series.alloc(s.size());
     if (e == hipSuccess) e = hipMemcpy(c->d_series, s.data(), sizeof(double) * s.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
@@ -302,13 +303,8 @@ void carma_ctx_destroy(carma_ctx* h)
     if (!h) return;
     Ctx* c = reinterpret_cast<Ctx*>(h);
     (void)hipSetDevice(c->device);
-    if (c->pt) pt_state_free(c);
-    if (c->d_series) (void)dev_free(c->d_series);
-    if (c->d_theta) (void)dev_free(c->d_theta);
-    if (c->d_out) (void)dev_free(c->d_out);
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                                 // (its members release their buffers, the sampler state among them)
 }
 
 int carma_ctx_n(const carma_ctx* h) { return h ? reinterpret_cast<const Ctx*>(h)->n : CARMA_EINVAL; }
@@ -353,10 +349,9 @@ int carma_logdensity_batch_dev(carma_ctx* h, const double* d_theta, int B, int i
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     hipError_t e;
     if (c->p == 1)
-        e = launch_logdens_car1(d_theta, B, reinterpret_cast<const double4*>(c->d_series), c->n, c->pr, d_out, st);
+        e = launch_logdens_car1(d_theta, B, c->rec(), c->n, c->pr, d_out, st);
     else
-        e = launch_logdens_carma(c->p, d_theta, B, c->d, c->q, reinterpret_cast<const double4*>(c->d_series), c->n, c->pr,
-                                 ignore_prior, d_out, st, c->series_flags());
+        e = launch_logdens_carma(c->p, d_theta, B, c->d, c->q, c->rec(), c->n, c->pr, ignore_prior, d_out, st, c->series_flags());
     if (e != hipSuccess) return hip_fail(e, "launch logdensity");
     return CARMA_OK;
 }

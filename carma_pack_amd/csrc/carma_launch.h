@@ -80,32 +80,36 @@ hipError_t launch_simulate_carma(int p, const double* om_re_im, const double* ma
 hipError_t launch_simulate_car1(double sigsqr, double omega, const double* times, int n, int npaths, unsigned seed0,
                                 unsigned seed1, unsigned path0, double* out, hipStream_t st);
 
+// The buffers of an ensemble every sampler kernel takes, in the order of the kernels' parameter lists (pt_ens_buffers, carma_host.h,
+// fills it): temps [T]; theta [R T][d], logpost [R T], chol [R T][d d]; naccept, nswap [R T]; samples [R][cap][d], sample_lp [R][cap]
+struct PtBuffers {
+    const double* temps;
+    double *theta, *logpost, *chol;
+    unsigned *naccept, *nswap;
+    double *samples, *sample_lp;
+};
+
 // one chunk of the persistent PT sampler kernel (carma_pt.hip)
-hipError_t launch_pt(int p, const PtLaunch& L, const double4* series, const Prior& pr, const double* temps,
-                     double* theta, double* logpost, double* chol, unsigned* naccept, unsigned* nswap, double* samples,
-                     double* sample_lp, hipStream_t st);
+hipError_t launch_pt(int p, const PtLaunch& L, const double4* series, const Prior& pr, const PtBuffers& b, hipStream_t st);
 size_t pt_lds_bytes(int P, int d, int T, int* nthreads_out);
 // row variant (one chain per 16-lane DPP row, ladders spread over several workgroups): workgroups of it a CU holds for this
 // (p, d, T) as the runtime counts them (DeviceFacts::row_per_cu), 0 if the variant does not apply
 int pt_row_per_cu(int p, int d, int T);
 int pt_row_last_pipeline();     // 0 / 1 / 2 as carma_pt_row_pipeline (include/carma_mi355.h); -1 before the first launch
-hipError_t launch_pt_row(int p, const PtLaunch& L, const PtRowSync& S, const double4* series, const Prior& pr,
-                         const double* temps, double* theta, double* logpost, double* chol, unsigned* naccept,
-                         unsigned* nswap, double* samples, double* sample_lp, hipStream_t st);
+hipError_t launch_pt_row(int p, const PtLaunch& L, const PtRowSync& S, const double4* series, const Prior& pr, const PtBuffers& b,
+                         hipStream_t st);
 
 // sampler for large ensembles (carma_pt_lane.hip): one chain per lane, an iteration = propose kernel + the batched
 // log-density launch above + finish kernel; a ladder's T <= 64 chains are T consecutive lanes.  Enqueues L.niter
 // iterations on st.  scratch: pt_lane_scratch_doubles(d, T * R) doubles of device memory (chain-minor working state).
 size_t pt_lane_scratch_doubles(int d, long nchain);
-hipError_t launch_pt_lane(int p, const PtLaunch& L, double* scratch, const double4* series, const Prior& pr,
-                          const double* temps, double* theta, double* logpost, double* chol, unsigned* naccept,
-                          unsigned* nswap, double* samples, double* sample_lp, int series_flags, bool load_factor, hipStream_t st);
+hipError_t launch_pt_lane(int p, const PtLaunch& L, double* scratch, const double4* series, const Prior& pr, const PtBuffers& b,
+                          int series_flags, bool load_factor, hipStream_t st);
 // the same loop with the log-density step ("K1") supplied by the caller: k1(thn [nc][d], nc, ll [nc], st) enqueues the
 // log-densities of the nc = R * T proposals (chain-major, chain = ladder * T + temperature) on st
 using PtLaneK1 = std::function<hipError_t(const double* thn, long nc, double* ll, hipStream_t st)>;
-hipError_t launch_pt_lane_k1(int p, const PtLaunch& L, double* scratch, const PtLaneK1& k1, const double* temps, double* theta,
-                             double* logpost, double* chol, unsigned* naccept, unsigned* nswap, double* samples, double* sample_lp,
-                             bool load_factor, hipStream_t st);
+hipError_t launch_pt_lane_k1(int p, const PtLaunch& L, double* scratch, const PtLaneK1& k1, const PtBuffers& b, bool load_factor,
+                             hipStream_t st);
 // the lane sampler keeps the proposal factors in its chain-minor working state between calls; this writes them to the chain-major
 // array the other entry points read (carma_pt_get_factor, the shard packers): enqueued on st
 hipError_t pt_lane_store_factor(int d, int T, int R, double* scratch, double* chol, hipStream_t st);

@@ -71,7 +71,7 @@ static hipError_t launch_logdens_chains_ms(const Mctx* c, const MptState* s, con
     const dim3 grid((unsigned)((nc + 63) / 64)), block(64);
     if (c->p == 1) {
         hipLaunchKernelGGL(k_logdens_car1_chains_ms, grid, block, 0, st, thn, nc, s->T, c->rec(), c->offs(), c->ns(), c->prs(),
-                           s->d_lser, ll);
+                           s->d_lser.get(), ll);
         return hipGetLastError();
     }
     for (int rep = 0; rep < 2; rep++) {
@@ -79,25 +79,15 @@ static hipError_t launch_logdens_chains_ms(const Mctx* c, const MptState* s, con
         const hipError_t e = for_order(c->p, hipErrorInvalidValue, [&](auto P) {
             if (rep)
                 hipLaunchKernelGGL((k_logdens_carma_chains_ms<decltype(P)::value, true>), grid, block, 0, st, thn, c->d, c->q, nc, s->T,
-                                   c->rec(), c->offs(), c->ns(), c->prs(), s->d_rep, s->d_lser, ll);
+                                   c->rec(), c->offs(), c->ns(), c->prs(), s->d_rep.get(), s->d_lser.get(), ll);
             else
                 hipLaunchKernelGGL((k_logdens_carma_chains_ms<decltype(P)::value, false>), grid, block, 0, st, thn, c->d, c->q, nc, s->T,
-                                   c->rec(), c->offs(), c->ns(), c->prs(), s->d_rep, s->d_lser, ll);
+                                   c->rec(), c->offs(), c->ns(), c->prs(), s->d_rep.get(), s->d_lser.get(), ll);
             return hipGetLastError();
         });
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
-}
-
-void mpt_free(Mctx* c)
-{
-    if (!c->mpt) return;
-    pt_ens_release(c->mpt);
-    if (c->mpt->d_lser) (void)dev_free(c->mpt->d_lser);
-    if (c->mpt->d_rep) (void)dev_free(c->mpt->d_rep);
-    delete c->mpt;
-    c->mpt = nullptr;
 }
 
 // the sampler state of h, or null with the error set: `who` was called before carma_mpt_create (need_start: or before the
@@ -108,7 +98,7 @@ static MptState* mpt_state(carma_mctx* h, const char* who, bool need_start)
         set_error("%s: null context", who);
         return nullptr;
     }
-    MptState* s = reinterpret_cast<Mctx*>(h)->mpt;
+    MptState* s = reinterpret_cast<Mctx*>(h)->mpt.get();
     if (!s) {
         set_error("%s: call carma_mpt_create first", who);
         return nullptr;
@@ -131,7 +121,7 @@ static long mpt_chunk_iters(const MptState* s)
 // niter iterations, a chunk in flight at a time.  thin > 0: save the coldest chains every thin iterations from sample *save_offset on
 static int mpt_iterate(Mctx* c, long niter, int do_exchange, int thin, long* save_offset)
 {
-    MptState* s = c->mpt;
+    MptState* s = c->mpt.get();
     const long chunk0 = mpt_chunk_iters(s);
     const PtLaneK1 k1 = [c, s](const double* thn, long nc, double* ll, hipStream_t st) {
         return launch_logdens_chains_ms(c, s, thn, nc, ll, st);
@@ -140,8 +130,7 @@ static int mpt_iterate(Mctx* c, long niter, int do_exchange, int thin, long* sav
     while (left > 0) {
         const long ch = pt_next_chunk(left, chunk0, thin);
         const PtLaunch L = pt_ens_launch(s, c->d, c->q, s->nmax, ch, do_exchange, thin, save_offset ? *save_offset : 0);
-        hipError_t e = launch_pt_lane_k1(c->p, L, s->d_scratch, k1, s->d_temps, s->d_theta, s->d_lp, s->d_chol, s->d_nacc, s->d_nswap,
-                                         s->d_samples, s->d_slp, !s->factor_loaded, c->stream);
+        hipError_t e = launch_pt_lane_k1(c->p, L, s->d_scratch, k1, pt_ens_buffers(s), !s->factor_loaded, c->stream);
         if (e == hipSuccess) {
             s->factor_loaded = true;
             s->chol_stale = true;
@@ -190,9 +179,8 @@ int carma_mpt_create(carma_mctx* h, const int* series, int M, int ntemps, int nr
     }
     hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    mpt_free(c);
-    MptState* s = new MptState();
-    c->mpt = s;
+    c->mpt.reset(new MptState());         // (the state of an earlier call goes, with every buffer it holds)
+    MptState* s = c->mpt.get();
     s->M = M;
     s->reps = nreplicas;
     s->maxiter = adapt_iters;
@@ -216,15 +204,14 @@ int carma_mpt_create(carma_mctx* h, const int* series, int M, int ntemps, int nr
         for (int r = 0; r < nreplicas; r++) lser[(size_t)j * nreplicas + r] = sj;
     }
     e = pt_ens_create(s, ntemps, nlad, d, temps, chol.data());
-    if (e == hipSuccess) e = dev_malloc(&s->d_lser, sizeof(int) * lser.size());
-    if (e == hipSuccess) e = dev_malloc(&s->d_rep, sizeof(char) * (size_t)c->S);
-    if (e == hipSuccess) e = dev_malloc(&s->d_scratch, sizeof(double) * pt_lane_scratch_doubles(d, (long)nchain));
+    if (e == hipSuccess) e = s->d_lser.alloc(lser.size());
+    if (e == hipSuccess) e = s->d_rep.alloc((size_t)c->S);
+    if (e == hipSuccess) e = s->d_scratch.alloc(pt_lane_scratch_doubles(d, (long)nchain));
     if (e == hipSuccess) e = hipMemcpy(s->d_lser, lser.data(), sizeof(int) * lser.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(s->d_rep, c->repdt.data(), sizeof(char) * (size_t)c->S, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
-        const int rc = hip_fail(e, "carma_mpt_create");
-        mpt_free(c);
-        return rc;
+        c->mpt.reset();
+        return hip_fail(e, "carma_mpt_create");
     }
     return CARMA_OK;
 }
@@ -363,7 +350,7 @@ int carma_mpt_sample(carma_mctx* h, int nsamples, int thin, double* samples, dou
     hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     long capacity = 0;
-    e = pt_ens_reserve_samples(s, c->d, nsamples, &capacity);
+    e = s->reserve_samples(c->d, nsamples, &capacity);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         set_error("carma_mpt_sample: no device memory for the sample buffer: %zu bytes asked for (%ld ladders x %d samples x %d)",

@@ -1,6 +1,6 @@
 // carma_mseries.h -- what the multi-series translation units share (carma_mseries.hip: context and log-density;
 // carma_mitems.hip: Filter(), Predict and the smoother of (series, model) items; carma_mpt.hip: the sampler): the context, the
-// sampler state, the item packer and the small host helpers of the item calls.  Host code only.
+// sampler state (MptState, carma_pt_state.h), the item packer and the small host helpers of the item calls.  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,19 +14,9 @@
 
 namespace carma {
 
-// Sampler state of a multi-series context (carma_mpt_*): M runs of `reps` ladders of T chains = one ensemble of R = M reps ladders
-struct MptState : PtEnsemble {
-    int M = 0, reps = 0;              // runs, replicas per run
-    std::vector<int> series;          // [M] series of run j
-    int nmax = 0;                     // the longest series of the call
-    bool any_plain = false, any_rep = false;   // the call holds irregular / regular-cadence series
-    int* d_lser = nullptr;            // [R] series of every ladder, uploaded once
-    char* d_rep = nullptr;            // [S] SERIES_REPEATED_DT of every series
-};
-
 // Multi-series context: the series of a set packed one after another in HBM, each as carma_ctx_create packs one
 struct Mctx {
-    MptState* mpt = nullptr;
+    std::unique_ptr<MptState> mpt;    // sampler state of carma_mpt_create, if any
     int device = 0;
     int p = 0, q = 0, d = 0, S = 0;
     std::vector<long> hoff;           // [S + 1] start of series s in t / y / yerr (after sort/dedup)
@@ -42,7 +32,7 @@ struct Mctx {
     const Prior* prs() const { return d_pr.as<const Prior>(); }
     // per-call buffers, grown on demand: parameter vectors [cap_B][d], results [cap_B], plan [cap_W] + [cap_W][64]
     DevMem d_theta, d_out, d_wser, d_eidx;
-    char* h_stage = nullptr;          // pinned: the same four, in this order
+    PinnedBuf<char> h_stage;          // pinned: the same four, in this order
     long cap_B = 0, cap_W = 0;
     hipStream_t stream = nullptr;
     MlogdensPlan plan;                // workspace of the launch plans (carma_mseries_plan.h), kept between calls
@@ -56,23 +46,19 @@ struct Mctx {
         if (B <= cap_B && W <= cap_W) return CARMA_OK;
         const long nB = std::max(std::max(B, cap_B), 1024L), nW = std::max(std::max(W, cap_W), 64L);
         for (DevMem* b : {&d_theta, &d_out, &d_wser, &d_eidx}) b->release();
-        if (h_stage) (void)hipHostFree(h_stage);
-        h_stage = nullptr;
+        h_stage.release();
         cap_B = cap_W = 0;
         hipError_t e = d_theta.alloc(sizeof(double) * (size_t)nB * d);
         if (e == hipSuccess) e = d_out.alloc(sizeof(double) * (size_t)nB);
         if (e == hipSuccess) e = d_wser.alloc(sizeof(int) * (size_t)nW);
         if (e == hipSuccess) e = d_eidx.alloc(sizeof(int) * (size_t)nW * 64);
-        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h_stage), stage_bytes(nB, nW), hipHostMallocDefault);
+        if (e == hipSuccess) e = h_stage.alloc(stage_bytes(nB, nW));
         if (e != hipSuccess) return hip_fail(e, "carma_mlogdensity_batch: buffers");
         cap_B = nB;
         cap_W = nW;
         return CARMA_OK;
     }
 };
-
-// releases the sampler state of c, if any (carma_mpt.hip)
-void mpt_free(Mctx* c);
 
 // The items of carma_mkfilter / carma_mpredict / carma_msmooth -> par [M][3 p + 2] (p = 1: [M][3]: sigsqr, omega, mu) in the
 // caller's order, as the kernels read them.  Host only; an argument error names its item.

@@ -197,10 +197,8 @@ void carma_mctx_destroy(carma_mctx* h)
     if (!h) return;
     Mctx* c = reinterpret_cast<Mctx*>(h);
     (void)hipSetDevice(c->device);
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    mpt_free(c);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;                                                 // (the DevMem members release their buffers)
+    delete c;                                                 // (its members release their buffers, the sampler state among them)
 }
 
 int carma_mctx_nseries(const carma_mctx* h) { return h ? reinterpret_cast<const Mctx*>(h)->S : CARMA_EINVAL; }
@@ -254,7 +252,7 @@ int carma_mlogdensity_batch(carma_mctx* h, const double* theta, const int* serie
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     int rc = c->ensure(B, W);
     if (rc != CARMA_OK) return rc;
-    double* h_th = reinterpret_cast<double*>(c->h_stage);
+    double* h_th = reinterpret_cast<double*>(c->h_stage.get());
     double* h_out = h_th + (size_t)c->cap_B * d;
     int* h_wser = reinterpret_cast<int*>(h_out + c->cap_B);
     int* h_eidx = h_wser + c->cap_W;

@@ -165,28 +165,25 @@ size_t pt_lds_bytes(int P, int d, int T, int* nthreads_out)
 }
 
 template <int P, int G, int MAXT, bool PC>
-static hipError_t launch_pt_k(const PtLaunch& L, int nthr, size_t lds, const double4* series, const Prior& pr,
-                              const double* temps, double* theta, double* logpost, double* chol, unsigned* naccept,
-                              unsigned* nswap, double* samples, double* sample_lp, hipStream_t st)
+static hipError_t launch_pt_k(const PtLaunch& L, int nthr, size_t lds, const double4* series, const Prior& pr, const PtBuffers& b,
+                              hipStream_t st)
 {
     // before every launch (see launch_logdens_p: once per process is not enough)
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pt<P, G, MAXT, PC>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_pt<P, G, MAXT, PC>), dim3((unsigned)L.R), dim3((unsigned)nthr), lds, st, L, series, pr, temps,
-                       theta, logpost, chol, naccept, nswap, samples, sample_lp);
+    hipLaunchKernelGGL((k_pt<P, G, MAXT, PC>), dim3((unsigned)L.R), dim3((unsigned)nthr), lds, st, L, series, pr, b.temps,
+                       b.theta, b.logpost, b.chol, b.naccept, b.nswap, b.samples, b.sample_lp);
     return hipGetLastError();
 }
 
 // pt_ladder_plan (carma_shape_plan.h) decides; this names the instantiation
 template <int P>
-static hipError_t launch_pt_p(const PtLaunch& L, const double4* series, const Prior& pr, const double* temps,
-                              double* theta, double* logpost, double* chol, unsigned* naccept, unsigned* nswap,
-                              double* samples, double* sample_lp, hipStream_t st)
+static hipError_t launch_pt_p(const PtLaunch& L, const double4* series, const Prior& pr, const PtBuffers& b, hipStream_t st)
 {
     constexpr int G = PtGroupOf<P>::value;
     const PtLadderPlan pl = pt_ladder_plan(P, L.d, L.T, L.R, L.n, device_cus(), RingGeom<2>::BYTES, shape_switches());
-    auto go = [&](auto kern) { return kern(L, pl.nthr, pl.lds, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st); };
+    auto go = [&](auto kern) { return kern(L, pl.nthr, pl.lds, series, pr, b, st); };
     if constexpr (P >= 2) {
         if (pl.pc) return pl.maxt == 256 ? go(&launch_pt_k<P, G, 256, true>) : go(&launch_pt_k<P, G, 1024, true>);
     }
@@ -623,9 +620,8 @@ int pt_row_last_pipeline() { return g_row_pipeline.load(std::memory_order_relaxe
 
 // pt_row_plan (carma_shape_plan.h) decides; this names the instantiation and launches it
 template <int P>
-static hipError_t launch_pt_row_p(const PtLaunch& L, const PtRowSync& S, const double4* series, const Prior& pr,
-                                  const double* temps, double* theta, double* logpost, double* chol, unsigned* naccept,
-                                  unsigned* nswap, double* samples, double* sample_lp, hipStream_t st)
+static hipError_t launch_pt_row_p(const PtLaunch& L, const PtRowSync& S, const double4* series, const Prior& pr, PtBuffers b,
+                                  hipStream_t st)
 {
     const PtRowPlan pl = pt_row_plan(L.R, L.T, (int)L.T_global, L.n, S.window_ok, S.ncu, pt_row_lds(L.d, (int)L.T_global, L.n), shape_switches());
     const size_t lds = pt_row_lds(L.d, L.T, pl.two && pl.sl ? L.n : 0);
@@ -639,31 +635,29 @@ static hipError_t launch_pt_row_p(const PtLaunch& L, const PtRowSync& S, const d
     Sa.rot = pl.rot;
     Sa.xcd_map = pl.xcd_map;
     Prior pra = pr;
-    void* args[] = {&La, &Sa, (void*)&series, &pra, (void*)&temps, &theta, &logpost, &chol, &naccept, &nswap, &samples, &sample_lp};
+    void* args[] = {&La, &Sa, (void*)&series, &pra, (void*)&b.temps, &b.theta, &b.logpost, &b.chol, &b.naccept, &b.nswap,
+                    &b.samples, &b.sample_lp};
     if (!pl.cooperative) return hipLaunchKernel(fn, dim3((unsigned)pl.grid), dim3(256), args, lds, st);
     // The runtime checks that the whole grid is resident at once (hipErrorCooperativeLaunchTooLarge otherwise, and the
     // host falls back to the ladder kernel) and schedules the grid as a gang, instead of this code assuming it.
     return hipLaunchCooperativeKernel(fn, dim3((unsigned)pl.grid), dim3(256), args, (unsigned)lds, st);
 }
 
-hipError_t launch_pt_row(int p, const PtLaunch& L, const PtRowSync& S, const double4* series, const Prior& pr,
-                         const double* temps, double* theta, double* logpost, double* chol, unsigned* naccept,
-                         unsigned* nswap, double* samples, double* sample_lp, hipStream_t st)
+hipError_t launch_pt_row(int p, const PtLaunch& L, const PtRowSync& S, const double4* series, const Prior& pr, const PtBuffers& b,
+                         hipStream_t st)
 {
     (void)hipGetLastError();   // HIP's last-error is sticky: drop anything left by earlier calls
     return for_order(p, hipErrorInvalidValue, [&](auto P) {
-        return launch_pt_row_p<decltype(P)::value>(L, S, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st);
+        return launch_pt_row_p<decltype(P)::value>(L, S, series, pr, b, st);
     });
 }
 
-hipError_t launch_pt(int p, const PtLaunch& L, const double4* series, const Prior& pr, const double* temps,
-                     double* theta, double* logpost, double* chol, unsigned* naccept, unsigned* nswap, double* samples,
-                     double* sample_lp, hipStream_t st)
+hipError_t launch_pt(int p, const PtLaunch& L, const double4* series, const Prior& pr, const PtBuffers& b, hipStream_t st)
 {
     (void)hipGetLastError();   // HIP's last-error is sticky: drop anything left by earlier calls
-    if (p == 1) return launch_pt_p<1>(L, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st);
+    if (p == 1) return launch_pt_p<1>(L, series, pr, b, st);
     return for_order(p, hipErrorInvalidValue, [&](auto P) {
-        return launch_pt_p<decltype(P)::value>(L, series, pr, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, st);
+        return launch_pt_p<decltype(P)::value>(L, series, pr, b, st);
     });
 }
 

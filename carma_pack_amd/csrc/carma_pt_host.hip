@@ -19,32 +19,17 @@
 
 namespace carma {
 
-// ---- the ensemble both samplers hold (PtEnsemble, carma_host.h) ------------------------------------------------------------------
+// ---- the ensemble both samplers hold (PtEnsemble, carma_pt_state.h) --------------------------------------------------------------
 hipError_t pt_ens_create(PtEnsemble* s, int T, int R, int d, const std::vector<double>& temps, const double* chol)
 {
-    s->T = T;
-    s->R = R;
     s->temps = temps;
+    hipError_t e = s->reserve(T, R, d);
     const size_t nchain = s->nchain();
-    hipError_t e = dev_malloc(&s->d_temps, sizeof(double) * T);
-    if (e == hipSuccess) e = dev_malloc(&s->d_theta, sizeof(double) * nchain * d);
-    if (e == hipSuccess) e = dev_malloc(&s->d_lp, sizeof(double) * nchain);
-    if (e == hipSuccess) e = dev_malloc(&s->d_chol, sizeof(double) * nchain * d * d);
-    if (e == hipSuccess) e = dev_malloc(&s->d_nacc, sizeof(unsigned) * nchain);
-    if (e == hipSuccess) e = dev_malloc(&s->d_nswap, sizeof(unsigned) * nchain);
     if (e == hipSuccess) e = hipMemcpy(s->d_temps, s->temps.data(), sizeof(double) * T, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(s->d_chol, chol, sizeof(double) * nchain * d * d, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(s->d_nacc, 0, sizeof(unsigned) * nchain);
     if (e == hipSuccess) e = hipMemset(s->d_nswap, 0, sizeof(unsigned) * nchain);
     return e;
-}
-
-void pt_ens_release(PtEnsemble* s)
-{
-    if (s->ext_state) s->d_theta = s->d_lp = nullptr;
-    for (void* p : {(void*)s->d_temps, (void*)s->d_theta, (void*)s->d_lp, (void*)s->d_chol, (void*)s->d_nacc, (void*)s->d_nswap,
-                    (void*)s->d_samples, (void*)s->d_slp, (void*)s->d_scratch})
-        if (p) (void)dev_free(p);
 }
 
 PtLaunch pt_ens_launch(const PtEnsemble* s, int d, int q, int n, long ch, int do_exchange, int thin, long save_offset)
@@ -90,23 +75,6 @@ hipError_t pt_ens_get_chains(const PtEnsemble* s, int d, double* theta, double* 
     if (theta) e = hipMemcpy(theta, s->d_theta, sizeof(double) * s->nchain() * d, hipMemcpyDeviceToHost);
     if (e == hipSuccess && lp) e = hipMemcpy(lp, s->d_lp, sizeof(double) * s->nchain(), hipMemcpyDeviceToHost);
     return e;
-}
-
-hipError_t pt_ens_reserve_samples(PtEnsemble* s, int d, int nsamples, long* capacity)
-{
-    if (s->cap < nsamples) {
-        if (s->d_samples) (void)dev_free(s->d_samples);
-        if (s->d_slp) (void)dev_free(s->d_slp);
-        s->d_samples = s->d_slp = nullptr;
-        s->cap = 0;
-        hipError_t e = dev_malloc(&s->d_samples, sizeof(double) * (size_t)s->R * nsamples * d);
-        if (e == hipSuccess) e = dev_malloc(&s->d_slp, sizeof(double) * (size_t)s->R * nsamples);
-        if (e != hipSuccess) return e;
-        s->cap = nsamples;
-    }
-    *capacity = s->cap;
-    s->cap = nsamples;   // stride of this call's output
-    return hipSuccess;
 }
 
 hipError_t pt_ens_fetch_samples(const PtEnsemble* s, int d, int nsamples, double* samples, double* logposts)
@@ -166,18 +134,6 @@ hipError_t pt_ens_set_factor(PtEnsemble* s, int d, hipStream_t st, const double*
     return e;
 }
 
-void pt_state_free(Ctx* c)
-{
-    PtState* s = c->pt;
-    if (!s) return;
-    pt_ens_release(s);
-    for (void* p : {(void*)s->d_stage, (void*)s->d_abort, (void*)s->d_backup, (void*)s->d_send, (void*)s->d_recv, (void*)s->d_bnd_swaps,
-                    (void*)s->d_checksum})
-        if (p) (void)dev_free(p);
-    delete s;
-    c->pt = nullptr;
-}
-
 static int chunk_iters(const Ctx* c)
 {
     // Iterations per launch.  Ladder kernel: around a quarter of a second (~0.8 us per datum per iteration for p >= 5).
@@ -198,7 +154,7 @@ static int chunk_iters(const Ctx* c)
 // one launch of `ch` iterations on `st`
 static int pt_enqueue_one(Ctx* c, long ch, int do_exchange, int thin, long* save_offset, hipStream_t st)
 {
-    PtState* s = c->pt;
+    PtState* s = c->pt.get();
     PtLaunch L = pt_ens_launch(s, c->d, c->q, c->n, ch, do_exchange, thin, save_offset ? *save_offset : 0);
     L.slot0 = s->slot0;                                     // this context's block of the ladder and of the replicas (carma_pt_shard)
     L.T_global = s->T_global;
@@ -206,24 +162,20 @@ static int pt_enqueue_one(Ctx* c, long ch, int do_exchange, int thin, long* save
     hipError_t e;
     if (s->use_row) {
         PtRowSync S{s->d_stage, s->d_abort, ++s->epoch, s->wpl, device_cus(), 1, c->series_flags(), 0};
-        e = launch_pt_row(c->p, L, S, reinterpret_cast<const double4*>(c->d_series), c->pr, s->d_temps, s->d_theta, s->d_lp,
-                          s->d_chol, s->d_nacc, s->d_nswap, s->d_samples, s->d_slp, st);
+        e = launch_pt_row(c->p, L, S, c->rec(), c->pr, pt_ens_buffers(s), st);
         if (e == hipErrorCooperativeLaunchTooLarge) {      // the grid is not co-resident on this device: ladder kernel
             (void)hipGetLastError();
             s->use_row = false;
         }
     }
     if (!s->use_row && s->use_lane) {
-        e = launch_pt_lane(c->p, L, s->d_scratch, reinterpret_cast<const double4*>(c->d_series), c->pr, s->d_temps, s->d_theta,
-                           s->d_lp, s->d_chol, s->d_nacc, s->d_nswap, s->d_samples, s->d_slp, c->series_flags(), !s->factor_loaded,
-                           st);
+        e = launch_pt_lane(c->p, L, s->d_scratch, c->rec(), c->pr, pt_ens_buffers(s), c->series_flags(), !s->factor_loaded, st);
         if (e == hipSuccess) {
             s->factor_loaded = true;                   // ... and stays in the scratch: the chain-major copy is behind until
             s->chol_stale = true;                           // somebody asks for it (pt_ens_sync_factor)
         }
     } else if (!s->use_row) {
-        e = launch_pt(c->p, L, reinterpret_cast<const double4*>(c->d_series), c->pr, s->d_temps, s->d_theta, s->d_lp,
-                      s->d_chol, s->d_nacc, s->d_nswap, s->d_samples, s->d_slp, st);
+        e = launch_pt(c->p, L, c->rec(), c->pr, pt_ens_buffers(s), st);
     }
     if (e != hipSuccess) return hip_fail(e, "launch pt kernel");
     pt_ens_advance(s, ch, thin, save_offset);
@@ -245,7 +197,7 @@ int pt_enqueue(Ctx* c, long niter, int do_exchange, int thin, long* save_offset,
 
 int pt_check_abort(Ctx* c, bool* aborted)
 {
-    PtState* s = c->pt;
+    PtState* s = c->pt.get();
     *aborted = false;
     if (!s->use_row) return CARMA_OK;
     unsigned flag = 0;
@@ -258,7 +210,7 @@ int pt_check_abort(Ctx* c, bool* aborted)
 // chain state <-> backup (theta, logpost, chol), asynchronous on st
 static hipError_t pt_backup(Ctx* c, bool restore, hipStream_t st)
 {
-    PtState* s = c->pt;
+    PtState* s = c->pt.get();
     const size_t nchain = (size_t)s->T * s->R, d = c->d;
     double* b = s->d_backup;
     struct Part { double* p; size_t n; } parts[3] = {{s->d_theta, nchain * d}, {s->d_lp, nchain}, {s->d_chol, nchain * d * d}};
@@ -283,7 +235,7 @@ static hipError_t pt_backup(Ctx* c, bool restore, hipStream_t st)
 // guards against a wedged GPU), the chunk is restored and re-run -- like everything after it -- with the ladder kernel.
 static int pt_launch_chunks(Ctx* c, long niter, int do_exchange, int thin, long* save_offset)
 {
-    PtState* s = c->pt;
+    PtState* s = c->pt.get();
     if (!s->use_row) {
         int rc = pt_enqueue(c, niter, do_exchange, thin, save_offset, c->stream);
         if (rc != CARMA_OK) return rc;
@@ -344,9 +296,8 @@ int carma_pt_create(carma_ctx* h, int ntemps, int nreplicas, const double* tempe
     }
     hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    pt_state_free(c);
-    PtState* s = new PtState();
-    c->pt = s;
+    c->pt.reset(new PtState());           // (the state of an earlier call goes, with every buffer it holds)
+    PtState* s = c->pt.get();
     s->T_global = ntemps;
     s->maxiter = adapt_iters;
     s->seed = seed;
@@ -371,23 +322,19 @@ int carma_pt_create(carma_ctx* h, int ntemps, int nreplicas, const double* tempe
         const PtFamily fam = pt_family(c->p, ntemps, nreplicas, c->n, f, shape_switches(), forced, tv ? atol(tv) : TUNE_UNSET);
         if (fam == PtFamily::LANE) {
             s->use_lane = true;
-            e = dev_malloc(&s->d_scratch, sizeof(double) * pt_lane_scratch_doubles(d, (long)nchain));
+            e = s->d_scratch.alloc(pt_lane_scratch_doubles(d, (long)nchain));
         } else if (fam == PtFamily::ROW) {
             s->use_row = true;
             s->wpl = (ntemps + 3) / 4;
-            // tagged staging: two buffers x two copies of (theta[d], log-posterior) per chain; zeroed once (an all-zero
-            // pair of words never validates)
-            e = dev_malloc(&s->d_stage, sizeof(unsigned long long) * 4 * nchain * (d + 1));
+            // the tagged staging is zeroed once (an all-zero pair of words never validates)
+            e = s->reserve_row(d);
             if (e == hipSuccess) e = hipMemset(s->d_stage, 0, sizeof(unsigned long long) * 4 * nchain * (d + 1));
-            if (e == hipSuccess) e = dev_malloc(&s->d_abort, sizeof(unsigned));
             if (e == hipSuccess) e = hipMemset(s->d_abort, 0, sizeof(unsigned));
-            if (e == hipSuccess) e = dev_malloc(&s->d_backup, sizeof(double) * nchain * (d + 1 + (size_t)d * d));
         }
     }
     if (e != hipSuccess) {
-        int rc = hip_fail(e, "carma_pt_create");
-        pt_state_free(c);
-        return rc;
+        c->pt.reset();
+        return hip_fail(e, "carma_pt_create");
     }
     return CARMA_OK;
 }
@@ -395,7 +342,7 @@ int carma_pt_create(carma_ctx* h, int ntemps, int nreplicas, const double* tempe
 int carma_pt_shard(carma_ctx* h, int ntemps_global, int slot0, int replica0)
 {
     if (!h || !reinterpret_cast<Ctx*>(h)->pt) return CARMA_EINVAL;
-    PtState* s = reinterpret_cast<Ctx*>(h)->pt;
+    PtState* s = reinterpret_cast<Ctx*>(h)->pt.get();
     if (ntemps_global < s->T || slot0 < 0 || slot0 + s->T > ntemps_global || replica0 < 0) {
         set_error("carma_pt_shard: bad shard");
         return CARMA_EINVAL;
@@ -410,18 +357,12 @@ int carma_pt_bind_state(carma_ctx* h, double* d_theta, double* d_logpost)
 {
     if (!h || !reinterpret_cast<Ctx*>(h)->pt || !d_theta || !d_logpost) return CARMA_EINVAL;
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    PtState* s = c->pt;
+    PtState* s = c->pt.get();
     const size_t nchain = (size_t)s->T * s->R;
     hipError_t e = hipMemcpy(d_theta, s->d_theta, sizeof(double) * nchain * c->d, hipMemcpyDeviceToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_logpost, s->d_lp, sizeof(double) * nchain, hipMemcpyDeviceToDevice);
     if (e != hipSuccess) return hip_fail(e, "carma_pt_bind_state");
-    if (!s->ext_state) {
-        (void)dev_free(s->d_theta);
-        (void)dev_free(s->d_lp);
-    }
-    s->d_theta = d_theta;
-    s->d_lp = d_logpost;
-    s->ext_state = true;
+    s->bind(d_theta, d_logpost);
     return CARMA_OK;
 }
 
@@ -445,7 +386,7 @@ int carma_pt_set_chains(carma_ctx* h, const double* theta, const double* logpost
 {
     if (!h || !reinterpret_cast<Ctx*>(h)->pt || !theta) return CARMA_EINVAL;
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    PtState* s = c->pt;
+    PtState* s = c->pt.get();
     const size_t nchain = (size_t)s->T * s->R;
     std::vector<double> lp(nchain);
     if (logpost) {
@@ -468,7 +409,7 @@ int carma_pt_get_chains(carma_ctx* h, double* theta, double* logpost)
 {
     if (!h || !reinterpret_cast<Ctx*>(h)->pt) return CARMA_EINVAL;
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    const hipError_t e = pt_ens_get_chains(c->pt, c->d, theta, logpost);
+    const hipError_t e = pt_ens_get_chains(c->pt.get(), c->d, theta, logpost);
     if (e != hipSuccess) return hip_fail(e, "carma_pt_get_chains");
     return CARMA_OK;
 }
@@ -480,7 +421,7 @@ int carma_pt_start(carma_ctx* h, const double* init, int ninit)
         return CARMA_EINVAL;
     }
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    PtState* s = c->pt;
+    PtState* s = c->pt.get();
     const int d = c->d;
     const size_t nchain = (size_t)s->T * s->R;
     std::vector<double> theta(nchain * d), lp(nchain, -std::numeric_limits<double>::infinity());
@@ -541,7 +482,7 @@ int carma_pt_sample(carma_ctx* h, int nsamples, int thin, double* samples, doubl
         return CARMA_EINVAL;
     }
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    PtState* s = c->pt;
+    PtState* s = c->pt.get();
     if (!s->started) {
         set_error("carma_pt_sample: chains have no starting values");
         return CARMA_EINVAL;
@@ -549,8 +490,8 @@ int carma_pt_sample(carma_ctx* h, int nsamples, int thin, double* samples, doubl
     hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     long capacity = 0;
-    e = pt_ens_reserve_samples(s, c->d, nsamples, &capacity);
-    if (e != hipSuccess) return hip_fail(e, "dev_malloc(samples)");
+    e = s->reserve_samples(c->d, nsamples, &capacity);
+    if (e != hipSuccess) return hip_fail(e, "carma_pt_sample: sample buffers");
     long off = 0;
     int rc = pt_launch_chunks(c, (long)nsamples * thin, 1, thin, &off);
     if (rc == CARMA_OK) {
@@ -564,7 +505,7 @@ int carma_pt_sample(carma_ctx* h, int nsamples, int thin, double* samples, doubl
 int carma_pt_stats(carma_ctx* h, double* accept_rate, double* swap_rate, int reset)
 {
     if (!h || !reinterpret_cast<Ctx*>(h)->pt) return CARMA_EINVAL;
-    const hipError_t e = pt_ens_stats(reinterpret_cast<Ctx*>(h)->pt, accept_rate, swap_rate, reset);
+    const hipError_t e = pt_ens_stats(reinterpret_cast<Ctx*>(h)->pt.get(), accept_rate, swap_rate, reset);
     if (e != hipSuccess) return hip_fail(e, "carma_pt_stats");
     return CARMA_OK;
 }
@@ -572,7 +513,7 @@ int carma_pt_stats(carma_ctx* h, double* accept_rate, double* swap_rate, int res
 int carma_pt_kernel_in_use(const carma_ctx* h)
 {
     if (!h || !reinterpret_cast<const Ctx*>(h)->pt) return CARMA_EINVAL;
-    const PtState* s = reinterpret_cast<const Ctx*>(h)->pt;
+    const PtState* s = reinterpret_cast<const Ctx*>(h)->pt.get();
     return s->use_row ? 1 : (s->use_lane ? 2 : 0);
 }
 

@@ -353,9 +353,8 @@ static hipError_t ram_launch_d(int d, F&& f)
 // K1 is the caller's: k1(thn [nc][d], nc, ll [nc], st) enqueues the log-densities of the nc proposals.  The bookkeeping kernels never
 // touch a series, so whoever supplies K1 decides what a chain is evaluated on (launch_pt_lane below: one series for all chains;
 // carma_mpt.hip: every ladder on a series of its own).
-hipError_t launch_pt_lane_k1(int p, const PtLaunch& L, double* scratch, const PtLaneK1& k1, const double* temps, double* theta,
-                             double* logpost, double* chol, unsigned* naccept, unsigned* nswap, double* samples, double* sample_lp,
-                             bool load_factor, hipStream_t st)
+hipError_t launch_pt_lane_k1(int p, const PtLaunch& L, double* scratch, const PtLaneK1& k1, const PtBuffers& b, bool load_factor,
+                             hipStream_t st)
 {
     (void)hipGetLastError();
     if (p < 1 || L.T < 1 || L.T > 64 || L.d < 4 || L.d > RAM_DMAX || (p == 1) != (L.d == 4)) return hipErrorInvalidValue;
@@ -364,7 +363,7 @@ hipError_t launch_pt_lane_k1(int p, const PtLaunch& L, double* scratch, const Pt
     const int LPW = 64 / L.T;
     const long waves = ((long)L.R + LPW - 1) / LPW;
     const unsigned grid = (unsigned)((waves + 3) / 4), gridc = (unsigned)((nc + 255) / 256);
-    hipLaunchKernelGGL(k_ram_convert, dim3(gridc), dim3(256), 0, st, L, S, theta, logpost, chol, 1,
+    hipLaunchKernelGGL(k_ram_convert, dim3(gridc), dim3(256), 0, st, L, S, b.theta, b.logpost, b.chol, 1,
                        RAM_CONV_STATE | (load_factor ? RAM_CONV_FACTOR : 0));
     hipError_t e = hipGetLastError();
     for (int it = 0; it < L.niter && e == hipSuccess; it++) {
@@ -387,31 +386,30 @@ hipError_t launch_pt_lane_k1(int p, const PtLaunch& L, double* scratch, const Pt
             const bool next = fused && it + 1 < L.niter;
             e = ram_launch_d(L.d, [&](auto dc) {
                 if (next)
-                    hipLaunchKernelGGL((k_ram_finish<decltype(dc)::value, true>), dim3(grid), dim3(256), 0, st, Li, S, temps, naccept,
-                                       nswap, samples, sample_lp);
+                    hipLaunchKernelGGL((k_ram_finish<decltype(dc)::value, true>), dim3(grid), dim3(256), 0, st, Li, S, b.temps,
+                                       b.naccept, b.nswap, b.samples, b.sample_lp);
                 else
-                    hipLaunchKernelGGL((k_ram_finish<decltype(dc)::value, false>), dim3(grid), dim3(256), 0, st, Li, S, temps, naccept,
-                                       nswap, samples, sample_lp);
+                    hipLaunchKernelGGL((k_ram_finish<decltype(dc)::value, false>), dim3(grid), dim3(256), 0, st, Li, S, b.temps,
+                                       b.naccept, b.nswap, b.samples, b.sample_lp);
             });
         }
     }
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_ram_convert, dim3(gridc), dim3(256), 0, st, L, S, theta, logpost, chol, 0, RAM_CONV_STATE);
+        hipLaunchKernelGGL(k_ram_convert, dim3(gridc), dim3(256), 0, st, L, S, b.theta, b.logpost, b.chol, 0, RAM_CONV_STATE);
         e = hipGetLastError();
     }
     return e;
 }
 
 // ... with the batched log-density launch of ONE series as K1: the single-series sampler
-hipError_t launch_pt_lane(int p, const PtLaunch& L, double* scratch, const double4* series, const Prior& pr,
-                          const double* temps, double* theta, double* logpost, double* chol, unsigned* naccept,
-                          unsigned* nswap, double* samples, double* sample_lp, int series_flags, bool load_factor, hipStream_t st)
+hipError_t launch_pt_lane(int p, const PtLaunch& L, double* scratch, const double4* series, const Prior& pr, const PtBuffers& b,
+                          int series_flags, bool load_factor, hipStream_t st)
 {
     const PtLaneK1 k1 = [&](const double* thn, long nc, double* ll, hipStream_t s) {
         return p == 1 ? launch_logdens_car1(thn, (int)nc, series, L.n, pr, ll, s)
                       : launch_logdens_carma(p, thn, (int)nc, L.d, L.q, series, L.n, pr, 0, ll, s, series_flags);
     };
-    return launch_pt_lane_k1(p, L, scratch, k1, temps, theta, logpost, chol, naccept, nswap, samples, sample_lp, load_factor, st);
+    return launch_pt_lane_k1(p, L, scratch, k1, b, load_factor, st);
 }
 
 // the chain-minor factors -> the chain-major array chol [R][T][d][d] (enqueued on st)

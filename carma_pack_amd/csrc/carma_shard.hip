@@ -295,9 +295,9 @@ static int iterate_sharded(carma_ctx* const* shards, int nlocal, long niter, car
             return CARMA_EINVAL;
         }
     }
-    PtState* s0 = cs[0]->pt;
+    PtState* s0 = cs[0]->pt.get();
     for (int i = 0; i < nlocal; i++) {
-        PtState* s = cs[i]->pt;
+        PtState* s = cs[i]->pt.get();
         const bool chained = i == 0 || s->slot0 == cs[i - 1]->pt->slot0 + (unsigned)cs[i - 1]->pt->T;
         if (s->R != s0->R || cs[i]->d != cs[0]->d || s->T_global != s0->T_global || s->replica0 != s0->replica0 ||
             s->seed != s0->seed || s->iter != s0->iter || cs[i]->device != cs[0]->device || !chained) {
@@ -325,15 +325,15 @@ static int iterate_sharded(carma_ctx* const* shards, int nlocal, long niter, car
     const int R = s0->R, d = cs[0]->d;
     const size_t nbuf = (size_t)R * (d + 1) + 1;     // boundary chains of all replicas + the boundary temperature
     for (int i = 0; i < nlocal; i++) {
-        PtState* s = cs[i]->pt;
+        PtState* s = cs[i]->pt.get();
         if (!s->d_send) {
-            e = dev_malloc(&s->d_send, sizeof(double) * nbuf);
-            if (e == hipSuccess) e = dev_malloc(&s->d_recv, sizeof(double) * nbuf);
-            if (e == hipSuccess) e = dev_malloc(&s->d_bnd_swaps, sizeof(unsigned));
+            e = s->reserve_boundary(nbuf);
             if (e == hipSuccess) e = hipMemset(s->d_bnd_swaps, 0, sizeof(unsigned));
-            if (e == hipSuccess) e = dev_malloc(&s->d_checksum, 4 * sizeof(unsigned long long));
             if (e == hipSuccess) e = hipMemset(s->d_checksum, 0, 4 * sizeof(unsigned long long));
-            if (e != hipSuccess) return hip_fail(e, "carma_pt_iterate_sharded: boundary buffers");
+            if (e != hipSuccess) {
+                s->release_boundary();                // all four or none: the next call asks again
+                return hip_fail(e, "carma_pt_iterate_sharded: boundary buffers");
+            }
         }
     }
     // every block of this process on ONE stream (block 0's): kernels, RCCL calls and swap kernels are ordered by it
@@ -374,9 +374,9 @@ static int iterate_sharded(carma_ctx* const* shards, int nlocal, long niter, car
     // one boundary, as seen from this process: one side (the peer is another rank) or both (lower block first)
     auto exchange = [&](const Side* sides, int nsides, unsigned long long iter) -> int {
         for (int a = 0; a < nsides; a++) {
-            PtState* s = cs[sides[a].local]->pt;
+            PtState* s = cs[sides[a].local]->pt.get();
             hipLaunchKernelGGL(k_shard_pack, dim3((unsigned)((nbuf + tpb - 1) / tpb)), dim3(tpb), 0, st, s->d_theta, s->d_lp, R,
-                               s->T, d, sides[a].mine, s->temps[sides[a].mine], s->d_send);
+                               s->T, d, sides[a].mine, s->temps[sides[a].mine], s->d_send.get());
         }
         hipError_t el = hipGetLastError();
         if (el != hipSuccess) return hip_fail(el, "k_shard_pack");
@@ -387,7 +387,7 @@ static int iterate_sharded(carma_ctx* const* shards, int nlocal, long niter, car
         ncclResult_t nr = api->GroupStart();
         if (nr != ncclSuccess) return rccl_fail(nr, "ncclGroupStart");
         for (int a = 0; a < nsides; a++) {
-            PtState* s = cs[sides[a].local]->pt;
+            PtState* s = cs[sides[a].local]->pt.get();
             double* recv_into = nsides == 2 ? cs[sides[1 - a].local]->pt->d_recv : s->d_recv;
             nr = api->Send(s->d_send, nbuf, ncclDouble, sides[a].peer, cm->nccl, st);
             if (nr == ncclSuccess) nr = api->Recv(recv_into, nbuf, ncclDouble, sides[a].peer, cm->nccl, st);
@@ -400,11 +400,11 @@ static int iterate_sharded(carma_ctx* const* shards, int nlocal, long niter, car
         if (nr != ncclSuccess) return rccl_fail(nr, "ncclGroupEnd");
         stamp(ST_XFER, cur_it);
         for (int a = 0; a < nsides; a++) {
-            PtState* s = cs[sides[a].local]->pt;
+            PtState* s = cs[sides[a].local]->pt.get();
             const unsigned hot_slot = sides[a].upper ? s->slot0 + (unsigned)s->T : s->slot0;      // global slot of the hotter chain
             hipLaunchKernelGGL(k_shard_swap, dim3((unsigned)((R + tpb - 1) / tpb)), dim3(tpb), 0, st, s->d_theta, s->d_lp, R, s->T, d,
-                               sides[a].mine, s->d_recv, sides[a].upper, s->temps[sides[a].mine], (unsigned)(s->seed & 0xffffffffu),
-                               (unsigned)(s->seed >> 32), iter, s->T_global, s->replica0, hot_slot, s->d_bnd_swaps, s->d_nswap,
+                               sides[a].mine, s->d_recv.get(), sides[a].upper, s->temps[sides[a].mine], (unsigned)(s->seed & 0xffffffffu),
+                               (unsigned)(s->seed >> 32), iter, s->T_global, s->replica0, hot_slot, s->d_bnd_swaps.get(), s->d_nswap.get(),
                                s->d_checksum + (sides[a].upper ? 1 : 0));
             s->bnd_proposed += (unsigned long long)R;
         }
@@ -426,7 +426,7 @@ static int iterate_sharded(carma_ctx* const* shards, int nlocal, long niter, car
             // the sweep of the whole ladder, hottest pair first, as far as this process holds a side of it
             for (int i = nlocal - 1; i >= 0 && rc_loop == CARMA_OK; i--) {
                 const int gb = rank * nlocal + i;
-                PtState* s = cs[i]->pt;
+                PtState* s = cs[i]->pt.get();
                 if (i == nlocal - 1 && gb + 1 < nblocks) {             // the hotter neighbour is another rank's block
                     const Side sd{i, s->T - 1, 1, rank + 1};
                     rc_loop = exchange(&sd, 1, iter);
@@ -434,8 +434,8 @@ static int iterate_sharded(carma_ctx* const* shards, int nlocal, long niter, car
                 }
                 if (s->T > 1) {
                     hipLaunchKernelGGL(k_shard_sweep, dim3((unsigned)((R + tpb - 1) / tpb)), dim3(tpb), 0, st, s->d_theta, s->d_lp, R, s->T,
-                                       d, s->d_temps, (unsigned)(s->seed & 0xffffffffu), (unsigned)(s->seed >> 32), iter, s->T_global,
-                                       s->replica0, s->slot0, s->d_nswap);
+                                       d, s->d_temps.get(), (unsigned)(s->seed & 0xffffffffu), (unsigned)(s->seed >> 32), iter, s->T_global,
+                                       s->replica0, s->slot0, s->d_nswap.get());
                     e = hipGetLastError();
                     if (e != hipSuccess) {
                         rc_loop = hip_fail(e, "k_shard_sweep");
@@ -469,7 +469,7 @@ static int iterate_sharded(carma_ctx* const* shards, int nlocal, long niter, car
         ncclResult_t nr = ncclSuccess;
         for (int i = nlocal - 1; i >= 0 && nr == ncclSuccess; i--) {
             const int gb = rank * nlocal + i;
-            PtState* s = cs[i]->pt;
+            PtState* s = cs[i]->pt.get();
             // d_checksum: [0] lower side, [1] upper side of this block, [2] / [3] what the peers of those sides report
             if (i == nlocal - 1 && gb + 1 < nblocks) {
                 nr = api->GroupStart();
@@ -480,7 +480,7 @@ static int iterate_sharded(carma_ctx* const* shards, int nlocal, long niter, car
             if (gb > 0 && nr == ncclSuccess) {
                 nr = api->GroupStart();
                 if (i > 0) {
-                    PtState* sl = cs[i - 1]->pt;
+                    PtState* sl = cs[i - 1]->pt.get();
                     if (nr == ncclSuccess) nr = api->Send(sl->d_checksum + 1, 1, ncclUint64, rank, cm->nccl, st);
                     if (nr == ncclSuccess) nr = api->Recv(s->d_checksum + 2, 1, ncclUint64, rank, cm->nccl, st);
                     if (nr == ncclSuccess) nr = api->Send(s->d_checksum, 1, ncclUint64, rank, cm->nccl, st);
@@ -619,7 +619,7 @@ int carma_pt_debug_draws(carma_ctx* h, int replica, int temperature, unsigned lo
 {
     if (!h || !reinterpret_cast<Ctx*>(h)->pt || !z) return CARMA_EINVAL;
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    PtState* s = c->pt;
+    PtState* s = c->pt.get();
     if (replica < 0 || replica >= s->R || temperature < 0 || temperature >= s->T) {
         set_error("carma_pt_debug_draws: chain (%d, %d) outside %d x %d", replica, temperature, s->R, s->T);
         return CARMA_EINVAL;
@@ -649,7 +649,7 @@ int carma_pt_get_factor(carma_ctx* h, double* chol)
 {
     if (!h || !reinterpret_cast<Ctx*>(h)->pt || !chol) return CARMA_EINVAL;
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    const hipError_t e = pt_ens_get_factor(c->pt, c->d, c->stream, chol);
+    const hipError_t e = pt_ens_get_factor(c->pt.get(), c->d, c->stream, chol);
     if (e != hipSuccess) return hip_fail(e, "carma_pt_get_factor");
     return CARMA_OK;
 }
@@ -658,7 +658,7 @@ int carma_pt_set_factor(carma_ctx* h, const double* chol)
 {
     if (!h || !reinterpret_cast<Ctx*>(h)->pt || !chol) return CARMA_EINVAL;
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    const hipError_t e = pt_ens_set_factor(c->pt, c->d, c->stream, chol);
+    const hipError_t e = pt_ens_set_factor(c->pt.get(), c->d, c->stream, chol);
     if (e != hipSuccess) return hip_fail(e, "carma_pt_set_factor");
     return CARMA_OK;
 }
@@ -670,13 +670,13 @@ int carma_pt_sweep(carma_ctx* h)
         return CARMA_EINVAL;
     }
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    PtState* s = c->pt;
+    PtState* s = c->pt.get();
     hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     if (s->T > 1) {
         hipLaunchKernelGGL(k_shard_sweep, dim3((unsigned)((s->R + 63) / 64)), dim3(64), 0, c->stream, s->d_theta, s->d_lp, s->R, s->T, c->d,
-                           s->d_temps, (unsigned)(s->seed & 0xffffffffu), (unsigned)(s->seed >> 32), s->iter - 1, s->T_global,
-                           s->replica0, s->slot0, s->d_nswap);
+                           s->d_temps.get(), (unsigned)(s->seed & 0xffffffffu), (unsigned)(s->seed >> 32), s->iter - 1, s->T_global,
+                           s->replica0, s->slot0, s->d_nswap.get());
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) return hip_fail(e, "carma_pt_sweep");
@@ -687,7 +687,7 @@ int carma_pt_sweep(carma_ctx* h)
 int carma_pt_boundary_stats(carma_ctx* h, unsigned long long* proposed, unsigned long long* accepted)
 {
     if (!h || !reinterpret_cast<Ctx*>(h)->pt) return CARMA_EINVAL;
-    PtState* s = reinterpret_cast<Ctx*>(h)->pt;
+    PtState* s = reinterpret_cast<Ctx*>(h)->pt.get();
     unsigned acc = 0;
     if (s->d_bnd_swaps) {
         hipError_t e = hipMemcpy(&acc, s->d_bnd_swaps, sizeof(unsigned), hipMemcpyDeviceToHost);

@@ -5,6 +5,8 @@ CARMA_LIB_PATH, so that the outputs of two runs can be compared as files:
                                 evaluation and ladder counts at which the choice changes, at this device's CU count -> stdout
   shape_ab.py bits OUT.npz      log-densities of a fixed pool of prior-like thetas at p = 5, 3, 7 on the README series in launches of
                                 512 ... 4097 evaluations, and the chains of 200 iterations of the row sampler at 16 x 64 from one seed
+  shape_ab.py samplers OUT.npz  chains, factors, statistics and 25 samples of the ladder, row, lane and multi-series samplers at
+                                16 x 64 after 200 iterations from one seed
   shape_ab.py cmp A.npz B.npz   np.array_equal of every array of two such files
   shape_ab.py calls             wall time of 10^4 back-to-back carma_logdensity_batch_dev calls at B = 16, five times"""
 import os
@@ -79,6 +81,36 @@ def bits(out):
     print("wrote", out, len(res), "arrays;", res["row_kernel"][0])
 
 
+def samplers(out):
+    """Chains, factors, statistics and samples of the ladder, row, lane and multi-series samplers at 16 x 64 from one seed after 200
+    iterations (profiles/r10)."""
+    import carma_pack_amd as cpa
+    t, y, e = readme()
+    ms = 10.0 * y.std()
+    res = {}
+
+    def record(name, s):
+        s.pt_start(None)
+        s.pt_iterate(200)
+        res[name + "_theta"], res[name + "_lp"] = s.pt_get_chains()
+        res[name + "_factor"] = s.pt_get_factor()
+        res[name + "_accept"], res[name + "_swap"] = s.pt_stats()
+        res[name + "_samples"], res[name + "_sample_lp"] = s.pt_sample(25, thin=2)
+
+    for kern in ("ladder", "row", "lane"):
+        os.environ["CARMA_PT_KERNEL"] = kern
+        ctx = cpa.Context(t, y, e, 5, 3, max_stdev=ms)
+        ctx.pt_create(16, 64, adapt_iters=100, seed=11)
+        res[kern + "_kernel"] = np.array([ctx.pt_kernel()])
+        record(kern, ctx)
+    os.environ.pop("CARMA_PT_KERNEL", None)
+    mc = cpa.MultiContext([(t, y, e), (t[:150], y[:150], e[:150])], 5, 3)
+    mc.pt_create([0, 1], 16, 32, adapt_iters=100, seed=11)         # two runs of 32 ladders: 64 ladders of 16
+    record("multi", mc)
+    np.savez(out, **res)
+    print("wrote", out, len(res), "arrays;", " ".join(res[k + "_kernel"][0] for k in ("ladder", "row", "lane")))
+
+
 def cmp(a, b):
     A, B = np.load(a), np.load(b)
     assert sorted(A.files) == sorted(B.files)
@@ -113,4 +145,4 @@ def calls():
 
 
 if __name__ == "__main__":
-    {"names": names, "bits": bits, "cmp": cmp, "calls": calls}[sys.argv[1]](*sys.argv[2:])
+    {"names": names, "bits": bits, "samplers": samplers, "cmp": cmp, "calls": calls}[sys.argv[1]](*sys.argv[2:])
