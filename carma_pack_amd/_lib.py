@@ -3,6 +3,9 @@
 This is the ONLY route from Python to the compute path.  There is no CPU fallback: if the
 shared library is missing the import fails, and without a gfx950 device every compute call
 raises ``CarmaDeviceError``.
+
+Layout: SIGNATURES (the C ABI, once), the small marshalling helpers every wrapper uses, the handle base and the sampler
+mixin, then the classes and the stateless calls.  Every wrapper names the C function it calls and spells out its arguments.
 """
 import ctypes as C
 import importlib.util
@@ -18,8 +21,125 @@ LIB_PATH = os.environ.get("CARMA_LIB_PATH") or os.path.join(_HERE, "libcarma_mi3
 CARMA_OK, CARMA_EINVAL, CARMA_ENODEV, CARMA_ENOMEM, CARMA_EHIP = 0, -22, -19, -12, -5
 PMAX = 7
 
-_dp = C.POINTER(C.c_double)
-_ip = C.POINTER(C.c_int)
+_dp, _ip, _lp = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_long)
+_ullp = C.POINTER(C.c_ulonglong)
+_I, _L, _D, _V, _S, _U64 = C.c_int, C.c_long, C.c_double, C.c_void_p, C.c_char_p, C.c_uint64
+_SERIES = [_dp, _dp, _dp, _I]                                    # time, y, yerr, n
+_MLE_TAIL = [_I, _I, _D, _D, _D, _I, _V, _V, _V, _V, _V]         # maxiter ... ignore_prior, x, fun, nit, nfev, status
+_ITEMS = [_V, _ip, _I, _dp, _dp, _dp, _I, _dp]                   # handle, which, M, sigsqr, roots, ma, nma, mu
+_AT_TIMES = _ITEMS + [_dp, _lp, _dp, _dp, _ip]                   # ... times, toff, mean, var, singular
+
+# name -> (restype, argtypes): every function include/carma_mi355.h declares.  _load() applies it, EXPORTS is its keys, and
+# tests/test_capi_signatures_cpu.py holds it to the header.  c_void_p entries take device addresses as integers (the _dev
+# entry points) or are called by tests and tools with data_as(c_void_p): they stay c_void_p.
+SIGNATURES = {
+    "carma_version": (_S, []),
+    "carma_last_error": (_S, []),
+    "carma_device_count": (_I, []),
+    "carma_tune_set": (_I, [_S, _L]),
+    "carma_ctx_create": (_V, _SERIES + [_I, _I, _D, _I]),
+    "carma_ctx_destroy": (None, [_V]),
+    "carma_ctx_n": (_I, [_V]),
+    "carma_ctx_dim": (_I, [_V]),
+    "carma_ctx_get_data": (_I, [_V, _dp, _dp, _dp]),
+    "carma_ctx_get_prior": (_I, [_V, _dp]),
+    "carma_ctx_set_prior": (_I, [_V, _D]),
+    "carma_logdensity_batch": (_I, [_V, _dp, _I, _I, _dp]),
+    "carma_logdensity_batch_dev": (_I, [_V, _V, _I, _I, _V, _V]),
+    "carma_logdensity_kernel_name": (_I, [_V, _I, _S, _I]),
+    "carma_logprior": (_D, [_V, _dp]),
+    "carma_mle_batched": (_I, [_V, _V, _I, _V, _V] + _MLE_TAIL),
+    "carma_mctx_create": (_V, [_dp, _dp, _dp, _lp, _I, _I, _I, _dp, _I]),
+    "carma_mctx_destroy": (None, [_V]),
+    "carma_mctx_nseries": (_I, [_V]),
+    "carma_mctx_dim": (_I, [_V]),
+    "carma_mctx_n": (_I, [_V, _I]),
+    "carma_mctx_get_data": (_I, [_V, _I, _dp, _dp, _dp]),
+    "carma_mctx_get_prior": (_I, [_V, _I, _dp]),
+    "carma_mlogdensity_batch": (_I, [_V, _dp, _ip, _I, _I, _dp]),
+    "carma_mlogdensity_kernel_name": (_I, [_V, _S, _I]),
+    "carma_mkfilter": (_I, _ITEMS + [_dp, _dp, _lp, _ip]),
+    "carma_mpredict": (_I, _AT_TIMES),
+    "carma_msmooth": (_I, _AT_TIMES),
+    "carma_mle_batched_ms": (_I, [_V, _V, _V, _I, _V, _V] + _MLE_TAIL),
+    "carma_bands_create": (_V, [_dp, _dp, _dp, _lp, _I, _I, _I, _dp, _dp, _D, _I]),
+    "carma_bands_destroy": (None, [_V]),
+    "carma_bands_dim": (_I, [_V]),
+    "carma_bands_nbands": (_I, [_V]),
+    "carma_bands_n": (_I, [_V, _I]),
+    "carma_bands_get_prior": (_I, [_V, _dp]),
+    "carma_bands_logdensity_batch": (_I, [_V, _dp, _I, _I, _dp]),
+    "carma_bands_logdensity_batch_dev": (_I, [_V, _V, _I, _I, _V, _V]),
+    "carma_bands_mle_batched": (_I, [_V, _V, _I, _V, _V, _V] + _MLE_TAIL),
+    "carma_kfilter_carma": (_I, _SERIES + [_I, _D, _dp, _dp, _I, _dp, _dp, _ip, _I]),
+    "carma_kfilter_batch_carma": (_I, _SERIES + [_I, _I, _dp, _dp, _dp, _I, _dp, _dp, _dp, _ip, _ip, _I]),
+    "carma_kfilter_car1": (_I, _SERIES + [_D, _D, _dp, _dp, _ip, _I]),
+    "carma_predict_carma": (_I, _SERIES + [_I, _D, _dp, _dp, _I, _dp, _I, _dp, _dp, _I]),
+    "carma_predict_car1": (_I, _SERIES + [_D, _D, _dp, _I, _dp, _dp, _I]),
+    "carma_normalize_roots": (_I, [_I, _dp, _dp]),
+    "carma_kf_create_carma": (_V, _SERIES + [_I, _D, _dp, _dp, _I, _I]),
+    "carma_kf_create_car1": (_V, _SERIES + [_D, _D, _I]),
+    "carma_kf_destroy": (None, [_V]),
+    "carma_kf_n": (_I, [_V]),
+    "carma_kf_filter": (_I, [_V, _dp, _dp]),
+    "carma_kf_predict": (_I, [_V, _dp, _I, _dp, _dp]),
+    "carma_simulate_carma": (_I, [_dp, _I, _I, _D, _dp, _dp, _I, _I, _U64, _dp, _I]),
+    "carma_simulate_car1": (_I, [_dp, _I, _D, _D, _I, _U64, _dp, _I]),
+    "carma_simulate_cond_carma": (_I, _SERIES + [_I, _I, _dp, _dp, _dp, _I, _dp, _dp, _I, _U64, C.c_uint, _dp, _dp, _dp, _ip,
+                                                 _ip, _I]),
+    "carma_simulate_cond_car1": (_I, _SERIES + [_I, _dp, _dp, _dp, _dp, _I, _U64, C.c_uint, _dp, _dp, _dp, _ip, _ip, _I]),
+    "carma_smooth_carma": (_I, _SERIES + [_I, _I, _dp, _dp, _dp, _I, _dp, _dp, _I, _dp, _dp, _dp, _dp, _ip, _ip, _I]),
+    "carma_smooth_car1": (_I, _SERIES + [_I, _dp, _dp, _dp, _dp, _I, _dp, _dp, _dp, _dp, _ip, _ip, _I]),
+    "carma_sigma_noise_batch": (_I, [_I, _I, _dp, _dp, _dp, _I, _dp, _I]),
+    "carma_psd_band": (_I, [_I, _I, _dp, _dp, _dp, _I, _dp, _I, _dp, _I, _dp, _dp, _I]),
+    "carma_mpsd_band": (_I, [_I, _I, _dp, _dp, _dp, _lp, _I, _dp, _I, _dp, _I, _dp, _I]),
+    "carma_mpsd_fused_max": (_I, []),
+    "carma_mpsd_freq_tile": (_I, []),
+    "carma_chain_diag": (_I, [_dp, _L, _I, _L, _I, _dp, _dp, _dp, _ip, _dp, _I]),
+    "carma_chain_diag_dmax": (_I, []),
+    "carma_chain_diag_kernel_ms": (_D, []),
+    "carma_pt_run": (_I, [_V, _I, _I, _I, _I, _I, _dp, _I, _U64, _dp, _dp]),
+    "carma_pt_create": (_I, [_V, _I, _I, _dp, _I, _U64]),
+    "carma_pt_shard": (_I, [_V, _I, _I, _I]),
+    "carma_pt_bind_state": (_I, [_V, _V, _V]),
+    "carma_pt_start": (_I, [_V, _dp, _I]),
+    "carma_pt_set_chains": (_I, [_V, _dp, _dp]),
+    "carma_pt_get_chains": (_I, [_V, _dp, _dp]),
+    "carma_pt_get_factor": (_I, [_V, _dp]),
+    "carma_pt_set_factor": (_I, [_V, _dp]),
+    "carma_pt_iterate": (_I, [_V, _L, _I]),
+    "carma_pt_sample": (_I, [_V, _I, _I, _dp, _dp]),
+    "carma_pt_stats": (_I, [_V, _dp, _dp, _I]),
+    "carma_pt_iterations_done": (_L, [_V]),
+    "carma_pt_iterate_sharded": (_I, [C.POINTER(_V), _I, _L, _V]),
+    "carma_pt_sample_sharded": (_I, [C.POINTER(_V), _I, _I, _I, _V, _dp, _dp]),
+    "carma_pt_boundary_stats": (_I, [_V, _ullp, _ullp]),
+    "carma_pt_boundary_check": (_I, [_V]),
+    "carma_pt_kernel_in_use": (_I, [_V]),
+    "carma_pt_row_pipeline": (_I, []),
+    "carma_pt_sweep": (_I, [_V]),
+    "carma_pt_debug_draws": (_I, [_V, _I, _I, C.c_ulonglong, _dp, _dp, _dp]),
+    "carma_mpt_create": (_I, [_V, _ip, _I, _I, _I, _dp, _I, _U64]),
+    "carma_mpt_start": (_I, [_V, _dp]),
+    "carma_mpt_set_chains": (_I, [_V, _dp, _dp]),
+    "carma_mpt_get_chains": (_I, [_V, _dp, _dp]),
+    "carma_mpt_get_factor": (_I, [_V, _dp]),
+    "carma_mpt_set_factor": (_I, [_V, _dp]),
+    "carma_mpt_iterate": (_I, [_V, _L, _I]),
+    "carma_mpt_sample": (_I, [_V, _I, _I, _dp, _dp]),
+    "carma_mpt_stats": (_I, [_V, _dp, _dp, _I]),
+    "carma_mpt_iterations_done": (_L, [_V]),
+    "carma_mpt_logdensity": (_I, [_V, _dp, _dp]),
+    "carma_mpt_kernel_name": (_I, [_V, _S, _I]),
+    "carma_mpt_run": (_I, [_V, _ip, _I, _I, _I, _I, _I, _I, _dp, _U64, _dp, _dp]),
+    "carma_comm_unique_id": (_I, [_V]),
+    "carma_comm_create": (_V, [_V, _I, _I, _I]),
+    "carma_comm_destroy": (None, [_V]),
+    "carma_comm_rank": (_I, [_V]),
+    "carma_comm_size": (_I, [_V]),
+}
+EXPORTS = list(SIGNATURES)
+TUNE_SWITCHES = ("WIN_ROWS", "WIN2_EVALS", "PT_ROW_WIN", "CSIM_CHUNK_PATHS", "SMOOTH_CHUNK_MODELS")
 
 
 class CarmaError(RuntimeError):
@@ -30,14 +150,16 @@ class CarmaDeviceError(CarmaError):
     pass
 
 
-def _share_hip_runtime_with_torch():
+def _share_with_torch(libname):
     """One process, ONE HIP runtime.  The PyTorch wheel bundles its own libamdhip64.so (soname libamdhip64.so.7, like
     the system's); whichever copy is mapped first serves every later request for that soname, but `import torch` asks
     for it by file name and would map a SECOND runtime if this library had already pulled in /opt/rocm's.  Two runtimes
     in one process cannot share streams or device pointers (the `_dev` entry points take torch's) and cooperative
-    launches fail outright (measured: hipErrorUnknown).  So when PyTorch is installed and not yet imported, its copy is
-    mapped first -- without importing torch.  CARMA_HIP_RUNTIME=system keeps the system runtime."""
-    if "torch" in sys.modules or os.environ.get("CARMA_HIP_RUNTIME") == "system":
+    launches fail outright (measured: hipErrorUnknown).  So when PyTorch is installed and not yet imported, its copy of
+    `libname` is mapped first -- without importing torch.  The same for RCCL (bound by the library at run time as
+    librccl.so.1), also when torch is imported already: its copy -- and the HIP runtime it was built against -- is the
+    one carma_comm_* finds.  CARMA_HIP_RUNTIME=system keeps the system's libraries."""
+    if os.environ.get("CARMA_HIP_RUNTIME") == "system" or (libname == "libamdhip64.so" and "torch" in sys.modules):
         return
     try:
         spec = importlib.util.find_spec("torch")
@@ -45,23 +167,7 @@ def _share_hip_runtime_with_torch():
         return
     if spec is None or not spec.submodule_search_locations:
         return
-    cand = os.path.join(list(spec.submodule_search_locations)[0], "lib", "libamdhip64.so")
-    if os.path.exists(cand):
-        C.CDLL(cand, mode=C.RTLD_GLOBAL)
-
-
-def _share_rccl_with_torch():
-    """Same for RCCL (bound by the library at run time as librccl.so.1): map PyTorch's copy first when there is one, so
-    that it -- and the HIP runtime it was built against -- is the one carma_comm_* finds."""
-    if os.environ.get("CARMA_HIP_RUNTIME") == "system":
-        return
-    try:
-        spec = importlib.util.find_spec("torch")
-    except (ImportError, ValueError):
-        return
-    if spec is None or not spec.submodule_search_locations:
-        return
-    cand = os.path.join(list(spec.submodule_search_locations)[0], "lib", "librccl.so")
+    cand = os.path.join(list(spec.submodule_search_locations)[0], "lib", libname)
     if os.path.exists(cand):
         C.CDLL(cand, mode=C.RTLD_GLOBAL)
 
@@ -99,180 +205,28 @@ def _load():
         raise ImportError(
             "carma_pack_amd: %s not found -- build it with ./build.sh (or __graft_entry__.build()); "
             "there is no CPU fallback" % LIB_PATH)
-    _share_hip_runtime_with_torch()
+    _share_with_torch("libamdhip64.so")
     L = C.CDLL(LIB_PATH)
-    L.carma_version.restype = C.c_char_p
-    L.carma_last_error.restype = C.c_char_p
-    L.carma_device_count.restype = C.c_int
-    L.carma_ctx_create.restype = C.c_void_p
-    L.carma_ctx_create.argtypes = [_dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int]
-    L.carma_ctx_destroy.argtypes = [C.c_void_p]
-    L.carma_ctx_destroy.restype = None
-    L.carma_ctx_n.argtypes = [C.c_void_p]
-    L.carma_ctx_dim.argtypes = [C.c_void_p]
-    L.carma_ctx_get_data.argtypes = [C.c_void_p, _dp, _dp, _dp]
-    L.carma_ctx_get_prior.argtypes = [C.c_void_p, _dp]
-    L.carma_ctx_set_prior.argtypes = [C.c_void_p, C.c_double]
-    L.carma_logdensity_batch.argtypes = [C.c_void_p, _dp, C.c_int, C.c_int, _dp]
-    L.carma_logdensity_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.carma_logdensity_kernel_name.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int]
-    L.carma_tune_set.argtypes = [C.c_char_p, C.c_long]
-    L.carma_tune_set.restype = C.c_int
-    L.carma_mle_batched.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
-                                    C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.carma_mle_batched.restype = C.c_int
-    L.carma_mctx_create.restype = C.c_void_p
-    L.carma_mctx_create.argtypes = [_dp, _dp, _dp, C.POINTER(C.c_long), C.c_int, C.c_int, C.c_int, _dp, C.c_int]
-    L.carma_mctx_destroy.argtypes = [C.c_void_p]
-    L.carma_mctx_destroy.restype = None
-    L.carma_mctx_nseries.argtypes = [C.c_void_p]
-    L.carma_mctx_dim.argtypes = [C.c_void_p]
-    L.carma_mctx_n.argtypes = [C.c_void_p, C.c_int]
-    L.carma_mctx_get_data.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
-    L.carma_mctx_get_prior.argtypes = [C.c_void_p, C.c_int, _dp]
-    L.carma_mlogdensity_batch.argtypes = [C.c_void_p, _dp, _ip, C.c_int, C.c_int, _dp]
-    L.carma_mlogdensity_kernel_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-    L.carma_mkfilter.argtypes = [C.c_void_p, _ip, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_long), _ip]
-    L.carma_mpredict.argtypes = [C.c_void_p, _ip, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, C.POINTER(C.c_long), _dp, _dp, _ip]
-    L.carma_mle_batched_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                       C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p]
-    L.carma_msmooth.argtypes = [C.c_void_p, _ip, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, C.POINTER(C.c_long), _dp, _dp, _ip]
-    L.carma_bands_create.restype = C.c_void_p
-    L.carma_bands_create.argtypes = [_dp, _dp, _dp, C.POINTER(C.c_long), C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_int]
-    L.carma_bands_destroy.argtypes = [C.c_void_p]
-    L.carma_bands_destroy.restype = None
-    L.carma_bands_dim.argtypes = [C.c_void_p]
-    L.carma_bands_nbands.argtypes = [C.c_void_p]
-    L.carma_bands_n.argtypes = [C.c_void_p, C.c_int]
-    L.carma_bands_get_prior.argtypes = [C.c_void_p, _dp]
-    L.carma_bands_logdensity_batch.argtypes = [C.c_void_p, _dp, C.c_int, C.c_int, _dp]
-    L.carma_bands_logdensity_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.carma_bands_mle_batched.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                          C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p]
-    L.carma_mpt_create.argtypes = [C.c_void_p, _ip, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_uint64]
-    L.carma_mpt_start.argtypes = [C.c_void_p, _dp]
-    L.carma_mpt_set_chains.argtypes = [C.c_void_p, _dp, _dp]
-    L.carma_mpt_get_chains.argtypes = [C.c_void_p, _dp, _dp]
-    L.carma_mpt_get_factor.argtypes = [C.c_void_p, _dp]
-    L.carma_mpt_set_factor.argtypes = [C.c_void_p, _dp]
-    L.carma_mpt_iterate.argtypes = [C.c_void_p, C.c_long, C.c_int]
-    L.carma_mpt_sample.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp]
-    L.carma_mpt_stats.argtypes = [C.c_void_p, _dp, _dp, C.c_int]
-    L.carma_mpt_iterations_done.argtypes = [C.c_void_p]
-    L.carma_mpt_iterations_done.restype = C.c_long
-    L.carma_mpt_logdensity.argtypes = [C.c_void_p, _dp, _dp]
-    L.carma_mpt_kernel_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-    L.carma_mpt_run.argtypes = [C.c_void_p, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_uint64, _dp, _dp]
-    L.carma_logprior.argtypes = [C.c_void_p, _dp]
-    L.carma_logprior.restype = C.c_double
-    L.carma_kfilter_batch_carma.argtypes = [_dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp,
-                                            C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
-    L.carma_kfilter_batch_carma.restype = C.c_int
-    L.carma_kfilter_carma.argtypes = [_dp, _dp, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_int, _dp, _dp,
-                                      _ip, C.c_int]
-    L.carma_kfilter_car1.argtypes = [_dp, _dp, _dp, C.c_int, C.c_double, C.c_double, _dp, _dp, _ip, C.c_int]
-    L.carma_predict_carma.argtypes = [_dp, _dp, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_int, _dp, C.c_int,
-                                      _dp, _dp, C.c_int]
-    L.carma_predict_car1.argtypes = [_dp, _dp, _dp, C.c_int, C.c_double, C.c_double, _dp, C.c_int, _dp, _dp, C.c_int]
-    L.carma_normalize_roots.argtypes = [C.c_int, _dp, _dp]
-    L.carma_kf_create_carma.restype = C.c_void_p
-    L.carma_kf_create_carma.argtypes = [_dp, _dp, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_int, C.c_int]
-    L.carma_kf_create_car1.restype = C.c_void_p
-    L.carma_kf_create_car1.argtypes = [_dp, _dp, _dp, C.c_int, C.c_double, C.c_double, C.c_int]
-    L.carma_kf_destroy.argtypes = [C.c_void_p]
-    L.carma_kf_destroy.restype = None
-    L.carma_kf_n.argtypes = [C.c_void_p]
-    L.carma_kf_filter.argtypes = [C.c_void_p, _dp, _dp]
-    L.carma_kf_predict.argtypes = [C.c_void_p, _dp, C.c_int, _dp, _dp]
-    L.carma_simulate_carma.argtypes = [_dp, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_int, C.c_int, C.c_uint64, _dp, C.c_int]
-    L.carma_simulate_car1.argtypes = [_dp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_uint64, _dp, C.c_int]
-    L.carma_simulate_cond_carma.argtypes = [_dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, C.c_int,
-                                            C.c_uint64, C.c_uint, _dp, _dp, _dp, _ip, _ip, C.c_int]
-    L.carma_simulate_cond_car1.argtypes = [_dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_uint64, C.c_uint,
-                                           _dp, _dp, _dp, _ip, _ip, C.c_int]
-    L.carma_smooth_carma.argtypes = [_dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, C.c_int,
-                                     _dp, _dp, _dp, _dp, _ip, _ip, C.c_int]
-    L.carma_smooth_car1.argtypes = [_dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
-                                    C.c_int]
-    L.carma_sigma_noise_batch.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int]
-    L.carma_psd_band.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int]
-    L.carma_mpsd_band.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_long), C.c_int, _dp, C.c_int, _dp, C.c_int, _dp,
-                                  C.c_int]
-    L.carma_mpsd_fused_max.argtypes = []
-    L.carma_mpsd_freq_tile.argtypes = []
-    L.carma_chain_diag.argtypes = [_dp, C.c_long, C.c_int, C.c_long, C.c_int, _dp, _dp, _dp, _ip, _dp, C.c_int]
-    L.carma_chain_diag_dmax.argtypes = []
-    L.carma_chain_diag_kernel_ms.argtypes = []
-    L.carma_chain_diag_kernel_ms.restype = C.c_double
-    L.carma_pt_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_uint64,
-                               _dp, _dp]
-    L.carma_pt_create.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, C.c_uint64]
-    L.carma_pt_shard.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-    L.carma_pt_bind_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.carma_pt_start.argtypes = [C.c_void_p, _dp, C.c_int]
-    L.carma_pt_set_chains.argtypes = [C.c_void_p, _dp, _dp]
-    L.carma_pt_get_chains.argtypes = [C.c_void_p, _dp, _dp]
-    L.carma_pt_iterate.argtypes = [C.c_void_p, C.c_long, C.c_int]
-    L.carma_pt_sample.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp]
-    L.carma_pt_stats.argtypes = [C.c_void_p, _dp, _dp, C.c_int]
-    L.carma_pt_iterations_done.argtypes = [C.c_void_p]
-    L.carma_pt_iterations_done.restype = C.c_long
-    L.carma_comm_unique_id.argtypes = [C.c_void_p]
-    L.carma_comm_create.restype = C.c_void_p
-    L.carma_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-    L.carma_comm_destroy.argtypes = [C.c_void_p]
-    L.carma_comm_destroy.restype = None
-    L.carma_comm_rank.argtypes = [C.c_void_p]
-    L.carma_comm_size.argtypes = [C.c_void_p]
-    L.carma_pt_iterate_sharded.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_long, C.c_void_p]
-    L.carma_pt_sample_sharded.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, _dp, _dp]
-    L.carma_pt_boundary_stats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
-    L.carma_pt_boundary_check.argtypes = [C.c_void_p]
-    L.carma_pt_kernel_in_use.argtypes = [C.c_void_p]
-    L.carma_pt_row_pipeline.argtypes = []
-    L.carma_pt_sweep.argtypes = [C.c_void_p]
-    L.carma_pt_debug_draws.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_ulonglong, _dp, _dp, _dp]
-    L.carma_pt_get_factor.argtypes = [C.c_void_p, _dp]
-    L.carma_pt_set_factor.argtypes = [C.c_void_p, _dp]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     return L
 
 
 lib = _load()
 
-# every symbol include/carma_mi355.h declares (kept in sync by tests/test_capi_symbols.py)
-EXPORTS = [
-    "carma_version", "carma_last_error", "carma_device_count", "carma_ctx_create", "carma_ctx_destroy",
-    "carma_ctx_n", "carma_ctx_dim", "carma_ctx_get_data", "carma_ctx_get_prior", "carma_ctx_set_prior",
-    "carma_logdensity_batch", "carma_logdensity_batch_dev", "carma_logdensity_kernel_name", "carma_logprior", "carma_mle_batched", "carma_kfilter_carma", "carma_kfilter_batch_carma",
-    "carma_kfilter_car1", "carma_predict_carma", "carma_predict_car1", "carma_normalize_roots", "carma_kf_create_carma", "carma_kf_create_car1",
-    "carma_kf_destroy", "carma_kf_n", "carma_kf_filter", "carma_kf_predict", "carma_simulate_carma", "carma_simulate_car1", "carma_simulate_cond_carma", "carma_simulate_cond_car1", "carma_smooth_carma", "carma_smooth_car1", "carma_sigma_noise_batch", "carma_psd_band", "carma_pt_run", "carma_pt_create", "carma_pt_shard", "carma_pt_bind_state",
-    "carma_pt_start", "carma_pt_set_chains", "carma_pt_get_chains", "carma_pt_iterate", "carma_pt_sample",
-    "carma_pt_stats", "carma_pt_iterations_done", "carma_comm_unique_id", "carma_comm_create", "carma_comm_destroy",
-    "carma_comm_rank", "carma_comm_size", "carma_pt_iterate_sharded", "carma_pt_sample_sharded", "carma_pt_boundary_stats",
-    "carma_pt_boundary_check", "carma_pt_sweep", "carma_pt_kernel_in_use", "carma_pt_row_pipeline", "carma_pt_debug_draws", "carma_pt_get_factor",
-    "carma_pt_set_factor", "carma_tune_set", "carma_mctx_create", "carma_mctx_destroy", "carma_mctx_nseries", "carma_mctx_dim",
-    "carma_mctx_n", "carma_mctx_get_data", "carma_mctx_get_prior", "carma_mlogdensity_batch", "carma_mlogdensity_kernel_name",
-    "carma_mle_batched_ms", "carma_mkfilter", "carma_mpredict", "carma_msmooth", "carma_mpt_create", "carma_mpt_start", "carma_mpt_set_chains",
-    "carma_mpt_get_chains", "carma_mpt_get_factor", "carma_mpt_set_factor", "carma_mpt_iterate", "carma_mpt_sample",
-    "carma_mpt_stats", "carma_mpt_iterations_done", "carma_mpt_logdensity", "carma_mpt_kernel_name", "carma_mpt_run",
-    "carma_mpsd_band", "carma_mpsd_fused_max", "carma_mpsd_freq_tile", "carma_chain_diag", "carma_chain_diag_dmax", "carma_chain_diag_kernel_ms",
-    "carma_bands_create", "carma_bands_destroy", "carma_bands_dim", "carma_bands_nbands", "carma_bands_n", "carma_bands_get_prior",
-    "carma_bands_logdensity_batch", "carma_bands_logdensity_batch_dev", "carma_bands_mle_batched",
-]
-
 
 def tune_set(name, value):
-    """Move a launch-shape switch ("WIN_ROWS", "WIN2_EVALS", "PT_ROW_WIN", "CSIM_CHUNK_PATHS", "SMOOTH_CHUNK_MODELS": carma_tune_set; measurements and
-    parity tests).
-    value None: back to the library's default."""
     check(lib.carma_tune_set(str(name).encode(), -2 ** 63 if value is None else int(value)), "carma_tune_set")
+
+
+tune_set.__doc__ = """Move a launch-shape switch (%s: carma_tune_set; measurements and parity tests).
+    value None: back to the library's default.""" % ", ".join('"%s"' % s for s in TUNE_SWITCHES)
 
 
 def tune_reset():
     """Every switch back to what the environment said when the library read it (CARMA_TUNE_<name>), or to the default."""
-    for name in ("WIN_ROWS", "WIN2_EVALS", "PT_ROW_WIN", "CSIM_CHUNK_PATHS", "SMOOTH_CHUNK_MODELS"):
+    for name in TUNE_SWITCHES:
         e = os.environ.get("CARMA_TUNE_" + name)
         tune_set(name, None if e is None else int(e))
 
@@ -292,6 +246,17 @@ def check(rc, what):
     raise CarmaError(msg)
 
 
+def default_device():
+    """One process per GPU: LOCAL_RANK picks the device when launched by torch.distributed.run."""
+    n = lib.carma_device_count()
+    lr = int(os.environ.get("LOCAL_RANK", "0"))
+    return lr % n if n > 0 else 0
+
+
+# ---- marshalling helpers: what every wrapper does to its arguments, once -------------------------
+_SINGULAR = "KalmanFilterp: singular eigenvector matrix (solve failed)"
+
+
 def as_f64(x):
     return np.ascontiguousarray(x, dtype=np.float64)
 
@@ -300,38 +265,141 @@ def ptr(a):
     return a.ctypes.data_as(_dp)
 
 
-def default_device():
-    """One process per GPU: LOCAL_RANK picks the device when launched by torch.distributed.run."""
-    n = lib.carma_device_count()
-    lr = int(os.environ.get("LOCAL_RANK", "0"))
-    return lr % n if n > 0 else 0
+def _optr(a):
+    """double* of an optional array: None -> NULL."""
+    return None if a is None else a.ctypes.data_as(_dp)
 
 
-class Context:
-    """Owns one carma_ctx (series resident in HBM + prior bounds)."""
+def _iptr(a):
+    return a.ctypes.data_as(_ip)
 
-    def __init__(self, time, y, yerr, p, q=0, max_stdev=None, device=None):
-        time, y, yerr = as_f64(time), as_f64(y), as_f64(yerr)
-        if not (time.size == y.size == yerr.size):
-            raise ValueError("time, y, yerr must have the same length")
-        if max_stdev is None:
-            # default of the CARMA_Base ctor: 10*sqrt(arma::var(y)) (sample variance, carpack.hpp:71)
-            max_stdev = 10.0 * np.sqrt(np.var(y, ddof=1)) if y.size > 1 else 0.0
-        self.device = default_device() if device is None else int(device)
-        self._h = lib.carma_ctx_create(ptr(time), ptr(y), ptr(yerr), time.size, int(p), int(q), float(max_stdev),
-                                       self.device)
-        if not self._h:
-            msg = "carma_ctx_create failed: " + last_error()
-            if "no HIP device" in msg:
-                raise CarmaDeviceError(msg)
-            raise ValueError(msg)
-        self.p, self.q = int(p), int(q)
-        self.n = lib.carma_ctx_n(self._h)
-        self.d = lib.carma_ctx_dim(self._h)
+
+def _lptr(a):
+    return a.ctypes.data_as(_lp)
+
+
+def _dev(device):
+    return default_device() if device is None else int(device)
+
+
+def _seed(seed):
+    return C.c_uint64(int(seed) & (2 ** 64 - 1))
+
+
+def _reim(z):
+    """Complex roots [...] -> float64 [..., 2] (re, im), as every entry point takes them; a single root counts as [1]."""
+    z = np.atleast_1d(z)
+    return as_f64(np.stack([z.real, z.imag], axis=-1))
+
+
+def _singular(rc, msg):
+    """rc == 1 is the library's "repeated AR root" answer of the single-model calls."""
+    if rc == 1:
+        raise CarmaError(msg)
+
+
+def _created(h, what, exc=None):
+    """The handle a create function returned, or its NULL as the exception (exc None: by the library's message)."""
+    if not h:
+        msg = "%s failed: %s" % (what, last_error())
+        raise (exc or (CarmaDeviceError if "no HIP device" in msg else ValueError))(msg)
+    return h
+
+
+def _default_max_stdev(y):
+    # default of the CARMA_Base ctor: 10*sqrt(arma::var(y)) (sample variance, carpack.hpp:71)
+    return 10.0 * np.sqrt(np.var(y, ddof=1)) if y.size > 1 else 0.0
+
+
+def _offsets(sizes):
+    off = np.zeros(len(sizes) + 1, dtype=np.int64)
+    off[1:] = np.cumsum(sizes)
+    return off
+
+
+def _split(a, off):
+    return [a[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+
+def _concat_series(series, owner, noun):
+    """A list of (t, y, yerr) -> (the y of each, offsets [S + 1], t, y, yerr back to back): MultiContext's series and
+    BandsContext's bands."""
+    series = list(series)
+    if not series:
+        raise ValueError("%s needs at least one %s" % (owner, noun))
+    cols = []
+    for s, item in enumerate(series):
+        if len(item) != 3:
+            raise ValueError("%s %d: expected (t, y, yerr)" % (noun, s))
+        t, y, e = (as_f64(a).ravel() for a in item)
+        if not (t.size == y.size == e.size):
+            raise ValueError("%s %d: time, y, yerr must have the same length" % (noun, s))
+        cols.append((t, y, e))
+    ts, ys, es = zip(*cols)
+    return (ys, _offsets([t.size for t in ts])) + tuple(as_f64(np.concatenate(a)) for a in (ts, ys, es))
+
+
+def _theta_rows(thetas, d):
+    """thetas [d] or [B, d] -> ([B, d], whether it was one row)."""
+    thetas = as_f64(thetas)
+    return thetas.reshape(-1, d), thetas.ndim == 1
+
+
+def _pack_models(who, noun, sigsqr, omega, ma=None):
+    """The K models of a batched stateless call -> (K, p, sigsqr [K], roots, ma).  With ma: omega [K][p] complex ->
+    roots [K][p][2], ma [K][nma]; without (CAR(1)): omega [K] = 1 / tau -> roots [K]."""
+    sig = as_f64(np.atleast_1d(sigsqr))
+    if ma is None:
+        om = as_f64(np.atleast_1d(omega))
+        if om.size != sig.size:
+            raise ValueError("%s: sigsqr and omega must describe the same number of %s" % (who, noun))
+        return sig.size, 1, sig, om, None
+    omega = np.atleast_2d(np.asarray(omega, dtype=complex))
+    K, p = omega.shape
+    ma = as_f64(np.atleast_2d(ma))
+    if ma.shape[0] != K or sig.size != K:
+        raise ValueError("%s: sigsqr, omega and ma must describe the same number of %s" % (who, noun))
+    return K, p, sig, _reim(omega), ma
+
+
+def _pack_mu(mu, K, who, noun):
+    if mu is None:
+        return None
+    mu = as_f64(np.atleast_1d(mu)).ravel()
+    if mu.size != K:
+        raise ValueError("%s: mu must have one entry per %s" % (who, noun))
+    return mu
+
+
+def _mle_x0(x0, d):
+    x0 = np.ascontiguousarray(np.atleast_2d(np.asarray(x0, dtype=np.float64)))
+    B, dd = x0.shape
+    if dd != d:
+        raise ValueError("x0 must be [B, %d]" % d)
+    return x0, B
+
+
+def _mle_tail(B, d, maxiter, mem, ftol, gtol, fd_step, ignore_prior):
+    """The results (x [B, d], fun, nit, nfev, status [B]) of a carma_*mle_batched* call and the arguments all three end in."""
+    out = (np.empty((B, d)), np.empty(B)) + tuple(np.zeros(B, dtype=np.int32) for _ in range(3))
+    return out, (int(maxiter), int(mem), float(ftol), float(gtol), float(fd_step), 1 if ignore_prior else 0, ptr(out[0]),
+                 ptr(out[1])) + tuple(a.ctypes.data_as(C.c_void_p) for a in out[2:])
+
+
+def _kernel_name(what, *args):
+    """A carma_*_kernel_name call: its arguments, then the buffer and its size."""
+    buf = C.create_string_buffer(128)
+    check(getattr(lib, what)(*args, buf, 128), what)
+    return buf.value.decode()
+
+
+class _Handle:
+    """Owns one handle of the library: `_h`, released once by the class's destroy function."""
+    _destroy = None
 
     def close(self):
         if getattr(self, "_h", None):
-            lib.carma_ctx_destroy(self._h)
+            getattr(lib, self._destroy)(self._h)
             self._h = None
 
     def __del__(self):
@@ -343,6 +411,74 @@ class Context:
     @property
     def handle(self):
         return self._h
+
+
+class _Sampler:
+    """The parallel-tempering calls Context (carma_pt_*, chains [R][T]) and MultiContext (carma_mpt_*, chains [M][R][T]) share:
+    `_pt` is the prefix of the C functions, `_pt_lead()` the leading shape (..., R, T) that pt_create / pt_run left."""
+    _pt = None
+
+    def _pt_call(self, name, *args):
+        check(getattr(lib, self._pt + name)(self._h, *args), self._pt + name)
+
+    def pt_set_chains(self, theta, logpost=None):
+        lead = self._pt_lead()
+        theta = as_f64(theta).reshape(lead + (self.d,))
+        lp = as_f64(logpost).reshape(lead) if logpost is not None else None
+        self._pt_call("set_chains", ptr(theta), _optr(lp))
+
+    def pt_get_chains(self):
+        lead = self._pt_lead()
+        theta, lp = np.empty(lead + (self.d,)), np.empty(lead)
+        self._pt_call("get_chains", ptr(theta), ptr(lp))
+        return theta, lp
+
+    def pt_get_factor(self):
+        """chol_factor_ of every chain, [...][R][T][d][d] (upper triangular; src/steps.cpp:32)."""
+        chol = np.empty(self._pt_lead() + (self.d, self.d))
+        self._pt_call("get_factor", ptr(chol))
+        return chol
+
+    def pt_set_factor(self, chol):
+        chol = as_f64(chol).reshape(self._pt_lead() + (self.d, self.d))
+        self._pt_call("set_factor", ptr(chol))
+
+    def pt_iterate(self, niter, do_exchange=True):
+        self._pt_call("iterate", int(niter), int(bool(do_exchange)))
+
+    def pt_sample(self, nsamples, thin=1):
+        """(samples [...][R][nsamples][d], logposts [...][R][nsamples]) of the coldest chains."""
+        head = self._pt_lead()[:-1] + (int(nsamples),)
+        samples, logposts = np.empty(head + (self.d,)), np.empty(head)
+        self._pt_call("sample", int(nsamples), int(thin), ptr(samples), ptr(logposts))
+        return samples, logposts
+
+    def pt_stats(self, reset=False):
+        lead = self._pt_lead()
+        acc, swp = np.empty(lead), np.empty(lead)
+        self._pt_call("stats", ptr(acc), ptr(swp), int(bool(reset)))
+        return acc, swp
+
+    def pt_iterations_done(self):
+        return getattr(lib, self._pt + "iterations_done")(self._h)
+
+
+class Context(_Handle, _Sampler):
+    """Owns one carma_ctx (series resident in HBM + prior bounds)."""
+    _destroy, _pt = "carma_ctx_destroy", "carma_pt_"
+
+    def __init__(self, time, y, yerr, p, q=0, max_stdev=None, device=None):
+        time, y, yerr = as_f64(time), as_f64(y), as_f64(yerr)
+        if not (time.size == y.size == yerr.size):
+            raise ValueError("time, y, yerr must have the same length")
+        if max_stdev is None:
+            max_stdev = _default_max_stdev(y)
+        self.device = _dev(device)
+        self._h = _created(lib.carma_ctx_create(ptr(time), ptr(y), ptr(yerr), time.size, int(p), int(q), float(max_stdev),
+                                                self.device), "carma_ctx_create")
+        self.p, self.q = int(p), int(q)
+        self.n = lib.carma_ctx_n(self._h)
+        self.d = lib.carma_ctx_dim(self._h)
 
     def data(self):
         t, y, e = np.empty(self.n), np.empty(self.n), np.empty(self.n)
@@ -358,9 +494,7 @@ class Context:
         check(lib.carma_ctx_set_prior(self._h, float(max_stdev)), "carma_ctx_set_prior")
 
     def logdensity(self, thetas, ignore_prior=False):
-        thetas = as_f64(thetas)
-        one = thetas.ndim == 1
-        thetas = thetas.reshape(-1, self.d)
+        thetas, one = _theta_rows(thetas, self.d)
         out = np.empty(thetas.shape[0])
         check(lib.carma_logdensity_batch(self._h, ptr(thetas), thetas.shape[0], int(bool(ignore_prior)), ptr(out)),
               "carma_logdensity_batch")
@@ -374,49 +508,45 @@ class Context:
 
     def kernel_name(self, B):
         """Name of the kernel a launch of B evaluations takes (carma_logdensity_kernel_name)."""
-        buf = C.create_string_buffer(128)
-        check(lib.carma_logdensity_kernel_name(self._h, int(B), buf, 128), "carma_logdensity_kernel_name")
-        return buf.value.decode()
+        return _kernel_name("carma_logdensity_kernel_name", self._h, int(B))
 
     def mle_batched(self, x0, bounds, maxiter=2000, mem=8, ftol=2.220446049250313e-09, gtol=1e-5, fd_step=1e-6,
                     ignore_prior=True):
         """carma_mle_batched: lock-step bounded L-BFGS from every row of x0 on -LogDensity, host loop in the library.
         bounds = [(lo, hi)] with None for unbounded.  Returns (x [B, d], fun [B], nit [B], nfev [B], status [B])."""
-        x0 = np.ascontiguousarray(np.atleast_2d(np.asarray(x0, dtype=np.float64)))
-        B, d = x0.shape
-        if d != self.d:
-            raise ValueError("x0 must be [B, %d]" % self.d)
+        x0, B = _mle_x0(x0, self.d)
         lo = np.array([-np.inf if b[0] is None else b[0] for b in bounds], dtype=np.float64)
         hi = np.array([np.inf if b[1] is None else b[1] for b in bounds], dtype=np.float64)
-        x, fun = np.empty((B, d)), np.empty(B)
-        nit, nfev, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
-        check(lib.carma_mle_batched(self._h, ptr(x0), B, ptr(lo), ptr(hi), int(maxiter), int(mem), float(ftol), float(gtol),
-                                    float(fd_step), 1 if ignore_prior else 0, ptr(x), ptr(fun),
-                                    nit.ctypes.data_as(C.c_void_p), nfev.ctypes.data_as(C.c_void_p),
-                                    status.ctypes.data_as(C.c_void_p)), "carma_mle_batched")
-        return x, fun, nit, nfev, status
+        out, tail = _mle_tail(B, self.d, maxiter, mem, ftol, gtol, fd_step, ignore_prior)
+        check(lib.carma_mle_batched(self._h, ptr(x0), B, ptr(lo), ptr(hi), *tail), "carma_mle_batched")
+        return out
 
     def logprior(self, theta):
         theta = as_f64(theta)
         return lib.carma_logprior(self._h, ptr(theta))
 
-    # ---- parallel-tempering sampler (RunCarmaSampler / RunCar1Sampler on the GPU) ----------------
+    # ---- parallel-tempering sampler (RunCarmaSampler / RunCar1Sampler on the GPU); the rest is _Sampler's ----
+    def _pt_lead(self):
+        return self._pt_shape
+
+    @staticmethod
+    def _init_values(init):
+        a = as_f64(init) if init is not None and len(init) else None
+        return _optr(a), 0 if a is None else a.size
+
     def pt_run(self, ntemps, nreplicas, sample_size, burnin, thin=1, init=None, seed=0):
         """Whole Sampler::Run; returns (samples[R][S][d], logposts[R][S]) of the coldest chains."""
-        init_a = as_f64(init) if init is not None and len(init) else None
         samples = np.empty((nreplicas, sample_size, self.d))
         logposts = np.empty((nreplicas, sample_size))
         check(lib.carma_pt_run(self._h, int(ntemps), int(nreplicas), int(sample_size), int(burnin), int(thin),
-                               ptr(init_a) if init_a is not None else None,
-                               init_a.size if init_a is not None else 0, C.c_uint64(int(seed) & (2 ** 64 - 1)),
-                               ptr(samples), ptr(logposts)), "carma_pt_run")
+                               *self._init_values(init), _seed(seed), ptr(samples), ptr(logposts)), "carma_pt_run")
         self._pt_shape = (int(nreplicas), int(ntemps))
         return samples, logposts
 
     def pt_create(self, ntemps, nreplicas, adapt_iters, seed=0, temperatures=None):
         tt = as_f64(temperatures) if temperatures is not None else None
-        check(lib.carma_pt_create(self._h, int(ntemps), int(nreplicas), ptr(tt) if tt is not None else None,
-                                  int(adapt_iters), C.c_uint64(int(seed) & (2 ** 64 - 1))), "carma_pt_create")
+        check(lib.carma_pt_create(self._h, int(ntemps), int(nreplicas), _optr(tt), int(adapt_iters), _seed(seed)),
+              "carma_pt_create")
         self._pt_shape = (int(nreplicas), int(ntemps))
 
     def pt_shard(self, ntemps_global, slot0, replica0):
@@ -428,48 +558,7 @@ class Context:
               "carma_pt_bind_state")
 
     def pt_start(self, init=None):
-        init_a = as_f64(init) if init is not None and len(init) else None
-        check(lib.carma_pt_start(self._h, ptr(init_a) if init_a is not None else None,
-                                 init_a.size if init_a is not None else 0), "carma_pt_start")
-
-    def pt_set_chains(self, theta, logpost=None):
-        R, T = self._pt_shape
-        theta = as_f64(theta).reshape(R, T, self.d)
-        lp = as_f64(logpost).reshape(R, T) if logpost is not None else None
-        check(lib.carma_pt_set_chains(self._h, ptr(theta), ptr(lp) if lp is not None else None), "carma_pt_set_chains")
-
-    def pt_get_chains(self):
-        R, T = self._pt_shape
-        theta, lp = np.empty((R, T, self.d)), np.empty((R, T))
-        check(lib.carma_pt_get_chains(self._h, ptr(theta), ptr(lp)), "carma_pt_get_chains")
-        return theta, lp
-
-    def pt_iterate(self, niter, do_exchange=True):
-        check(lib.carma_pt_iterate(self._h, int(niter), int(bool(do_exchange))), "carma_pt_iterate")
-
-    def pt_sample(self, nsamples, thin=1):
-        R, T = self._pt_shape
-        samples, logposts = np.empty((R, nsamples, self.d)), np.empty((R, nsamples))
-        check(lib.carma_pt_sample(self._h, int(nsamples), int(thin), ptr(samples), ptr(logposts)), "carma_pt_sample")
-        return samples, logposts
-
-    def pt_stats(self, reset=False):
-        R, T = self._pt_shape
-        acc, swp = np.empty((R, T)), np.empty((R, T))
-        check(lib.carma_pt_stats(self._h, ptr(acc), ptr(swp), int(bool(reset))), "carma_pt_stats")
-        return acc, swp
-
-    def pt_get_factor(self):
-        """chol_factor_ of every chain, [R][T][d][d] (upper triangular; src/steps.cpp:32)."""
-        R, T = self._pt_shape
-        chol = np.empty((R, T, self.d, self.d))
-        check(lib.carma_pt_get_factor(self._h, ptr(chol)), "carma_pt_get_factor")
-        return chol
-
-    def pt_set_factor(self, chol):
-        R, T = self._pt_shape
-        chol = np.ascontiguousarray(chol, dtype=np.float64).reshape(R, T, self.d, self.d)
-        check(lib.carma_pt_set_factor(self._h, ptr(chol)), "carma_pt_set_factor")
+        check(lib.carma_pt_start(self._h, *self._init_values(init)), "carma_pt_start")
 
     def pt_debug_draws(self, replica, temperature, iteration):
         """(z[d], u_accept, u_swap): the variates chain (replica, temperature) uses at `iteration`, from the device's own
@@ -489,9 +578,6 @@ class Context:
         """Recursion of the process's last k_pt_row launch: "one-datum", "window", "two-sided" (carma_pt_row_pipeline); None before it."""
         return {0: "one-datum", 1: "window", 2: "two-sided"}.get(lib.carma_pt_row_pipeline())
 
-    def pt_iterations_done(self):
-        return lib.carma_pt_iterations_done(self._h)
-
     def pt_boundary_stats(self):
         """(proposed, accepted) swaps across this block's boundaries (carma_pt_iterate_sharded)."""
         a, b = C.c_ulonglong(0), C.c_ulonglong(0)
@@ -507,26 +593,25 @@ class Context:
         check(lib.carma_pt_sweep(self._h), "carma_pt_sweep")
 
 
-class Comm:
+class Comm(_Handle):
     """RCCL communicator owned by libcarma_mi355.so (carma_comm_*): one rank per process / GPU.
 
     ``Comm.unique_id()`` on rank 0 -> 128 bytes to broadcast with the host program's own bootstrap -> every rank
     ``Comm(id, nranks, rank, device)`` (collective)."""
+    _destroy = "carma_comm_destroy"
 
     @staticmethod
     def unique_id():
-        _share_rccl_with_torch()
+        _share_with_torch("librccl.so")
         buf = C.create_string_buffer(128)
         check(lib.carma_comm_unique_id(buf), "carma_comm_unique_id")
         return buf.raw
 
     def __init__(self, unique_id, nranks, rank, device=None):
-        _share_rccl_with_torch()
-        self.device = default_device() if device is None else int(device)
+        _share_with_torch("librccl.so")
+        self.device = _dev(device)
         self._id = C.create_string_buffer(bytes(unique_id), 128)
-        self._h = lib.carma_comm_create(self._id, int(nranks), int(rank), self.device)
-        if not self._h:
-            raise CarmaError("carma_comm_create failed: " + last_error())
+        self._h = _created(lib.carma_comm_create(self._id, int(nranks), int(rank), self.device), "carma_comm_create", CarmaError)
         self.rank, self.size = int(rank), int(nranks)
 
     @classmethod
@@ -537,49 +622,55 @@ class Comm:
         dist.broadcast_object_list(box, src=0)
         return cls(box[0], world, rank, device)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib.carma_comm_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+def _sharded(contexts, comm):
+    """The leading arguments of the sharded sampler calls: the handles of this process's ladder blocks and their count;
+    and the communicator's handle, which follows the call's own counts."""
+    return (C.c_void_p * len(contexts))(*[c.handle for c in contexts]), len(contexts), comm._h if comm is not None else None
 
 
 def pt_iterate_sharded(contexts, niter, comm=None):
     """carma_pt_iterate_sharded: `contexts` = this process's consecutive ladder blocks (normally one)."""
-    arr = (C.c_void_p * len(contexts))(*[c.handle for c in contexts])
-    check(lib.carma_pt_iterate_sharded(arr, len(contexts), int(niter), comm._h if comm is not None else None),
-          "carma_pt_iterate_sharded")
+    arr, nctx, ch = _sharded(contexts, comm)
+    check(lib.carma_pt_iterate_sharded(arr, nctx, int(niter), ch), "carma_pt_iterate_sharded")
 
 
-class KalmanHandle:
+def pt_sample_sharded(contexts, nsamples, thin=1, comm=None):
+    """carma_pt_sample_sharded: returns (samples[R][nsamples][d], logposts[R][nsamples]) on the process that owns
+    temperature 0, (None, None) elsewhere."""
+    arr, nctx, ch = _sharded(contexts, comm)
+    c0 = contexts[0]
+    owner = getattr(c0, "_pt_slot0", 0) == 0
+    R = c0._pt_shape[0]
+    samples = np.empty((R, int(nsamples), c0.d)) if owner else None
+    logposts = np.empty((R, int(nsamples))) if owner else None
+    check(lib.carma_pt_sample_sharded(arr, nctx, int(nsamples), int(thin), ch, _optr(samples), _optr(logposts)),
+          "carma_pt_sample_sharded")
+    return samples, logposts
+
+
+class KalmanHandle(_Handle):
     """carma_kf: a KalmanFilter1 / KalmanFilterp object whose series and model stay resident in HBM; Filter and any
     number of (batched) Predict calls only launch and copy results back."""
+    _destroy = "carma_kf_destroy"
 
     def __init__(self, time, y, yerr, sigsqr, omega, ma=None, device=None):
         time, y, yerr = as_f64(time), as_f64(y), as_f64(yerr)
-        dev = default_device() if device is None else int(device)
+        dev = _dev(device)
         if ma is None:                                   # CAR(1): omega is the real rate 1 / tau
-            self._h = lib.carma_kf_create_car1(ptr(time), ptr(y), ptr(yerr), time.size, float(sigsqr), float(omega), dev)
+            h = lib.carma_kf_create_car1(ptr(time), ptr(y), ptr(yerr), time.size, float(sigsqr), float(omega), dev)
         else:
             omega = np.asarray(omega, dtype=complex)
-            om, ma = as_f64(np.c_[omega.real, omega.imag]), as_f64(ma)
-            self._h = lib.carma_kf_create_carma(ptr(time), ptr(y), ptr(yerr), time.size, omega.size, float(sigsqr), ptr(om),
-                                                ptr(ma), ma.size, dev)
-        if not self._h:
-            msg = "carma_kf_create failed: " + last_error()
-            raise CarmaDeviceError(msg) if "no HIP device" in msg else ValueError(msg)
+            om, ma = _reim(omega), as_f64(ma)
+            h = lib.carma_kf_create_carma(ptr(time), ptr(y), ptr(yerr), time.size, omega.size, float(sigsqr), ptr(om),
+                                          ptr(ma), ma.size, dev)
+        self._h = _created(h, "carma_kf_create")
         self.n = lib.carma_kf_n(self._h)
 
     def filter(self):
         mean, var = np.empty(self.n), np.empty(self.n)
         rc = lib.carma_kf_filter(self._h, ptr(mean), ptr(var))
-        if rc == 1:
-            raise CarmaError("KalmanFilterp: singular eigenvector matrix (solve failed)")
+        _singular(rc, _SINGULAR)
         check(rc, "carma_kf_filter")
         return mean, var
 
@@ -587,35 +678,20 @@ class KalmanHandle:
         tp = as_f64(np.atleast_1d(tpred))
         pm, pv = np.empty(tp.size), np.empty(tp.size)
         rc = lib.carma_kf_predict(self._h, ptr(tp), tp.size, ptr(pm), ptr(pv))
-        if rc == 1:
-            raise CarmaError("KalmanFilterp: singular eigenvector matrix (solve failed)")
+        _singular(rc, _SINGULAR)
         check(rc, "carma_kf_predict")
         return pm, pv
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib.carma_kf_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def kfilter_carma(time, y, yerr, sigsqr, omega, ma, device=None):
     time, y, yerr = as_f64(time), as_f64(y), as_f64(yerr)
     omega = np.asarray(omega, dtype=complex)
-    om = as_f64(np.c_[omega.real, omega.imag])
-    ma = as_f64(ma)
+    om, ma = _reim(omega), as_f64(ma)
     mean, var = np.empty(time.size), np.empty(time.size)
     nout = C.c_int(0)
     rc = lib.carma_kfilter_carma(ptr(time), ptr(y), ptr(yerr), time.size, omega.size, float(sigsqr), ptr(om), ptr(ma),
-                                 ma.size, ptr(mean), ptr(var), C.byref(nout),
-                                 default_device() if device is None else device)
-    if rc == 1:
-        raise CarmaError("KalmanFilterp: singular eigenvector matrix (solve failed)")
+                                 ma.size, ptr(mean), ptr(var), C.byref(nout), _dev(device))
+    _singular(rc, _SINGULAR)
     check(rc, "carma_kfilter_carma")
     return mean[:nout.value], var[:nout.value]
 
@@ -624,23 +700,13 @@ def kfilter_carma_batch(time, y, yerr, sigsqr, omega, ma, mu=None, device=None):
     """Filter() of B models on one series in one launch: sigsqr [B], omega [B][p] complex, ma [B][nma], mu [B] or None
     -> (mean [B][n], var [B][n], singular [B] bool).  mu is subtracted from y inside and added back to mean."""
     time, y, yerr = as_f64(time), as_f64(y), as_f64(yerr)
-    omega = np.atleast_2d(np.asarray(omega, dtype=complex))
-    B, p = omega.shape
-    om = as_f64(np.stack([omega.real, omega.imag], axis=-1))
-    ma = as_f64(np.atleast_2d(ma))
-    sig = as_f64(np.atleast_1d(sigsqr))
-    if ma.shape[0] != B or sig.size != B:
-        raise ValueError("kfilter_carma_batch: sigsqr, omega and ma must describe the same number of models")
-    mu_ = None if mu is None else as_f64(np.atleast_1d(mu))
-    if mu_ is not None and mu_.size != B:
-        raise ValueError("kfilter_carma_batch: mu must have one entry per model")
+    B, p, sig, om, ma = _pack_models("kfilter_carma_batch", "models", sigsqr, omega, ma)
+    mu_ = _pack_mu(mu, B, "kfilter_carma_batch", "model")
     mean, var = np.empty((B, time.size)), np.empty((B, time.size))
     sing = np.zeros(B, dtype=np.int32)
     nout = C.c_int(0)
     rc = lib.carma_kfilter_batch_carma(ptr(time), ptr(y), ptr(yerr), time.size, p, B, ptr(sig), ptr(om), ptr(ma), ma.shape[1],
-                                       ptr(mu_) if mu_ is not None else None, ptr(mean), ptr(var),
-                                       sing.ctypes.data_as(C.POINTER(C.c_int)), C.byref(nout),
-                                       default_device() if device is None else device)
+                                       _optr(mu_), ptr(mean), ptr(var), _iptr(sing), C.byref(nout), _dev(device))
     check(rc, "carma_kfilter_batch_carma")
     m = nout.value
     # (the library writes rows of n_out values back to back)
@@ -649,61 +715,27 @@ def kfilter_carma_batch(time, y, yerr, sigsqr, omega, ma, mu=None, device=None):
     return mean, var, sing.astype(bool)
 
 
-class MultiContext:
+class MultiContext(_Handle, _Sampler):
     """Owns one carma_mctx: MANY series of one order (p, q) resident in HBM, evaluated in shared launches.
 
     series: a list of (t, y, yerr); each is prepared as Context prepares one (sort, dedup, prior bounds).  max_stdev: None
     (10 sqrt(var(y, ddof=1)) per series, as Context), a number for all series, or one value per series."""
+    _destroy, _pt = "carma_mctx_destroy", "carma_mpt_"
 
     def __init__(self, series, p, q=0, max_stdev=None, device=None):
-        series = list(series)
-        if not series:
-            raise ValueError("MultiContext needs at least one series")
-        ts, ys, es = [], [], []
-        for s, item in enumerate(series):
-            if len(item) != 3:
-                raise ValueError("series %d: expected (t, y, yerr)" % s)
-            t, y, e = (as_f64(a).ravel() for a in item)
-            if not (t.size == y.size == e.size):
-                raise ValueError("series %d: time, y, yerr must have the same length" % s)
-            ts.append(t)
-            ys.append(y)
-            es.append(e)
-        S = len(series)
+        ys, offsets, t_all, y_all, e_all = _concat_series(series, "MultiContext", "series")
+        S = len(ys)
         if max_stdev is None:
-            ms = np.array([10.0 * np.sqrt(np.var(y, ddof=1)) if y.size > 1 else 0.0 for y in ys])
+            ms = np.array([_default_max_stdev(y) for y in ys])
         else:
             ms = np.broadcast_to(as_f64(max_stdev), (S,)).copy()
-        offsets = np.zeros(S + 1, dtype=np.int64)
-        offsets[1:] = np.cumsum([t.size for t in ts])
-        t_all, y_all, e_all = (as_f64(np.concatenate(a)) for a in (ts, ys, es))
-        self.device = default_device() if device is None else int(device)
-        self._h = lib.carma_mctx_create(ptr(t_all), ptr(y_all), ptr(e_all), offsets.ctypes.data_as(C.POINTER(C.c_long)), S,
-                                        int(p), int(q), ptr(ms), self.device)
-        if not self._h:
-            msg = "carma_mctx_create failed: " + last_error()
-            if "no HIP device" in msg:
-                raise CarmaDeviceError(msg)
-            raise ValueError(msg)
+        self.device = _dev(device)
+        self._h = _created(lib.carma_mctx_create(ptr(t_all), ptr(y_all), ptr(e_all), _lptr(offsets), S, int(p), int(q), ptr(ms),
+                                                 self.device), "carma_mctx_create")
         self.p, self.q = int(p), int(q)
         self.nseries = lib.carma_mctx_nseries(self._h)
         self.d = lib.carma_mctx_dim(self._h)
         self.n = np.array([lib.carma_mctx_n(self._h, s) for s in range(self.nseries)], dtype=np.int64)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib.carma_mctx_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        return self._h
 
     def data(self, s):
         n = int(self.n[s])
@@ -724,20 +756,16 @@ class MultiContext:
 
     def logdensity(self, thetas, which, ignore_prior=False):
         """Log-density of thetas[i] on series which[i] (which: one index per row, or one for all), one launch."""
-        thetas = as_f64(thetas)
-        one = thetas.ndim == 1
-        thetas = thetas.reshape(-1, self.d)
+        thetas, one = _theta_rows(thetas, self.d)
         B = thetas.shape[0]
         w = self._which(which, B)
         out = np.empty(B)
-        check(lib.carma_mlogdensity_batch(self._h, ptr(thetas), w.ctypes.data_as(_ip), B, int(bool(ignore_prior)), ptr(out)),
+        check(lib.carma_mlogdensity_batch(self._h, ptr(thetas), _iptr(w), B, int(bool(ignore_prior)), ptr(out)),
               "carma_mlogdensity_batch")
         return float(out[0]) if one else out
 
     def kernel_name(self):
-        buf = C.create_string_buffer(128)
-        check(lib.carma_mlogdensity_kernel_name(self._h, buf, 128), "carma_mlogdensity_kernel_name")
-        return buf.value.decode()
+        return _kernel_name("carma_mlogdensity_kernel_name", self._h)
 
     def _items(self, which, sigsqr, roots, ma, mu, who):
         """The (series, model) items of kfilter / predict as the library takes them; every shape error is raised here."""
@@ -760,11 +788,7 @@ class MultiContext:
             if ma_.ndim != 2 or ma_.shape[0] != M or not (1 <= ma_.shape[1] <= self.p):
                 raise ValueError("%s: ma must be [%d, nma] with 1 <= nma <= %d" % (who, M, self.p))
             nma = ma_.shape[1]
-        om = as_f64(np.stack([roots.real, roots.imag], axis=-1))
-        mu_ = None if mu is None else as_f64(np.atleast_1d(mu)).ravel()
-        if mu_ is not None and mu_.size != M:
-            raise ValueError("%s: mu must have one entry per item" % who)
-        return M, w, sig, om, ma_, nma, mu_
+        return M, w, sig, _reim(roots), ma_, nma, _pack_mu(mu, M, who, "item")
 
     def kfilter(self, which, sigsqr, roots, ma, mu=None):
         """Filter() of M items in one launch (carma_mkfilter): item i is the model (sigsqr[i], roots[i], ma[i]) on series
@@ -772,82 +796,58 @@ class MultiContext:
         None -- subtracted from y inside and added back to the mean.  Returns (means, vars, singular): lists of M arrays, item
         i's of length n[which[i]], and a bool array."""
         M, w, sig, om, ma_, nma, mu_ = self._items(which, sigsqr, roots, ma, mu, "MultiContext.kfilter")
-        off = np.zeros(M + 1, dtype=np.int64)
-        off[1:] = np.cumsum(self.n[w])
+        off = _offsets(self.n[w])
         mean, var = np.empty(off[-1]), np.empty(off[-1])
         sing = np.zeros(M, dtype=np.int32)
-        check(lib.carma_mkfilter(self._h, w.ctypes.data_as(_ip), M, ptr(sig), ptr(om), ptr(ma_), nma,
-                                 ptr(mu_) if mu_ is not None else None, ptr(mean), ptr(var), None, sing.ctypes.data_as(_ip)),
-              "carma_mkfilter")
-        return ([mean[off[i]:off[i + 1]] for i in range(M)], [var[off[i]:off[i + 1]] for i in range(M)], sing.astype(bool))
+        check(lib.carma_mkfilter(self._h, _iptr(w), M, ptr(sig), ptr(om), ptr(ma_), nma, _optr(mu_), ptr(mean), ptr(var), None,
+                                 _iptr(sing)), "carma_mkfilter")
+        return _split(mean, off), _split(var, off), sing.astype(bool)
+
+    def _at_times(self, what, who, which, sigsqr, roots, ma, times, mu, return_singular):
+        """carma_mpredict / carma_msmooth (`what`): M items, item i at times[i]."""
+        M, w, sig, om, ma_, nma, mu_ = self._items(which, sigsqr, roots, ma, mu, who)
+        times = [as_f64(np.atleast_1d(t)).ravel() for t in times]
+        if len(times) != M:
+            raise ValueError("%s: times must hold one array per item (%d), got %d" % (who, M, len(times)))
+        toff = _offsets([t.size for t in times])
+        tp = as_f64(np.concatenate(times)) if toff[-1] else np.zeros(1)       # all empty: one dummy time, outputs of length 1
+        pm, pv = np.empty(max(int(toff[-1]), 1)), np.empty(max(int(toff[-1]), 1))
+        sing = np.zeros(M, dtype=np.int32)
+        check(getattr(lib, what)(self._h, _iptr(w), M, ptr(sig), ptr(om), ptr(ma_), nma, _optr(mu_), ptr(tp), _lptr(toff), ptr(pm),
+                                 ptr(pv), _iptr(sing)), what)
+        if return_singular:
+            return _split(pm, toff), _split(pv, toff), sing.astype(bool)
+        if sing.any():
+            raise CarmaError(_SINGULAR + " for item(s) %s" % np.flatnonzero(sing)[:8].tolist())
+        return _split(pm, toff), _split(pv, toff)
 
     def predict(self, which, sigsqr, roots, ma, times, mu=None, return_singular=False):
         """Predict of M items in one launch (carma_mpredict): item i (as in kfilter) at times[i], a list of M arrays (any of
         them may be empty).  Returns (means, vars): lists of M arrays shaped as times[i].  An item with a repeated AR root
         raises CarmaError, as KalmanHandle.predict does -- or, with return_singular, is flagged in a third return value."""
-        M, w, sig, om, ma_, nma, mu_ = self._items(which, sigsqr, roots, ma, mu, "MultiContext.predict")
-        times = [as_f64(np.atleast_1d(t)).ravel() for t in times]
-        if len(times) != M:
-            raise ValueError("MultiContext.predict: times must hold one array per item (%d), got %d" % (M, len(times)))
-        toff = np.zeros(M + 1, dtype=np.int64)
-        toff[1:] = np.cumsum([t.size for t in times])
-        tp = as_f64(np.concatenate(times)) if toff[-1] else np.zeros(1)
-        pm, pv = np.empty(max(int(toff[-1]), 1)), np.empty(max(int(toff[-1]), 1))
-        sing = np.zeros(M, dtype=np.int32)
-        check(lib.carma_mpredict(self._h, w.ctypes.data_as(_ip), M, ptr(sig), ptr(om), ptr(ma_), nma,
-                                 ptr(mu_) if mu_ is not None else None, ptr(tp), toff.ctypes.data_as(C.POINTER(C.c_long)), ptr(pm),
-                                 ptr(pv), sing.ctypes.data_as(_ip)), "carma_mpredict")
-        if return_singular:
-            return ([pm[toff[i]:toff[i + 1]] for i in range(M)], [pv[toff[i]:toff[i + 1]] for i in range(M)], sing.astype(bool))
-        if sing.any():
-            raise CarmaError("KalmanFilterp: singular eigenvector matrix (solve failed) for item(s) %s"
-                             % np.flatnonzero(sing)[:8].tolist())
-        return [pm[toff[i]:toff[i + 1]] for i in range(M)], [pv[toff[i]:toff[i + 1]] for i in range(M)]
+        return self._at_times("carma_mpredict", "MultiContext.predict", which, sigsqr, roots, ma, times, mu, return_singular)
 
     def smooth(self, which, sigsqr, roots, ma, times, mu=None, return_singular=False):
         """The interpolated light curve of M items in one call (carma_msmooth): arguments and return values as predict, the
         numbers those of predict to rounding -- but from ONE forward and ONE backward pass over an item's series and times
         (O((n + M_i) p^2) per item instead of O(M_i n p^2)): the route for dense curves.  Items that share a series and a list
         of times share waves; an item's outputs have the bits smooth_carma / smooth_car1 gives for it on its series alone."""
-        M, w, sig, om, ma_, nma, mu_ = self._items(which, sigsqr, roots, ma, mu, "MultiContext.smooth")
-        times = [as_f64(np.atleast_1d(t)).ravel() for t in times]
-        if len(times) != M:
-            raise ValueError("MultiContext.smooth: times must hold one array per item (%d), got %d" % (M, len(times)))
-        toff = np.zeros(M + 1, dtype=np.int64)
-        toff[1:] = np.cumsum([t.size for t in times])
-        tp = as_f64(np.concatenate(times)) if toff[-1] else np.zeros(1)
-        pm, pv = np.empty(max(int(toff[-1]), 1)), np.empty(max(int(toff[-1]), 1))
-        sing = np.zeros(M, dtype=np.int32)
-        check(lib.carma_msmooth(self._h, w.ctypes.data_as(_ip), M, ptr(sig), ptr(om), ptr(ma_), nma,
-                                ptr(mu_) if mu_ is not None else None, ptr(tp), toff.ctypes.data_as(C.POINTER(C.c_long)), ptr(pm),
-                                ptr(pv), sing.ctypes.data_as(_ip)), "carma_msmooth")
-        if return_singular:
-            return ([pm[toff[i]:toff[i + 1]] for i in range(M)], [pv[toff[i]:toff[i + 1]] for i in range(M)], sing.astype(bool))
-        if sing.any():
-            raise CarmaError("KalmanFilterp: singular eigenvector matrix (solve failed) for item(s) %s"
-                             % np.flatnonzero(sing)[:8].tolist())
-        return [pm[toff[i]:toff[i + 1]] for i in range(M)], [pv[toff[i]:toff[i + 1]] for i in range(M)]
+        return self._at_times("carma_msmooth", "MultiContext.smooth", which, sigsqr, roots, ma, times, mu, return_singular)
 
     def mle_batched(self, x0, which, lo, hi, maxiter=2000, mem=8, ftol=2.220446049250313e-09, gtol=1e-5, fd_step=1e-6,
                     ignore_prior=True):
         """carma_mle_batched_ms: Context.mle_batched with start i on series which[i] and its own box lo[i], hi[i] ([B, d],
         non-finite = unbounded; or [d] for every start).  Returns (x [B, d], fun [B], nit [B], nfev [B], status [B])."""
-        x0 = np.ascontiguousarray(np.atleast_2d(np.asarray(x0, dtype=np.float64)))
-        B, d = x0.shape
-        if d != self.d:
-            raise ValueError("x0 must be [B, %d]" % self.d)
+        x0, B = _mle_x0(x0, self.d)
         w = self._which(which, B)
-        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.float64), (B, d)))
-        hi = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.float64), (B, d)))
-        x, fun = np.empty((B, d)), np.empty(B)
-        nit, nfev, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
-        check(lib.carma_mle_batched_ms(self._h, ptr(x0), w.ctypes.data_as(C.c_void_p), B, ptr(lo), ptr(hi), int(maxiter), int(mem),
-                                       float(ftol), float(gtol), float(fd_step), 1 if ignore_prior else 0, ptr(x), ptr(fun),
-                                       nit.ctypes.data_as(C.c_void_p), nfev.ctypes.data_as(C.c_void_p),
-                                       status.ctypes.data_as(C.c_void_p)), "carma_mle_batched_ms")
-        return x, fun, nit, nfev, status
+        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.float64), x0.shape))
+        hi = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.float64), x0.shape))
+        out, tail = _mle_tail(B, self.d, maxiter, mem, ftol, gtol, fd_step, ignore_prior)
+        check(lib.carma_mle_batched_ms(self._h, ptr(x0), w.ctypes.data_as(C.c_void_p), B, ptr(lo), ptr(hi), *tail),
+              "carma_mle_batched_ms")
+        return out
 
-    # ---- parallel-tempering sampler over many series (carma_mpt_*) -------------------------------
+    # ---- parallel-tempering sampler over many series (carma_mpt_*); the rest is _Sampler's --------
     def _runs(self, series):
         w = np.asarray(series, dtype=np.int64).ravel()
         if w.size < 1:
@@ -862,6 +862,11 @@ class MultiContext:
             raise ValueError("init must be [%d, %d] (one row per run), got %r" % (M, self.d, a.shape))
         return a
 
+    def _pt_lead(self):
+        if getattr(self, "_mpt_shape", None) is None:
+            raise ValueError("call pt_create first")
+        return self._mpt_shape
+
     def pt_create(self, series, ntemps, nreplicas, adapt_iters, seed=0, temperatures=None):
         """One sampler run (nreplicas ladders of ntemps chains) per entry of `series` (indices into this context, any order,
         repeats allowed), all advancing in the same launches (carma_mpt_create)."""
@@ -869,78 +874,26 @@ class MultiContext:
         tt = as_f64(temperatures) if temperatures is not None else None
         if tt is not None and tt.size != int(ntemps):
             raise ValueError("temperatures must hold ntemps = %d values" % int(ntemps))
-        check(lib.carma_mpt_create(self._h, w.ctypes.data_as(_ip), w.size, int(ntemps), int(nreplicas),
-                                   ptr(tt) if tt is not None else None, int(adapt_iters), C.c_uint64(int(seed) & (2 ** 64 - 1))),
-              "carma_mpt_create")
+        check(lib.carma_mpt_create(self._h, _iptr(w), w.size, int(ntemps), int(nreplicas), _optr(tt), int(adapt_iters),
+                                   _seed(seed)), "carma_mpt_create")
         self._mpt_shape = (int(w.size), int(nreplicas), int(ntemps))
         self._mpt_series = w
 
-    def _mpt(self):
-        if getattr(self, "_mpt_shape", None) is None:
-            raise ValueError("call pt_create first")
-        return self._mpt_shape
-
     def pt_start(self, init=None):
         """Starting values (carma_mpt_start); init: None or [M, d], row j for every chain of run j where it is finite."""
-        M = self._mpt()[0]
-        a = self._init_rows(init, M)
-        check(lib.carma_mpt_start(self._h, ptr(a) if a is not None else None), "carma_mpt_start")
-
-    def pt_set_chains(self, theta, logpost=None):
-        M, R, T = self._mpt()
-        theta = as_f64(theta).reshape(M, R, T, self.d)
-        lp = as_f64(logpost).reshape(M, R, T) if logpost is not None else None
-        check(lib.carma_mpt_set_chains(self._h, ptr(theta), ptr(lp) if lp is not None else None), "carma_mpt_set_chains")
-
-    def pt_get_chains(self):
-        M, R, T = self._mpt()
-        theta, lp = np.empty((M, R, T, self.d)), np.empty((M, R, T))
-        check(lib.carma_mpt_get_chains(self._h, ptr(theta), ptr(lp)), "carma_mpt_get_chains")
-        return theta, lp
-
-    def pt_get_factor(self):
-        """The proposal factor of every chain, [M][R][T][d][d] (upper triangular)."""
-        M, R, T = self._mpt()
-        chol = np.empty((M, R, T, self.d, self.d))
-        check(lib.carma_mpt_get_factor(self._h, ptr(chol)), "carma_mpt_get_factor")
-        return chol
-
-    def pt_set_factor(self, chol):
-        M, R, T = self._mpt()
-        chol = as_f64(chol).reshape(M, R, T, self.d, self.d)
-        check(lib.carma_mpt_set_factor(self._h, ptr(chol)), "carma_mpt_set_factor")
-
-    def pt_iterate(self, niter, do_exchange=True):
-        check(lib.carma_mpt_iterate(self._h, int(niter), int(bool(do_exchange))), "carma_mpt_iterate")
-
-    def pt_sample(self, nsamples, thin=1):
-        """(samples [M][R][nsamples][d], logposts [M][R][nsamples]) of the coldest chains."""
-        M, R, T = self._mpt()
-        samples, logposts = np.empty((M, R, int(nsamples), self.d)), np.empty((M, R, int(nsamples)))
-        check(lib.carma_mpt_sample(self._h, int(nsamples), int(thin), ptr(samples), ptr(logposts)), "carma_mpt_sample")
-        return samples, logposts
-
-    def pt_stats(self, reset=False):
-        M, R, T = self._mpt()
-        acc, swp = np.empty((M, R, T)), np.empty((M, R, T))
-        check(lib.carma_mpt_stats(self._h, ptr(acc), ptr(swp), int(bool(reset))), "carma_mpt_stats")
-        return acc, swp
-
-    def pt_iterations_done(self):
-        return lib.carma_mpt_iterations_done(self._h)
+        a = self._init_rows(init, self._pt_lead()[0])
+        check(lib.carma_mpt_start(self._h, _optr(a)), "carma_mpt_start")
 
     def pt_logdensity(self, theta):
         """Log-densities of chain states [M][R][T][d], each on its run's series, through the sampler's own log-density kernel."""
-        M, R, T = self._mpt()
-        theta = as_f64(theta).reshape(M, R, T, self.d)
-        out = np.empty((M, R, T))
+        lead = self._pt_lead()
+        theta = as_f64(theta).reshape(lead + (self.d,))
+        out = np.empty(lead)
         check(lib.carma_mpt_logdensity(self._h, ptr(theta), ptr(out)), "carma_mpt_logdensity")
         return out
 
     def pt_kernel_name(self):
-        buf = C.create_string_buffer(128)
-        check(lib.carma_mpt_kernel_name(self._h, buf, 128), "carma_mpt_kernel_name")
-        return buf.value.decode()
+        return _kernel_name("carma_mpt_kernel_name", self._h)
 
     def pt_run(self, series, ntemps, nreplicas, sample_size, burnin, thin=1, init=None, seed=0):
         """Whole Sampler::Run of every run: (samples [M][R][S][d], logposts [M][R][S]) of the coldest chains (carma_mpt_run)."""
@@ -948,53 +901,32 @@ class MultiContext:
         a = self._init_rows(init, w.size)
         samples = np.empty((w.size, int(nreplicas), int(sample_size), self.d))
         logposts = np.empty((w.size, int(nreplicas), int(sample_size)))
-        check(lib.carma_mpt_run(self._h, w.ctypes.data_as(_ip), w.size, int(ntemps), int(nreplicas), int(sample_size), int(burnin),
-                                int(thin), ptr(a) if a is not None else None, C.c_uint64(int(seed) & (2 ** 64 - 1)), ptr(samples),
-                                ptr(logposts)), "carma_mpt_run")
+        check(lib.carma_mpt_run(self._h, _iptr(w), w.size, int(ntemps), int(nreplicas), int(sample_size), int(burnin), int(thin),
+                                _optr(a), _seed(seed), ptr(samples), ptr(logposts)), "carma_mpt_run")
         self._mpt_shape = (int(w.size), int(nreplicas), int(ntemps))
         self._mpt_series = w
         return samples, logposts
 
 
-class BandsContext:
+class BandsContext(_Handle):
     """Owns one carma_bands: K bands of ONE process resident in HBM, band b seen as a_b x(t - lag_b) + mu_b.
 
     bands: a list of (t, y, yerr), band 0 the reference band; lag_bounds: [K - 1] pairs (lo, hi), the box of every lag.  The
     parameter vector is Context's (d entries) followed by (lag_b, log a_b, mu_b) for b = 1 ... K - 1: dx entries."""
+    _destroy = "carma_bands_destroy"
 
     def __init__(self, bands, p, q=0, lag_bounds=None, max_stdev=None, device=None):
-        bands = list(bands)
-        if not bands:
-            raise ValueError("BandsContext needs at least one band")
-        ts, ys, es = [], [], []
-        for b, item in enumerate(bands):
-            if len(item) != 3:
-                raise ValueError("band %d: expected (t, y, yerr)" % b)
-            t, y, e = (as_f64(a).ravel() for a in item)
-            if not (t.size == y.size == e.size):
-                raise ValueError("band %d: time, y, yerr must have the same length" % b)
-            ts.append(t)
-            ys.append(y)
-            es.append(e)
-        K = len(bands)
+        ys, offsets, t_all, y_all, e_all = _concat_series(bands, "BandsContext", "band")
+        K = len(ys)
         lb = np.zeros((0, 2)) if lag_bounds is None else as_f64(lag_bounds).reshape(-1, 2)
         if lb.shape[0] != K - 1:
             raise ValueError("lag_bounds must hold one (lo, hi) pair for each of the %d bands after the first" % (K - 1))
-        lo, hi = as_f64(lb[:, 0]), as_f64(lb[:, 1])
+        lo, hi = (as_f64(lb[:, 0]), as_f64(lb[:, 1])) if K > 1 else (None, None)
         if max_stdev is None:
-            max_stdev = 10.0 * np.sqrt(np.var(ys[0], ddof=1)) if ys[0].size > 1 else 0.0
-        offsets = np.zeros(K + 1, dtype=np.int64)
-        offsets[1:] = np.cumsum([t.size for t in ts])
-        t_all, y_all, e_all = (as_f64(np.concatenate(a)) for a in (ts, ys, es))
-        self.device = default_device() if device is None else int(device)
-        self._h = lib.carma_bands_create(ptr(t_all), ptr(y_all), ptr(e_all), offsets.ctypes.data_as(C.POINTER(C.c_long)), K,
-                                         int(p), int(q), ptr(lo) if K > 1 else None, ptr(hi) if K > 1 else None,
-                                         float(max_stdev), self.device)
-        if not self._h:
-            msg = "carma_bands_create failed: " + last_error()
-            if "no HIP device" in msg:
-                raise CarmaDeviceError(msg)
-            raise ValueError(msg)
+            max_stdev = _default_max_stdev(ys[0])
+        self.device = _dev(device)
+        self._h = _created(lib.carma_bands_create(ptr(t_all), ptr(y_all), ptr(e_all), _lptr(offsets), K, int(p), int(q),
+                                                  _optr(lo), _optr(hi), float(max_stdev), self.device), "carma_bands_create")
         self.p, self.q = int(p), int(q)
         self.nbands = lib.carma_bands_nbands(self._h)
         self.dx = lib.carma_bands_dim(self._h)
@@ -1002,30 +934,13 @@ class BandsContext:
         self.n = np.array([lib.carma_bands_n(self._h, b) for b in range(self.nbands)], dtype=np.int64)
         self.lag_bounds = lb.copy()
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib.carma_bands_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        return self._h
-
     def prior(self):
         out = np.empty(3)
         check(lib.carma_bands_get_prior(self._h, ptr(out)), "carma_bands_get_prior")
         return tuple(out)
 
     def logdensity(self, thetas, ignore_prior=False):
-        thetas = as_f64(thetas)
-        one = thetas.ndim == 1
-        thetas = thetas.reshape(-1, self.dx)
+        thetas, one = _theta_rows(thetas, self.dx)
         out = np.empty(thetas.shape[0])
         check(lib.carma_bands_logdensity_batch(self._h, ptr(thetas), thetas.shape[0], int(bool(ignore_prior)), ptr(out)),
               "carma_bands_logdensity_batch")
@@ -1042,22 +957,13 @@ class BandsContext:
         """carma_bands_mle_batched: lock-step bounded L-BFGS from every row of x0 [B, dx] on -LogDensity.  lo / hi: [dx] (None
         or non-finite = unbounded; lags stay in their boxes).  fixed_lag [B, K - 1]: the lags of start i are held at
         fixed_lag[i] and come back unchanged in x.  Returns (x [B, dx], fun [B], nit [B], nfev [B], status [B])."""
-        x0 = np.ascontiguousarray(np.atleast_2d(np.asarray(x0, dtype=np.float64)))
-        B, dx = x0.shape
-        if dx != self.dx:
-            raise ValueError("x0 must be [B, %d]" % self.dx)
-        lo = np.full(dx, -np.inf) if lo is None else as_f64(lo).reshape(dx)
-        hi = np.full(dx, np.inf) if hi is None else as_f64(hi).reshape(dx)
-        fl = None
-        if fixed_lag is not None:
-            fl = as_f64(fixed_lag).reshape(B, self.nbands - 1)
-        x, fun = np.empty((B, dx)), np.empty(B)
-        nit, nfev, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
-        check(lib.carma_bands_mle_batched(self._h, ptr(x0), B, ptr(lo), ptr(hi), None if fl is None else ptr(fl), int(maxiter),
-                                          int(mem), float(ftol), float(gtol), float(fd_step), 1 if ignore_prior else 0, ptr(x),
-                                          ptr(fun), nit.ctypes.data_as(C.c_void_p), nfev.ctypes.data_as(C.c_void_p),
-                                          status.ctypes.data_as(C.c_void_p)), "carma_bands_mle_batched")
-        return x, fun, nit, nfev, status
+        x0, B = _mle_x0(x0, self.dx)
+        lo = np.full(self.dx, -np.inf) if lo is None else as_f64(lo).reshape(self.dx)
+        hi = np.full(self.dx, np.inf) if hi is None else as_f64(hi).reshape(self.dx)
+        fl = None if fixed_lag is None else as_f64(fixed_lag).reshape(B, self.nbands - 1)
+        out, tail = _mle_tail(B, self.dx, maxiter, mem, ftol, gtol, fd_step, ignore_prior)
+        check(lib.carma_bands_mle_batched(self._h, ptr(x0), B, ptr(lo), ptr(hi), _optr(fl), *tail), "carma_bands_mle_batched")
+        return out
 
 
 def kfilter_car1(time, y, yerr, sigsqr, omega, device=None):
@@ -1065,7 +971,7 @@ def kfilter_car1(time, y, yerr, sigsqr, omega, device=None):
     mean, var = np.empty(time.size), np.empty(time.size)
     nout = C.c_int(0)
     rc = lib.carma_kfilter_car1(ptr(time), ptr(y), ptr(yerr), time.size, float(sigsqr), float(omega), ptr(mean),
-                                ptr(var), C.byref(nout), default_device() if device is None else device)
+                                ptr(var), C.byref(nout), _dev(device))
     check(rc, "carma_kfilter_car1")
     return mean[:nout.value], var[:nout.value]
 
@@ -1074,15 +980,12 @@ def predict_carma(time, y, yerr, sigsqr, omega, ma, tpred, device=None):
     """KalmanFilterp::Predict for all `tpred` in one launch -> (mean[M], var[M])."""
     time, y, yerr = as_f64(time), as_f64(y), as_f64(yerr)
     omega = np.asarray(omega, dtype=complex)
-    om = as_f64(np.c_[omega.real, omega.imag])
-    ma = as_f64(ma)
+    om, ma = _reim(omega), as_f64(ma)
     tp = as_f64(np.atleast_1d(tpred))
     pm, pv = np.empty(tp.size), np.empty(tp.size)
     rc = lib.carma_predict_carma(ptr(time), ptr(y), ptr(yerr), time.size, omega.size, float(sigsqr), ptr(om), ptr(ma),
-                                 ma.size, ptr(tp), tp.size, ptr(pm), ptr(pv),
-                                 default_device() if device is None else device)
-    if rc == 1:
-        raise CarmaError("KalmanFilterp: singular eigenvector matrix (solve failed)")
+                                 ma.size, ptr(tp), tp.size, ptr(pm), ptr(pv), _dev(device))
+    _singular(rc, _SINGULAR)
     check(rc, "carma_predict_carma")
     return pm, pv
 
@@ -1092,8 +995,7 @@ def predict_car1(time, y, yerr, sigsqr, omega, tpred, device=None):
     tp = as_f64(np.atleast_1d(tpred))
     pm, pv = np.empty(tp.size), np.empty(tp.size)
     check(lib.carma_predict_car1(ptr(time), ptr(y), ptr(yerr), time.size, float(sigsqr), float(omega), ptr(tp), tp.size,
-                                 ptr(pm), ptr(pv), default_device() if device is None else device),
-          "carma_predict_car1")
+                                 ptr(pm), ptr(pv), _dev(device)), "carma_predict_car1")
     return pm, pv
 
 
@@ -1101,13 +1003,11 @@ def simulate_carma(time, sigsqr, omega, ma, npaths=1, seed=0, device=None):
     """carma_process for `npaths` paths in one launch -> [npaths][n] at the sorted times (carma_simulate_carma)."""
     time = as_f64(np.sort(np.asarray(time, dtype=float)))
     omega = np.asarray(omega, dtype=complex)
-    om = as_f64(np.c_[omega.real, omega.imag])
-    ma = as_f64(ma)
+    om, ma = _reim(omega), as_f64(ma)
     out = np.empty((int(npaths), time.size))
     rc = lib.carma_simulate_carma(ptr(time), time.size, omega.size, float(sigsqr), ptr(om), ptr(ma), ma.size, int(npaths),
-                                  C.c_uint64(int(seed) & (2 ** 64 - 1)), ptr(out), default_device() if device is None else device)
-    if rc == 1:
-        raise CarmaError("carma_process: repeated AR root (singular eigenvector matrix)")
+                                  _seed(seed), ptr(out), _dev(device))
+    _singular(rc, "carma_process: repeated AR root (singular eigenvector matrix)")
     check(rc, "carma_simulate_carma")
     return out
 
@@ -1115,9 +1015,8 @@ def simulate_carma(time, sigsqr, omega, ma, npaths=1, seed=0, device=None):
 def simulate_car1(time, sigsqr, omega, npaths=1, seed=0, device=None):
     time = as_f64(np.sort(np.asarray(time, dtype=float)))
     out = np.empty((int(npaths), time.size))
-    check(lib.carma_simulate_car1(ptr(time), time.size, float(sigsqr), float(omega), int(npaths),
-                                  C.c_uint64(int(seed) & (2 ** 64 - 1)), ptr(out), default_device() if device is None else device),
-          "carma_simulate_car1")
+    check(lib.carma_simulate_car1(ptr(time), time.size, float(sigsqr), float(omega), int(npaths), _seed(seed), ptr(out),
+                                  _dev(device)), "carma_simulate_car1")
     return out
 
 
@@ -1141,19 +1040,15 @@ def merged_times(time, tsim):
 def _simulate_cond(call, what, time, y, yerr, K, model_args, mu, tsim, seed, path0, return_parts, return_singular, device):
     time, y, yerr = as_f64(time), as_f64(y), as_f64(yerr)
     tp = as_f64(np.atleast_1d(tsim))
-    mu_ = None if mu is None else as_f64(np.atleast_1d(mu))
-    if mu_ is not None and mu_.size != K:
-        raise ValueError("%s: mu must have one entry per path" % what)
+    mu_ = _pack_mu(mu, K, what, "path")
     n, M = time.size, tp.size
     out = np.empty((K, max(M, 1)))
     unc = np.empty((K, n + M)) if return_parts else None
     noi = np.empty((K, n)) if return_parts else None
     sing = np.zeros(K, dtype=np.int32)
     nout = C.c_int(0)
-    rc = call(ptr(time), ptr(y), ptr(yerr), n, *model_args, ptr(mu_) if mu_ is not None else None, ptr(tp), M,
-              C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint(int(path0) & 0xffffffff), ptr(out),
-              ptr(unc) if return_parts else None, ptr(noi) if return_parts else None, sing.ctypes.data_as(_ip),
-              C.byref(nout), default_device() if device is None else device)
+    rc = call(ptr(time), ptr(y), ptr(yerr), n, *model_args, _optr(mu_), ptr(tp), M, _seed(seed),
+              C.c_uint(int(path0) & 0xffffffff), ptr(out), _optr(unc), _optr(noi), _iptr(sing), C.byref(nout), _dev(device))
     check(rc, what)
     sing = sing.astype(bool)
     if sing.any() and not return_singular:
@@ -1177,13 +1072,7 @@ def simulate_cond_carma(time, y, yerr, sigsqr, omega, ma, mu, tsim, seed=0, path
     unconditional paths on the merged grid and the unit normals of the measurement noise, from which simulate_carma and
     predict_carma rebuild every path.  return_singular: also the flags [K] of paths with a repeated AR root (otherwise such
     a path raises)."""
-    omega = np.atleast_2d(np.asarray(omega, dtype=complex))
-    K, p = omega.shape
-    om = as_f64(np.stack([omega.real, omega.imag], axis=-1))
-    ma = as_f64(np.atleast_2d(ma))
-    sig = as_f64(np.atleast_1d(sigsqr))
-    if ma.shape[0] != K or sig.size != K:
-        raise ValueError("simulate_cond_carma: sigsqr, omega and ma must describe the same number of paths")
+    K, p, sig, om, ma = _pack_models("simulate_cond_carma", "paths", sigsqr, omega, ma)
     return _simulate_cond(lib.carma_simulate_cond_carma, "carma_simulate_cond_carma", time, y, yerr, K,
                           (p, K, ptr(sig), ptr(om), ptr(ma), ma.shape[1]), mu, tsim, seed, path0, return_parts,
                           return_singular, device)
@@ -1192,11 +1081,7 @@ def simulate_cond_carma(time, y, yerr, sigsqr, omega, ma, mu, tsim, seed=0, path
 def simulate_cond_car1(time, y, yerr, sigsqr, omega, mu, tsim, seed=0, path0=0, return_parts=False, return_singular=False,
                        device=None):
     """simulate_cond_carma for CAR(1) models: sigsqr [K], omega [K] = 1 / tau (carma_simulate_cond_car1)."""
-    sig = as_f64(np.atleast_1d(sigsqr))
-    om = as_f64(np.atleast_1d(omega))
-    K = sig.size
-    if om.size != K:
-        raise ValueError("simulate_cond_car1: sigsqr and omega must describe the same number of paths")
+    K, _, sig, om, _ = _pack_models("simulate_cond_car1", "paths", sigsqr, omega)
     return _simulate_cond(lib.carma_simulate_cond_car1, "carma_simulate_cond_car1", time, y, yerr, K,
                           (K, ptr(sig), ptr(om)), mu, tsim, seed, path0, return_parts, return_singular, device)
 
@@ -1204,28 +1089,21 @@ def simulate_cond_car1(time, y, yerr, sigsqr, omega, mu, tsim, seed=0, path0=0, 
 def _smooth(call, what, time, y, yerr, K, model_args, mu, tout, band, return_singular, device):
     time, y, yerr = as_f64(time), as_f64(y), as_f64(yerr)
     tp = as_f64(np.atleast_1d(tout))
-    mu_ = None if mu is None else as_f64(np.atleast_1d(mu))
-    if mu_ is not None and mu_.size != K:
-        raise ValueError("%s: mu must have one entry per model" % what)
+    mu_ = _pack_mu(mu, K, what, "model")
     if band not in (False, True, "only"):
         raise ValueError("%s: band must be False, True or 'only'" % what)
     M = tp.size
-    samples = band != "only"
-    mean = np.empty((K, M)) if samples else None
-    var = np.empty((K, M)) if samples else None
-    bm = np.empty(M) if band else None
-    bv = np.empty(M) if band else None
+    mean, var = (np.empty((K, M)), np.empty((K, M))) if band != "only" else (None, None)
+    bm, bv = (np.empty(M), np.empty(M)) if band else (None, None)
     sing = np.zeros(K, dtype=np.int32)
     nout = C.c_int(0)
-    rc = call(ptr(time), ptr(y), ptr(yerr), time.size, *model_args, ptr(mu_) if mu_ is not None else None, ptr(tp), M,
-              ptr(mean) if samples else None, ptr(var) if samples else None, ptr(bm) if band else None,
-              ptr(bv) if band else None, sing.ctypes.data_as(_ip), C.byref(nout), default_device() if device is None else device)
+    rc = call(ptr(time), ptr(y), ptr(yerr), time.size, *model_args, _optr(mu_), ptr(tp), M, _optr(mean), _optr(var), _optr(bm),
+              _optr(bv), _iptr(sing), C.byref(nout), _dev(device))
     check(rc, what)
     sing = sing.astype(bool)
     if sing.any() and not return_singular:
         raise CarmaError("%s: repeated AR root (singular eigenvector matrix) in model %d" % (what, int(np.argmax(sing))))
-    res = ((mean, var) if samples else ()) + ((bm, bv) if band else ()) + ((sing,) if return_singular else ())
-    return res
+    return ((mean, var) if band != "only" else ()) + ((bm, bv) if band else ()) + ((sing,) if return_singular else ())
 
 
 def smooth_carma(time, y, yerr, sigsqr, omega, ma, mu, tout, band=False, return_singular=False, device=None):
@@ -1236,24 +1114,14 @@ def smooth_carma(time, y, yerr, sigsqr, omega, ma, mu, tout, band=False, return_
     singular; band="only": just those two (the K x M arrays never leave the device).  return_singular: also the flags [K] of
     models with a repeated AR root (otherwise such a model raises); a flagged model is left out of the band.  The variance is
     returned as computed (a difference: see include/carma_mi355.h), never clipped."""
-    omega = np.atleast_2d(np.asarray(omega, dtype=complex))
-    K, p = omega.shape
-    om = as_f64(np.stack([omega.real, omega.imag], axis=-1))
-    ma = as_f64(np.atleast_2d(ma))
-    sig = as_f64(np.atleast_1d(sigsqr))
-    if ma.shape[0] != K or sig.size != K:
-        raise ValueError("smooth_carma: sigsqr, omega and ma must describe the same number of models")
+    K, p, sig, om, ma = _pack_models("smooth_carma", "models", sigsqr, omega, ma)
     return _smooth(lib.carma_smooth_carma, "carma_smooth_carma", time, y, yerr, K, (p, K, ptr(sig), ptr(om), ptr(ma), ma.shape[1]),
                    mu, tout, band, return_singular, device)
 
 
 def smooth_car1(time, y, yerr, sigsqr, omega, mu, tout, band=False, return_singular=False, device=None):
     """smooth_carma for CAR(1) models: sigsqr [K], omega [K] = 1 / tau (carma_smooth_car1)."""
-    sig = as_f64(np.atleast_1d(sigsqr))
-    om = as_f64(np.atleast_1d(omega))
-    K = sig.size
-    if om.size != K:
-        raise ValueError("smooth_car1: sigsqr and omega must describe the same number of models")
+    K, _, sig, om, _ = _pack_models("smooth_car1", "models", sigsqr, omega)
     return _smooth(lib.carma_smooth_car1, "carma_smooth_car1", time, y, yerr, K, (K, ptr(sig), ptr(om)), mu, tout, band,
                    return_singular, device)
 
@@ -1263,14 +1131,14 @@ def sigma_noise_batch(ar_roots, ma_coefs, var, device=None):
     ma_coefs [ns, nma] lowest order first, var [ns] -> sigma [ns]."""
     roots = np.atleast_2d(np.asarray(ar_roots, dtype=complex))
     ns, p = roots.shape
-    om = as_f64(np.stack([roots.real, roots.imag], axis=-1))
+    om = _reim(roots)
     ma = as_f64(np.atleast_2d(np.asarray(ma_coefs, dtype=float)))
     v = as_f64(np.ravel(var))
     if ma.shape[0] != ns or v.size != ns:
         raise ValueError("sigma_noise_batch: one row of roots, MA coefficients and one variance per sample")
     out = np.empty(ns)
-    check(lib.carma_sigma_noise_batch(p, ma.shape[1], ptr(om), ptr(ma), ptr(v), ns, ptr(out),
-                                      default_device() if device is None else device), "carma_sigma_noise_batch")
+    check(lib.carma_sigma_noise_batch(p, ma.shape[1], ptr(om), ptr(ma), ptr(v), ns, ptr(out), _dev(device)),
+          "carma_sigma_noise_batch")
     return out
 
 
@@ -1289,8 +1157,7 @@ def psd_band(ar_coefs, ma_coefs, sigma, freq, percentiles, return_samples=False,
     band = np.empty((fr.size, pc.size))
     grid = np.empty((fr.size, ns)) if return_samples else None
     check(lib.carma_psd_band(ar.shape[1], ma.shape[1], ptr(ar), ptr(ma), ptr(sg), ns, ptr(fr), fr.size, ptr(pc), pc.size,
-                             ptr(band), ptr(grid) if return_samples else None, default_device() if device is None else device),
-          "carma_psd_band")
+                             ptr(band), _optr(grid), _dev(device)), "carma_psd_band")
     return (band, grid) if return_samples else band
 
 
@@ -1330,9 +1197,8 @@ def mpsd_band(ar_coefs, ma_coefs, sigma, sample_start, freq, percentiles, device
     if not 1 <= pc.size <= 4:
         raise ValueError("mpsd_band: 1 ... 4 percentiles, got %d" % pc.size)
     band = np.empty((S, fr.shape[1], pc.size))
-    check(lib.carma_mpsd_band(ar.shape[1], ma.shape[1], ptr(ar), ptr(ma), ptr(sg), st.ctypes.data_as(C.POINTER(C.c_long)), S,
-                              ptr(fr), fr.shape[1], ptr(pc), pc.size, ptr(band), default_device() if device is None else device),
-          "carma_mpsd_band")
+    check(lib.carma_mpsd_band(ar.shape[1], ma.shape[1], ptr(ar), ptr(ma), ptr(sg), _lptr(st), S, ptr(fr), fr.shape[1], ptr(pc),
+                              pc.size, ptr(band), _dev(device)), "carma_mpsd_band")
     return band
 
 
@@ -1364,7 +1230,7 @@ def chain_diag(x, rhat=True, device=None):
     if 0 in x.shape:
         raise ValueError("chain_diag: x has an empty axis: %r" % (x.shape,))
     G, R, L, d = x.shape
-    dev = default_device() if device is None else int(device)
+    dev = _dev(device)
     dmax = chain_diag_dmax()
     out = dict(tau=np.empty((G, R, d)), mean=np.empty((G, R, d)), sigma=np.empty((G, R, d)),
                status=np.empty((G, R, d), dtype=np.int32), rhat=np.empty((G, d)) if rhat else None)
@@ -1374,8 +1240,8 @@ def chain_diag(x, rhat=True, device=None):
         part = [np.empty((G, R, c1 - c0)) for _ in range(3)]
         st = np.empty((G, R, c1 - c0), dtype=np.int32)
         rh = np.empty((G, c1 - c0)) if rhat else None
-        check(lib.carma_chain_diag(ptr(xs), G, R, L, c1 - c0, ptr(part[0]), ptr(part[1]), ptr(part[2]), st.ctypes.data_as(_ip),
-                                   ptr(rh) if rhat else None, dev), "carma_chain_diag")
+        check(lib.carma_chain_diag(ptr(xs), G, R, L, c1 - c0, ptr(part[0]), ptr(part[1]), ptr(part[2]), _iptr(st), _optr(rh), dev),
+              "carma_chain_diag")
         for k, name in enumerate(("tau", "mean", "sigma")):
             out[name][..., c0:c1] = part[k]
         out["status"][..., c0:c1] = st
@@ -1384,26 +1250,11 @@ def chain_diag(x, rhat=True, device=None):
     return out
 
 
-def pt_sample_sharded(contexts, nsamples, thin=1, comm=None):
-    """carma_pt_sample_sharded: returns (samples[R][nsamples][d], logposts[R][nsamples]) on the process that owns
-    temperature 0, (None, None) elsewhere."""
-    arr = (C.c_void_p * len(contexts))(*[c.handle for c in contexts])
-    c0 = contexts[0]
-    owner = getattr(c0, "_pt_slot0", 0) == 0
-    R = c0._pt_shape[0]
-    samples = np.empty((R, int(nsamples), c0.d)) if owner else None
-    logposts = np.empty((R, int(nsamples))) if owner else None
-    check(lib.carma_pt_sample_sharded(arr, len(contexts), int(nsamples), int(thin), comm._h if comm is not None else None,
-                                      ptr(samples) if owner else None, ptr(logposts) if owner else None),
-          "carma_pt_sample_sharded")
-    return samples, logposts
-
-
 def normalize_roots(omega):
     """AR roots in any order -> conjugate pairs adjacent (negative imaginary part first), real roots last
     (carma_normalize_roots; host arithmetic, no device needed).  ValueError when the set is not closed under conjugation."""
     omega = np.asarray(omega, dtype=complex)
-    om = as_f64(np.c_[omega.real, omega.imag])
+    om = _reim(omega)
     out = np.empty_like(om)
     rc = lib.carma_normalize_roots(omega.size, ptr(om), ptr(out))
     if rc != CARMA_OK:

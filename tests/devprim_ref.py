@@ -51,7 +51,7 @@ def build_device(force=False, out=None):
 @functools.lru_cache(None)
 def device():
     # one process, ONE HIP runtime: the product's loader decides which copy the process maps (carma_pack_amd/_lib.py,
-    # _share_hip_runtime_with_torch); loading this harness first would map the system's and leave the product without devices
+    # _share_with_torch); loading this harness first would map the system's and leave the product without devices
     import carma_pack_amd._lib  # noqa: F401
     L = C.CDLL(build_device())
     L.devprim_math.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]
