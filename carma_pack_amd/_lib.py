@@ -71,6 +71,7 @@ SIGNATURES = {
     "carma_bands_logdensity_batch": (_I, [_V, _dp, _I, _I, _dp]),
     "carma_bands_logdensity_batch_dev": (_I, [_V, _V, _I, _I, _V, _V]),
     "carma_bands_mle_batched": (_I, [_V, _V, _I, _V, _V, _V] + _MLE_TAIL),
+    "carma_bands_smooth": (_I, [_V, _dp, _I, _I, _dp, _I, _dp, _dp, _dp, _dp, _ip]),
     "carma_kfilter_carma": (_I, _SERIES + [_I, _D, _dp, _dp, _I, _dp, _dp, _ip, _I]),
     "carma_kfilter_batch_carma": (_I, _SERIES + [_I, _I, _dp, _dp, _dp, _I, _dp, _dp, _dp, _ip, _ip, _I]),
     "carma_kfilter_car1": (_I, _SERIES + [_D, _D, _dp, _dp, _ip, _I]),
@@ -139,6 +140,8 @@ SIGNATURES = {
     "carma_comm_size": (_I, [_V]),
 }
 EXPORTS = list(SIGNATURES)
+# (the switches tune_reset puts back; carma_tune_set knows further keys, "MBAND_SMOOTH_CHUNK_ROWS" of BandsContext.smooth among
+# them, which a caller moves and resets itself)
 TUNE_SWITCHES = ("WIN_ROWS", "WIN2_EVALS", "PT_ROW_WIN", "CSIM_CHUNK_PATHS", "SMOOTH_CHUNK_MODELS")
 
 
@@ -964,6 +967,26 @@ class BandsContext(_Handle):
         out, tail = _mle_tail(B, self.dx, maxiter, mem, ftol, gtol, fd_step, ignore_prior)
         check(lib.carma_bands_mle_batched(self._h, ptr(x0), B, ptr(lo), ptr(hi), _optr(fl), *tail), "carma_bands_mle_batched")
         return out
+
+    def smooth(self, thetas, band, times, moments=False):
+        """carma_bands_smooth: mean and variance of a_b x(t - lag_b) + mu_b for b = `band` at the observer times `times` [M] (any
+        order, repeats allowed) given ALL data of all bands, under every row of thetas [B, dx] -- one row per lane, each lane on
+        the merge order ITS lags give, one forward and one backward pass.  The prior is never applied.
+        -> (mean [B, M], var [B, M], invalid [B]); a single vector [dx]: (mean [M], var [M], invalid bool).  moments=True:
+        (mean, var, band_mean [M], band_var [M], invalid), the moment-matched mixture over the rows that are not invalid.  An
+        invalid row (repeated AR root, non-finite lag, scale or offset) is NaN.  The variance is returned as computed."""
+        thetas, one = _theta_rows(thetas, self.dx)
+        tp = as_f64(np.atleast_1d(times)).ravel()
+        B, M = thetas.shape[0], tp.size
+        mean, var = np.empty((B, M)), np.empty((B, M))
+        bm, bv = (np.empty(M), np.empty(M)) if moments else (None, None)
+        inv = np.zeros(B, dtype=np.int32)
+        check(lib.carma_bands_smooth(self._h, ptr(thetas), B, int(band), ptr(tp), M, ptr(mean), ptr(var), _optr(bm), _optr(bv),
+                                     _iptr(inv)), "carma_bands_smooth")
+        inv = inv.astype(bool)
+        if one:
+            mean, var, inv = mean[0], var[0], bool(inv[0])
+        return (mean, var, bm, bv, inv) if moments else (mean, var, inv)
 
 
 def kfilter_car1(time, y, yerr, sigsqr, omega, device=None):

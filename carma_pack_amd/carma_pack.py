@@ -1280,12 +1280,33 @@ class CarmaBandsModel(object):
         best = fs.argmin(axis=1)
         return -fs[np.arange(L), best], xs.reshape(L, nt, self.dx)[np.arange(L), best]
 
+    def _smooth_rows(self, theta, time, band, moments):
+        out = self.context().smooth(theta, band, time, moments=moments)
+        inv = np.atleast_1d(out[-1])
+        if inv.any():
+            raise ValueError("CarmaBandsModel.smooth: row %d has a repeated AR root or a non-finite lag, scale or offset"
+                             % int(np.argmax(inv)))
+        return out[:-1]
+
+    def smooth(self, theta, time, band=0):
+        """The interpolated light curve of band `band`: mean and variance of a_b x(t - lag_b) + mu_b at the observer times `time`
+        [M] given all data of all bands (carma_bands_smooth; no prior, the semantics of loglik).  theta: [dx] -> (mean [M],
+        var [M]); [B, dx] -> ([B, M], [B, M]), every row on the merge order its own lags give, one launch.  ValueError on an
+        invalid row."""
+        return self._smooth_rows(theta, time, band, False)
+
+    def smooth_band(self, thetas, time, band=0):
+        """(band_mean [M], band_var [M]): the moment-matched equal-weight mixture of smooth() over the rows of thetas [B, dx] --
+        the optima of a lag_profile, of get_mle(return_all=True), or whatever vectors the caller holds.  Mixed on the device."""
+        return self._smooth_rows(thetas, time, band, True)[2:]
+
     def merged(self, theta):
         """The single light curve the bands make at theta, in the units of band 0: (time, y, ysig, band) with
         time = t - lag_b, y = (y_b - mu_b) / a_b + mu_0, ysig = ysig_b / a_b, sorted by time (equal times: the lower band
-        first), band = the band each datum came from.  Host numpy.  CarmaModel(time, y, ysig, p, q) on it gives the sampler, the
-        smoother and the power spectrum at the fitted lag -- but CarmaModel DROPS data with equal times (it keeps the first
-        of each), which the multi-band likelihood keeps."""
+        first), band = the band each datum came from.  Host numpy.  CarmaModel(time, y, ysig, p, q) on it gives the sampler and
+        the power spectrum at the fitted lag -- but CarmaModel DROPS data with equal times (it keeps the first of each), which
+        the multi-band likelihood keeps.  For the interpolated light curve of a band use smooth / smooth_band: they keep every
+        datum, work in that band's units and take many vectors with different lags per call."""
         theta = np.asarray(theta, dtype=float).reshape(self.dx)
         ts, ys, es, bs = [], [], [], []
         for b, (t, y, e) in enumerate(self.bands):

@@ -40,14 +40,20 @@ int device_cus();
 // and parsed by atol, but PT_ROW_ROT (hexadecimal) and PT_PLAIN (CARMA_PT_PLAIN: "first character is 1").
 // CARMA_TUNE_CSIM_CHUNK_PATHS: paths per chunk of the conditional simulation (carma_csim.hip; 0 or unset: as many as its scratch cap holds).
 // CARMA_TUNE_SMOOTH_CHUNK_MODELS: models per chunk of the one-pass smoother (carma_smooth.hip; 0 or unset: as many whole waves as its scratch cap holds).
+// CARMA_TUNE_MBAND_SMOOTH_CHUNK_ROWS: parameter vectors per chunk of carma_bands_smooth (carma_mband_smooth.hip; 0 or unset: as many whole waves as its scratch cap holds).
 enum {
     TUNE_WIN_ROWS = 0, TUNE_WIN2_EVALS, TUNE_PT_ROW_WIN, TUNE_CSIM_CHUNK_PATHS, TUNE_SMOOTH_CHUNK_MODELS,
     TUNE_P3L_ROWS, TUNE_LANE_MIN, TUNE_LPC_MIN, TUNE_LPC_MAX, TUNE_LPC_ROT, TUNE_CAR1_SCAN_MAX,
-    TUNE_PT_ROW_WGS_PER_CU, TUNE_PT_ROW_ROT, TUNE_PT_ROW_XCD_MAP, TUNE_PT_PLAIN, TUNE_COUNT
+    TUNE_PT_ROW_WGS_PER_CU, TUNE_PT_ROW_ROT, TUNE_PT_ROW_XCD_MAP, TUNE_PT_PLAIN, TUNE_MBAND_SMOOTH_CHUNK_ROWS, TUNE_COUNT
 };
 long tune_get(int which);                    // TUNE_UNSET or the override
-int tune_set(const char* name, long value);  // "WIN_ROWS" / "WIN2_EVALS" / "PT_ROW_WIN" / "CSIM_CHUNK_PATHS" / "SMOOTH_CHUNK_MODELS" (or the full CARMA_TUNE_ name); 0 or -1
+int tune_set(const char* name, long value);  // "WIN_ROWS" / "WIN2_EVALS" / "PT_ROW_WIN" / "CSIM_CHUNK_PATHS" / "SMOOTH_CHUNK_MODELS" / "MBAND_SMOOTH_CHUNK_ROWS" (or the full CARMA_TUNE_ name); 0 or -1
 ShapeSwitches shape_switches();              // the planners' switches (carma_shape_plan.h) as the table holds them now
+
+// k_smooth_band (carma_smooth.hip) on `st`: the moment-matched equal-weight mixture over the rows of mean / var = [K][M] whose flag
+// in singular = [K] is 0 -> bmean / bvar = [M]
+hipError_t launch_smooth_band(const double* mean, const double* var, const int* singular, int K, int M, double* bmean, double* bvar,
+                              hipStream_t st);
 
 // repeated_dt: a good part of the series' time steps equal their predecessor (regular cadence): the throughput kernels
 // then run the variant that re-uses the transition factors of such steps (carma_core.h, RhoInline DTC)

@@ -19,6 +19,7 @@
 #include "carma_mband.h"
 #include "carma_host.h"
 #include "carma_mband_plan.h"
+#include "carma_mband_ctx.h"
 
 namespace carma {
 
@@ -76,18 +77,6 @@ static hipError_t launch_logdens_mband(int p, const double* theta, int B, int dx
     return for_order(p, hipErrorInvalidValue, go);
 }
 
-// Multi-band context: the records of all bands in one buffer, a sentinel behind each band
-struct Bctx {
-    int device = 0;
-    int p = 0, q = 0, d = 0, K = 0, dx = 0, N = 0;
-    std::vector<int> n, boff;         // [K] data per band, [K + 1] first record of a band (mband_pack)
-    std::vector<double> lagbox;       // [K - 1][2]
-    Prior pr{};
-    DevMem d_rec, d_boff, d_lagbox;
-    DevMem d_theta, d_out;            // per-call buffers of the host-pointer entry point, grown on demand
-    hipStream_t stream = nullptr;
-};
-
 }  // namespace carma
 
 using namespace carma;
@@ -134,6 +123,8 @@ carma_bands* carma_bands_create(const double* time, const double* y, const doubl
     }
     std::vector<double> rec;
     mband_pack(ts, ys, es, rec, c->boff);
+    c->t0 = ts[0][0];                                         // (as mband_pack takes it: requested times get the same shift)
+    for (int b = 1; b < K; b++) c->t0 = std::min(c->t0, ts[b][0]);
     if (select_device(device) != CARMA_OK) {
         delete c;
         return nullptr;

@@ -99,6 +99,14 @@ __global__ __launch_bounds__(64) void k_smooth_band(const double* __restrict__ m
     bvar[i] = sv / (double)kk;
 }
 
+// (declared in carma_launch.h: carma_bands_smooth mixes its rows with the same kernel)
+hipError_t launch_smooth_band(const double* mean, const double* var, const int* singular, int K, int M, double* bmean, double* bvar,
+                              hipStream_t st)
+{
+    hipLaunchKernelGGL(k_smooth_band, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, st, mean, var, singular, K, M, bmean, bvar);
+    return hipGetLastError();
+}
+
 struct SmoothArgs {
     const double* par;
     int kc;
@@ -192,9 +200,7 @@ static int smooth_host(const char* who, const double* time, const double* y, con
         e = launch_smooth(p, a);
     }
     if (e == hipSuccess && bmean) {
-        hipLaunchKernelGGL(k_smooth_band, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, nullptr, d_mean, d_var, d_sing, K, M,
-                           d_band, d_band + M);
-        e = hipGetLastError();
+        e = launch_smooth_band(d_mean, d_var, d_sing, K, M, d_band, d_band + M, nullptr);
     }
     // (blocking copies on the null stream: they wait for the launches above)
     if (e == hipSuccess && mean) e = hipMemcpy(mean, d_mean, sizeof(double) * (size_t)K * M, hipMemcpyDeviceToHost);

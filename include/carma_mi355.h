@@ -109,7 +109,8 @@ int carma_logdensity_kernel_name(const carma_ctx* h, int B, char* buf, int len);
  * "PT_ROW_WIN" -- the CARMA_TUNE_* environment variables of the same names give their initial values, read once when the first
  * launch asks; afterwards only this call moves them (process-wide, thread-safe).  CARMA_EINVAL for an unknown name.
  * "CSIM_CHUNK_PATHS": paths per chunk of carma_simulate_cond_* (0: as many as its scratch cap holds; results do not depend on it).
- * "SMOOTH_CHUNK_MODELS": models per chunk of carma_smooth_* (0: as many whole waves as its scratch cap holds; results do not depend on it). */
+ * "SMOOTH_CHUNK_MODELS": models per chunk of carma_smooth_* (0: as many whole waves as its scratch cap holds; results do not depend on it).
+ * "MBAND_SMOOTH_CHUNK_ROWS": parameter vectors per chunk of carma_bands_smooth (0: as many whole waves as its scratch cap holds; results do not depend on it). */
 int carma_tune_set(const char* name, long value);
 
 /*
@@ -201,6 +202,20 @@ int carma_mle_batched_ms(carma_mctx* h, const double* x0 /* [B][d] */, const int
  *   unbounded; the lag entries are cut to the lag boxes of the handle).  fixed_lag = [B][nbands - 1] or NULL: with it the
  *   optimiser runs on the dx - (nbands - 1) other variables and every evaluation of start i is made at the lags fixed_lag[i]
  *   (the lag entries of x0, lo and hi are not read); x = [B][dx] carries those lags unchanged.  status as carma_mle_batched.
+ * carma_bands_smooth: the interpolated light curve of band `band` with its variance under B parameter vectors at once: mean and
+ *   variance of a_b x(tout - lag_b) + mu_b (noise-free, in that band's units) given ALL the data of all bands, theta = [B][dx],
+ *   tout = [M] observer times of that band in any order, repeats allowed.  One vector per lane: each lane merges the bands and
+ *   the requested times in the order ITS lags give and walks the N + M points once forward (k_smooth_mband_fwd) and once backward
+ *   (k_smooth_mband_bwd; modified Bryson-Frazier), so vectors with different lags share a call -- the optima of a lag profile,
+ *   of many starts.  All data count: equal shifted times are legal and none is dropped; a requested time equal to a datum's
+ *   shifted time comes behind it.  The prior is never applied (neither the CARMA bounds nor the lag boxes, also for p = 1).
+ *   mean / var = [B][M] in the order of tout, or both NULL; band_mean / band_var = [M], the moment-matched equal-weight mixture
+ *   over the rows that are not invalid (as carma_smooth_carma), or both NULL; one pair at least.  invalid = [B] or NULL: 1 where a
+ *   row has a repeated AR root or a non-finite lag, scale or offset; its mean / var are NaN and it is left out of the mixture.
+ *   The variance is returned as computed, never clipped (see carma_smooth_carma).  Returns CARMA_OK; 1 if a row was invalid and
+ *   `invalid` is NULL; CARMA_EINVAL before any device work for a null handle, B < 1, M < 1, band outside [0, nbands), a
+ *   mismatched pair or a tout that is not finite.  Scratch: 8 (2 p + p / 2 + 5) (N + M) bytes a row, capped at 256 MiB a chunk of
+ *   rows ("MBAND_SMOOTH_CHUNK_ROWS" of carma_tune_set forces a chunk size; a row's result does not depend on it).
  */
 #define CARMA_KBANDS_MAX 8
 typedef struct carma_bands carma_bands;
@@ -219,6 +234,11 @@ int carma_bands_mle_batched(carma_bands* h, const double* x0 /* [B][dx] */, int 
                             const double* hi /* [dx] */, const double* fixed_lag /* [B][K-1] or NULL */, int maxiter, int mem,
                             double ftol, double gtol, double fd_step, int ignore_prior, double* x, double* fun, int* nit,
                             int* nfev, int* status);
+int carma_bands_smooth(carma_bands* h, const double* theta /* [B][dx] */, int B, int band,
+                       const double* tout /* [M], observer times of that band, any order, repeats allowed */, int M,
+                       double* mean /* [B][M] or NULL */, double* var /* [B][M] or NULL */,
+                       double* band_mean /* [M] or NULL */, double* band_var /* [M] or NULL */,
+                       int* invalid /* [B] or NULL */);
 
 /*
  * The parallel-tempering sampler over MANY SERIES (the carma_pt_* set on a carma_mctx).  A RUN is one sampler -- nreplicas
