@@ -148,6 +148,7 @@ sigma_noise_batch = _lib.sigma_noise_batch
 psd_band = _lib.psd_band
 mpsd_band = _lib.mpsd_band
 chain_diag = _lib.chain_diag
+chain_diag_dmax = _lib.chain_diag_dmax
 simulate_cond_carma = _lib.simulate_cond_carma
 simulate_cond_car1 = _lib.simulate_cond_car1
 smooth_carma = _lib.smooth_carma

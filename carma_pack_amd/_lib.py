@@ -72,6 +72,20 @@ SIGNATURES = {
     "carma_bands_logdensity_batch_dev": (_I, [_V, _V, _I, _I, _V, _V]),
     "carma_bands_mle_batched": (_I, [_V, _V, _I, _V, _V, _V] + _MLE_TAIL),
     "carma_bands_smooth": (_I, [_V, _dp, _I, _I, _dp, _I, _dp, _dp, _dp, _dp, _ip]),
+    "carma_bands_pt_default_box": (_I, [_V, _dp, _dp]),
+    "carma_bands_pt_create": (_I, [_V, _I, _I, _dp, _I, _U64, _dp, _dp]),
+    "carma_bands_pt_start": (_I, [_V, _dp]),
+    "carma_bands_pt_set_chains": (_I, [_V, _dp, _dp]),
+    "carma_bands_pt_get_chains": (_I, [_V, _dp, _dp]),
+    "carma_bands_pt_get_factor": (_I, [_V, _dp]),
+    "carma_bands_pt_set_factor": (_I, [_V, _dp]),
+    "carma_bands_pt_iterate": (_I, [_V, _L, _I]),
+    "carma_bands_pt_sample": (_I, [_V, _I, _I, _dp, _dp]),
+    "carma_bands_pt_stats": (_I, [_V, _dp, _dp, _I]),
+    "carma_bands_pt_iterations_done": (_L, [_V]),
+    "carma_bands_pt_logdensity": (_I, [_V, _dp, _dp]),
+    "carma_bands_pt_kernel_name": (_I, [_V, _S, _I]),
+    "carma_bands_pt_run": (_I, [_V, _I, _I, _I, _I, _I, _dp, _U64, _dp, _dp, _dp, _dp]),
     "carma_kfilter_carma": (_I, _SERIES + [_I, _D, _dp, _dp, _I, _dp, _dp, _ip, _I]),
     "carma_kfilter_batch_carma": (_I, _SERIES + [_I, _I, _dp, _dp, _dp, _I, _dp, _dp, _dp, _ip, _ip, _I]),
     "carma_kfilter_car1": (_I, _SERIES + [_D, _D, _dp, _dp, _ip, _I]),
@@ -418,32 +432,37 @@ class _Handle:
 
 class _Sampler:
     """The parallel-tempering calls Context (carma_pt_*, chains [R][T]) and MultiContext (carma_mpt_*, chains [M][R][T]) share:
-    `_pt` is the prefix of the C functions, `_pt_lead()` the leading shape (..., R, T) that pt_create / pt_run left."""
+    `_pt` is the prefix of the C functions, `_pt_lead()` the leading shape (..., R, T) that pt_create / pt_run left.  BandsContext (carma_bands_pt_*, chains [R][T] of dx
+    entries) takes them too."""
     _pt = None
+
+    def _pt_dim(self):
+        """Entries of a chain's vector: d of a series; a context whose chains carry more (BandsContext: dx) says so here."""
+        return self.d
 
     def _pt_call(self, name, *args):
         check(getattr(lib, self._pt + name)(self._h, *args), self._pt + name)
 
     def pt_set_chains(self, theta, logpost=None):
         lead = self._pt_lead()
-        theta = as_f64(theta).reshape(lead + (self.d,))
+        theta = as_f64(theta).reshape(lead + (self._pt_dim(),))
         lp = as_f64(logpost).reshape(lead) if logpost is not None else None
         self._pt_call("set_chains", ptr(theta), _optr(lp))
 
     def pt_get_chains(self):
         lead = self._pt_lead()
-        theta, lp = np.empty(lead + (self.d,)), np.empty(lead)
+        theta, lp = np.empty(lead + (self._pt_dim(),)), np.empty(lead)
         self._pt_call("get_chains", ptr(theta), ptr(lp))
         return theta, lp
 
     def pt_get_factor(self):
         """chol_factor_ of every chain, [...][R][T][d][d] (upper triangular; src/steps.cpp:32)."""
-        chol = np.empty(self._pt_lead() + (self.d, self.d))
+        chol = np.empty(self._pt_lead() + (self._pt_dim(), self._pt_dim()))
         self._pt_call("get_factor", ptr(chol))
         return chol
 
     def pt_set_factor(self, chol):
-        chol = as_f64(chol).reshape(self._pt_lead() + (self.d, self.d))
+        chol = as_f64(chol).reshape(self._pt_lead() + (self._pt_dim(), self._pt_dim()))
         self._pt_call("set_factor", ptr(chol))
 
     def pt_iterate(self, niter, do_exchange=True):
@@ -452,7 +471,7 @@ class _Sampler:
     def pt_sample(self, nsamples, thin=1):
         """(samples [...][R][nsamples][d], logposts [...][R][nsamples]) of the coldest chains."""
         head = self._pt_lead()[:-1] + (int(nsamples),)
-        samples, logposts = np.empty(head + (self.d,)), np.empty(head)
+        samples, logposts = np.empty(head + (self._pt_dim(),)), np.empty(head)
         self._pt_call("sample", int(nsamples), int(thin), ptr(samples), ptr(logposts))
         return samples, logposts
 
@@ -911,12 +930,81 @@ class MultiContext(_Handle, _Sampler):
         return samples, logposts
 
 
-class BandsContext(_Handle):
+class BandsContext(_Handle, _Sampler):
     """Owns one carma_bands: K bands of ONE process resident in HBM, band b seen as a_b x(t - lag_b) + mu_b.
 
     bands: a list of (t, y, yerr), band 0 the reference band; lag_bounds: [K - 1] pairs (lo, hi), the box of every lag.  The
-    parameter vector is Context's (d entries) followed by (lag_b, log a_b, mu_b) for b = 1 ... K - 1: dx entries."""
-    _destroy = "carma_bands_destroy"
+    parameter vector is Context's (d entries) followed by (lag_b, log a_b, mu_b) for b = 1 ... K - 1: dx entries.
+    The sampler (carma_bands_pt_*): pt_create / pt_start, then _Sampler's calls on chains [R][T] of dx entries."""
+    _destroy, _pt = "carma_bands_destroy", "carma_bands_pt_"
+
+    def _pt_dim(self):
+        return self.dx
+
+    def _pt_lead(self):
+        if getattr(self, "_bpt_shape", None) is None:
+            raise ValueError("call pt_create first")
+        return self._bpt_shape
+
+    def _band_box(self, band_box):
+        """None, or (lo, hi) [K - 1, 2] each, columns (log a_b, mu_b) -> the two arrays the C calls take (or None, None)."""
+        if band_box is None:
+            return None, None
+        lo, hi = (as_f64(v).reshape(self.nbands - 1, 2) for v in band_box)
+        return lo, hi
+
+    def pt_default_box(self):
+        """(lo, hi) [K - 1, 2] each: the default box of (log a_b, mu_b) (carma_bands_pt_default_box)."""
+        lo, hi = np.empty((self.nbands - 1, 2)), np.empty((self.nbands - 1, 2))
+        check(lib.carma_bands_pt_default_box(self._h, ptr(lo), ptr(hi)), "carma_bands_pt_default_box")
+        return lo, hi
+
+    def pt_create(self, ntemps, nreplicas, adapt_iters, seed=0, temperatures=None, band_box=None):
+        """nreplicas ladders of ntemps chains on the extended vector (carma_bands_pt_create).  band_box: None (no box) or (lo, hi),
+        [K - 1, 2] each for (log a_b, mu_b): outside it a chain's log-density is -inf."""
+        tt = as_f64(temperatures) if temperatures is not None else None
+        if tt is not None and tt.size != int(ntemps):
+            raise ValueError("temperatures must hold ntemps = %d values" % int(ntemps))
+        lo, hi = self._band_box(band_box)
+        self._bpt_shape = None
+        check(lib.carma_bands_pt_create(self._h, int(ntemps), int(nreplicas), _optr(tt), int(adapt_iters), _seed(seed), _optr(lo),
+                                        _optr(hi)), "carma_bands_pt_create")
+        self._bpt_shape = (int(nreplicas), int(ntemps))
+
+    def _init_row(self, init):
+        if init is None:
+            return None
+        a = as_f64(init)
+        if a.shape != (self.dx,):
+            raise ValueError("init must be [%d], got %r" % (self.dx, a.shape))
+        return a
+
+    def pt_start(self, init=None):
+        """Starting values (carma_bands_pt_start); init: None or [dx], every chain's value where its log-density is finite."""
+        check(lib.carma_bands_pt_start(self._h, _optr(self._init_row(init))), "carma_bands_pt_start")
+
+    def pt_logdensity(self, theta):
+        """Log-densities of chain states [R][T][dx] through the sampler's own log-density kernel (with the band box)."""
+        lead = self._pt_lead()
+        theta = as_f64(theta).reshape(lead + (self.dx,))
+        out = np.empty(lead)
+        check(lib.carma_bands_pt_logdensity(self._h, ptr(theta), ptr(out)), "carma_bands_pt_logdensity")
+        return out
+
+    def pt_kernel_name(self):
+        return _kernel_name("carma_bands_pt_kernel_name", self._h)
+
+    def pt_run(self, ntemps, nreplicas, sample_size, burnin, thin=1, init=None, seed=0, band_box=None):
+        """Whole Sampler::Run: (samples [R][S][dx], logposts [R][S]) of the coldest chains (carma_bands_pt_run)."""
+        a = self._init_row(init)
+        lo, hi = self._band_box(band_box)
+        samples = np.empty((int(nreplicas), int(sample_size), self.dx))
+        logposts = np.empty((int(nreplicas), int(sample_size)))
+        self._bpt_shape = None
+        check(lib.carma_bands_pt_run(self._h, int(ntemps), int(nreplicas), int(sample_size), int(burnin), int(thin), _optr(a),
+                                     _seed(seed), _optr(lo), _optr(hi), ptr(samples), ptr(logposts)), "carma_bands_pt_run")
+        self._bpt_shape = (int(nreplicas), int(ntemps))
+        return samples, logposts
 
     def __init__(self, bands, p, q=0, lag_bounds=None, max_stdev=None, device=None):
         ys, offsets, t_all, y_all, e_all = _concat_series(bands, "BandsContext", "band")

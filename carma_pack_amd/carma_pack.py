@@ -15,7 +15,7 @@ from scipy.optimize import minimize
 
 from . import _carmcmc as carmcmcLib
 
-__all__ = ["CarmaModel", "CarmaModelSet", "CarmaBandsModel", "CarmaSample", "Car1Sample", "MCMCSample", "get_ar_roots", "power_spectrum",
+__all__ = ["CarmaModel", "CarmaModelSet", "CarmaBandsModel", "CarmaBandsSample", "CarmaSample", "Car1Sample", "MCMCSample", "get_ar_roots", "power_spectrum",
            "carma_variance", "car1_process", "carma_process", "carma_process_batch", "car1_process_batch", "mle_to_model"]
 
 
@@ -1201,6 +1201,7 @@ class CarmaBandsModel(object):
         if self.lag_bounds.shape[0] != self.K - 1:
             raise ValueError("lag_bounds must hold one (lo, hi) pair for each band after the first")
         self._ctx = None
+        self.mcmc_sample = None
 
     def context(self):
         """The BandsContext of the model (created once; max_stdev as the samplers that provide get_mle's starts set it)."""
@@ -1300,6 +1301,59 @@ class CarmaBandsModel(object):
         the optima of a lag_profile, of get_mle(return_all=True), or whatever vectors the caller holds.  Mixed on the device."""
         return self._smooth_rows(thetas, time, band, True)[2:]
 
+    def _band_box(self, scale_bounds, offset_bounds):
+        """The (K - 1, 2) arrays run_mcmc was given, checked: scale_bounds = (lo, hi) of a_b > 0, offset_bounds = (lo, hi) of
+        mu_b, one pair per band after the first; None stays None (the default box)."""
+        out = []
+        for name, v in (("scale_bounds", scale_bounds), ("offset_bounds", offset_bounds)):
+            if v is None:
+                out.append(None)
+                continue
+            a = np.asarray(v, dtype=float)
+            if a.shape != (self.K - 1, 2):
+                raise ValueError("%s must hold one (lo, hi) pair for each of the %d bands after the first, got shape %r"
+                                 % (name, self.K - 1, a.shape))
+            if not np.all(a[:, 0] <= a[:, 1]) or (name == "scale_bounds" and not np.all(a[:, 0] > 0)):
+                raise ValueError("%s: need %slo <= hi in every pair" % (name, "0 < " if name == "scale_bounds" else ""))
+            out.append(a)
+        return out
+
+    def run_mcmc(self, nsamples, nburnin=None, ntemperatures=None, nthin=1, init=None, nreplicas=1, seed=None, scale_bounds=None,
+                 offset_bounds=None):
+        """Parallel-tempered RAM sampler on the extended vector (carma_bands_pt_run): the posterior of the lags, scales and
+        offsets together with the CARMA part.  Defaults as CarmaModel.run_mcmc: nburnin = nsamples / 2, ntemperatures =
+        max(10, p + q); nreplicas independent ladders advance in the same launches, one chain per lane.  init: None or [dx], the
+        starting value of every chain where its log-posterior is finite.
+        logpost is flat in log a_b and mu_b and tends to a constant as a_b -> 0, so the sampler keeps both in a box:
+        scale_bounds = [K - 1] pairs (lo, hi) of a_b, offset_bounds = [K - 1] pairs of mu_b; None: a_b within a factor 1000 of
+        std y_b / std y_0, mu_b within the range of y_b widened by its span on either side.
+        Returns a CarmaBandsSample (all replicas' cold-chain draws), kept as mcmc_sample."""
+        if self.K < 1:
+            raise ValueError("run_mcmc needs at least one band")
+        if int(nsamples) < 1:
+            raise ValueError("nsamples must be at least 1")
+        if int(nthin) < 1 or int(nreplicas) < 1:
+            raise ValueError("nthin and nreplicas must be at least 1")
+        if init is not None:
+            init = np.asarray(init, dtype=float)
+            if init.shape != (self.dx,):
+                raise ValueError("init must be [%d], got %r" % (self.dx, init.shape))
+        sb, ob = self._band_box(scale_bounds, offset_bounds)
+        if ntemperatures is None:
+            ntemperatures = max(10, self.p + self.q)
+        if nburnin is None:
+            nburnin = int(nsamples) // 2
+        ctx = self.context()
+        lo, hi = ctx.pt_default_box()
+        if sb is not None:
+            lo[:, 0], hi[:, 0] = np.log(sb[:, 0]), np.log(sb[:, 1])
+        if ob is not None:
+            lo[:, 1], hi[:, 1] = ob[:, 0], ob[:, 1]
+        samples, logposts = ctx.pt_run(int(ntemperatures), int(nreplicas), int(nsamples), int(nburnin), int(nthin), init,
+                                       carmcmcLib._seed(seed), band_box=(lo, hi))
+        self.mcmc_sample = CarmaBandsSample(self, samples, logposts)
+        return self.mcmc_sample
+
     def merged(self, theta):
         """The single light curve the bands make at theta, in the units of band 0: (time, y, ysig, band) with
         time = t - lag_b, y = (y_b - mu_b) / a_b + mu_0, ysig = ysig_b / a_b, sorted by time (equal times: the lower band
@@ -1322,3 +1376,82 @@ class CarmaBandsModel(object):
         t, y, e, band = (np.concatenate(a) for a in (ts, ys, es, bs))
         order = np.lexsort((band, t))
         return t[order], y[order], e[order], band[order]
+
+
+class CarmaBandsSample(MCMCSample):
+    """The draws of CarmaBandsModel.run_mcmc: every replica's cold chain, replica after replica, n = R x nsamples rows.
+
+    `_samples` holds the entries CarmaSample derives from the CARMA part (the first d columns: var, measerr_scale, mu,
+    quad_coefs, ar_roots, psd_centroid, psd_width, ar_coefs, ma_coefs, sigma), the band terms lag, log_scale, scale = a_b and
+    offset = mu_b ([n, K - 1] each), logpost, and loglik (the log-density with the prior bounds ignored, one batched launch).
+    samples: [R, nsamples, dx]; logposts: [R, nsamples].  loglik [n] and sigma [n] may be given by whoever holds them already;
+    without them they come from the device.  There is no predict or simulate: smooth_band interpolates a band."""
+
+    def __init__(self, model, samples, logposts, loglik=None, sigma=None):
+        samples, logposts = np.asarray(samples, dtype=float), np.asarray(logposts, dtype=float)
+        if samples.ndim != 3 or samples.shape[2] != model.dx or logposts.shape != samples.shape[:2]:
+            raise ValueError("CarmaBandsSample: samples must be [R, n, %d] and logposts [R, n], got %r and %r"
+                             % (model.dx, samples.shape, logposts.shape))
+        self.model, self.p, self.q, self.K = model, model.p, model.q, model.K
+        self.time, self.y, self.ysig = model.bands[0]
+        self._all = samples, logposts
+        trace = samples.reshape(-1, model.dx)
+        self.trace = trace
+        d = model.d
+        super(CarmaBandsSample, self).__init__(logpost=logposts.ravel())
+        # the CARMA part, by CarmaSample's own steps on the first d columns
+        CarmaSample.generate_from_trace(self, trace[:, :d])
+        CarmaSample._ar_roots(self)
+        CarmaSample._ar_coefs(self)
+        self._samples["ma_coefs"] = CarmaSample._ma_coefs_of(trace[:, :d], self.p, self.q)
+        if sigma is None:
+            sigma = carmcmcLib.sigma_noise_batch(self._samples["ar_roots"], self._samples["ma_coefs"], self._samples["var"])
+        self._samples["sigma"] = np.asarray(sigma, dtype=float).reshape(trace.shape[0])
+        cols = d + 3 * np.arange(model.K - 1)
+        self._samples["lag"] = trace[:, cols]
+        self._samples["log_scale"] = trace[:, cols + 1]
+        self._samples["scale"] = np.exp(trace[:, cols + 1])
+        self._samples["offset"] = trace[:, cols + 2]
+        if loglik is None:
+            loglik = model.context().logdensity(trace, ignore_prior=True)
+        self._samples["loglik"] = np.asarray(loglik, dtype=float).reshape(trace.shape[0])
+        self.parameters = list(self._samples.keys())
+        self.newaxis()
+
+    def lag_summary(self, percentile=68.0):
+        """(median, lower, upper) of every band's lag, [K - 1] each: the central `percentile` per cent interval."""
+        lower = (100.0 - percentile) / 2.0
+        med, lo, hi = np.percentile(self._samples["lag"], [50.0, lower, 100.0 - lower], axis=0)
+        return med, lo, hi
+
+    def smooth_band(self, time, band=0, nsamples=None, seed=None):
+        """(band_mean [M], band_var [M]) of band `band` at the observer times `time`: CarmaBandsModel.smooth_band over a subsample
+        of the draws (all of them by default; nsamples: evenly spaced ones, or drawn without replacement with a seed), so the
+        band is marginalised over the posterior of the lags as well."""
+        n = self.trace.shape[0]
+        if seed is not None and nsamples is not None and nsamples < n:
+            index = np.sort(np.random.default_rng(seed).choice(n, int(nsamples), replace=False))
+        else:
+            index = CarmaSample._subsample(nsamples, n)
+        return self.model.smooth_band(self.trace[index], time, band=band)
+
+    def diagnostics(self):
+        """As CarmaSample.diagnostics, over all replicas and the dx columns of the extended vector followed by logpost: tau
+        [R, dx + 1], ess [dx + 1], rhat [dx + 1], status, mean, sigma [R, dx + 1] (carma_chain_diag, in column groups of at most
+        carma_chain_diag_dmax() columns)."""
+        samples, logposts = self._all
+        dmax = carmcmcLib.chain_diag_dmax()
+        parts = [carmcmcLib.chain_diag(np.ascontiguousarray(samples[None, :, :, c:c + dmax]))
+                 for c in range(0, samples.shape[2], dmax)]
+        par = {k: np.concatenate([p[k] for p in parts], axis=-1) for k in ("tau", "mean", "sigma", "status", "rhat")}
+        out = _diagnostics_of(par, carmcmcLib.chain_diag(logposts[None, :, :, None]))
+        out = {k: v[0] for k, v in out.items()}
+        out["ess"] = _ess_of(out["tau"], out["status"], samples.shape[1])
+        return out
+
+    # the power spectrum of the CARMA part: CarmaSample's steps on the entries above (carma_psd_band)
+    _subsample = staticmethod(CarmaSample._subsample)
+    _psd_frequencies = CarmaSample._psd_frequencies
+    _psd_inputs = CarmaSample._psd_inputs
+    _psd_credint = CarmaSample._psd_credint
+    power_spectrum_band = CarmaSample.power_spectrum_band

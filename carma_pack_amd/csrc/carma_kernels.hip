@@ -715,7 +715,7 @@ static const TuneEntry TUNE_TAB[TUNE_COUNT] = {
     {"CARMA_TUNE_LANE_MIN", 11, TP_DEC},          {"CARMA_TUNE_LPC_MIN", 11, TP_DEC},             {"CARMA_TUNE_LPC_MAX", 11, TP_DEC},
     {"CARMA_TUNE_LPC_ROT", 11, TP_DEC},           {"CARMA_TUNE_CAR1_SCAN_MAX", 11, TP_DEC},       {"CARMA_TUNE_PT_ROW_WGS_PER_CU", 11, TP_DEC},
     {"CARMA_TUNE_PT_ROW_ROT", 11, TP_HEX},        {"CARMA_TUNE_PT_ROW_XCD_MAP", 11, TP_DEC},      {"CARMA_PT_PLAIN", 6, TP_FLAG},
-    {"CARMA_TUNE_MBAND_SMOOTH_CHUNK_ROWS", 11, TP_DEC}};
+    {"CARMA_TUNE_MBAND_SMOOTH_CHUNK_ROWS", 11, TP_DEC}, {"CARMA_TUNE_PT_RAM_WIDE_MIN", 11, TP_DEC}};
 static std::atomic<long> g_tune[TUNE_COUNT];
 static std::atomic<int> g_tune_init{0};
 static void tune_init()
@@ -759,6 +759,7 @@ ShapeSwitches shape_switches()
     sw.p3l_rows = v(TUNE_P3L_ROWS), sw.lane_min = v(TUNE_LANE_MIN), sw.lpc_min = v(TUNE_LPC_MIN), sw.lpc_max = v(TUNE_LPC_MAX);
     sw.lpc_rot = v(TUNE_LPC_ROT), sw.car1_scan_max = v(TUNE_CAR1_SCAN_MAX), sw.pt_row_wgs_per_cu = v(TUNE_PT_ROW_WGS_PER_CU);
     sw.pt_row_rot = v(TUNE_PT_ROW_ROT), sw.pt_row_xcd_map = v(TUNE_PT_ROW_XCD_MAP), sw.pt_plain = v(TUNE_PT_PLAIN);
+    sw.pt_ram_wide_min = v(TUNE_PT_RAM_WIDE_MIN);
     return sw;
 }
 

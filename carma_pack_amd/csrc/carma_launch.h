@@ -44,7 +44,8 @@ int device_cus();
 enum {
     TUNE_WIN_ROWS = 0, TUNE_WIN2_EVALS, TUNE_PT_ROW_WIN, TUNE_CSIM_CHUNK_PATHS, TUNE_SMOOTH_CHUNK_MODELS,
     TUNE_P3L_ROWS, TUNE_LANE_MIN, TUNE_LPC_MIN, TUNE_LPC_MAX, TUNE_LPC_ROT, TUNE_CAR1_SCAN_MAX,
-    TUNE_PT_ROW_WGS_PER_CU, TUNE_PT_ROW_ROT, TUNE_PT_ROW_XCD_MAP, TUNE_PT_PLAIN, TUNE_MBAND_SMOOTH_CHUNK_ROWS, TUNE_COUNT
+    TUNE_PT_ROW_WGS_PER_CU, TUNE_PT_ROW_ROT, TUNE_PT_ROW_XCD_MAP, TUNE_PT_PLAIN, TUNE_MBAND_SMOOTH_CHUNK_ROWS,
+    TUNE_PT_RAM_WIDE_MIN, TUNE_COUNT
 };
 long tune_get(int which);                    // TUNE_UNSET or the override
 int tune_set(const char* name, long value);  // "WIN_ROWS" / "WIN2_EVALS" / "PT_ROW_WIN" / "CSIM_CHUNK_PATHS" / "SMOOTH_CHUNK_MODELS" / "MBAND_SMOOTH_CHUNK_ROWS" (or the full CARMA_TUNE_ name); 0 or -1

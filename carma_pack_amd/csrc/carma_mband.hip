@@ -125,6 +125,8 @@ carma_bands* carma_bands_create(const double* time, const double* y, const doubl
     mband_pack(ts, ys, es, rec, c->boff);
     c->t0 = ts[0][0];                                         // (as mband_pack takes it: requested times get the same shift)
     for (int b = 1; b < K; b++) c->t0 = std::min(c->t0, ts[b][0]);
+    c->ts = ts;
+    c->ys = ys;
     if (select_device(device) != CARMA_OK) {
         delete c;
         return nullptr;

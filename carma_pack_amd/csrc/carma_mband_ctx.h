@@ -1,14 +1,23 @@
 // carma_mband_ctx.h -- the multi-band context behind a carma_bands handle, shared by the files that serve it (carma_mband.hip:
-// log-density and optimiser; carma_mband_smooth.hip: smoother).  Host C++ only.
+// log-density and optimiser; carma_mband_smooth.hip: smoother; carma_mband_pt.hip: sampler).  Host C++ only.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <vector>
 
 #include "carma_devbuf.h"
+#include "carma_pt_state.h"
 #include "carma_types.h"
 
 namespace carma {
+
+// Sampler state of a multi-band context (carma_bands_pt_*): one run of R replicas (ladders) of T chains on the extended vector
+struct BptState : PtEnsemble {
+    bool has_box = false;
+    std::vector<double> box;          // [2][K - 1][2]: lo then hi of (log a_b, mu_b), when has_box
+    DevBuf<double> d_box;             // ... on the device
+};
 
 // Multi-band context: the records of all bands in one buffer, a sentinel behind each band
 struct Bctx {
@@ -21,6 +30,8 @@ struct Bctx {
     DevMem d_rec, d_boff, d_lagbox;
     DevMem d_theta, d_out;            // per-call buffers of the host-pointer entry point, grown on demand
     hipStream_t stream = nullptr;
+    std::vector<std::vector<double>> ts, ys;   // [K] the bands' times and values after sort / dedup (the sampler's starting values)
+    std::unique_ptr<BptState> bpt;    // the sampler, after carma_bands_pt_create
 };
 
 }  // namespace carma

@@ -1,0 +1,430 @@
+// carma_mband_pt.hip -- the SAMPLER of a multi-band fit (carma_bands_pt_*): the large-ensemble
+// sampler of carma_pt_lane.hip -- one chain per lane, an iteration as propose / K1 / finish -- on the extended vector of a
+// carma_bands handle, [dx = 3 + p + q + 3 (K - 1)]: the CARMA part, then (lag_b, log a_b, mu_b) per further band.  K1 is
+// k_logdens_carma_mband_chains: the merged Kalman filter of carma_mband.h, one chain per lane, plus the sampler's band box
+// (carma_mband_pt_plan.h).  The bookkeeping is launch_pt_lane_k1's: the templated kernels up to dx = 16, the wide ones beyond
+// (ram_kernels_plan).  One run of R replicas x T temperatures; host-only decisions in carma_mband_pt_plan.h.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+#include "grp_device.h"
+#include "carma_core.h"
+#include "carma_lane.h"
+#include "carma_mband.h"
+#include "carma_host.h"
+#include "carma_mband_ctx.h"
+#include "carma_mband_pt_plan.h"
+
+namespace carma {
+
+static_assert(MBAND_PT_DMAX == RAM_DMAX_WIDE, "carma_mband_pt_plan.h and carma_shape_plan.h disagree on the widest chain");
+
+// dynamic LDS of a workgroup, as k_logdens_carma_mband carves it: tables, work arrays, band offsets (padded to 16 ints)
+static size_t mband_chains_lds_bytes(int K) { return sizeof(double) * MATH_TAB_N + MbandWork::bytes(K) + sizeof(int) * 16; }
+
+// K1 of the bands sampler: ONE CHAIN PER LANE, chain gi = 64 blockIdx.x + threadIdx.x; thn = [nc][dx] chain-major (the proposals
+// the bookkeeping kernels write), ll = [nc].  The body is logdensity_mband_lane with the prior, as k_logdens_carma_mband calls it:
+// inside the box a chain gets that kernel's bits.  box = [2][K - 1][2], lo then hi of (log a_b, mu_b), or null: a chain with a
+// band term outside (or NaN) gets -inf.  Lanes past nc shadow the wave's first chain and write nothing.
+template <int P>
+__global__ __launch_bounds__(64) void k_logdens_carma_mband_chains(const double* __restrict__ thn, int dx, int q, int K, int N,
+                                                                  const double4* __restrict__ rec, const int* __restrict__ boff,
+                                                                  const double* __restrict__ lagbox, const double* __restrict__ box,
+                                                                  Prior pr, long nc, double* __restrict__ ll)
+{
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    const int lane = threadIdx.x;
+    const size_t KL = (size_t)K * MBAND_LANES;
+    double* s_tab = s_dyn;
+    double* s_work = s_dyn + MATH_TAB_N;
+    int* s_pos = reinterpret_cast<int*>(s_work + 5 * KL);
+    int* s_boff = s_pos + KL;
+    math_tab_fill(s_tab);
+    if (lane <= K) s_boff[lane] = boff[lane];
+    __syncthreads();
+    MbandWork wk;
+    wk.y = s_work + lane;
+    wk.e2 = s_work + KL + lane;
+    wk.a = s_work + 2 * KL + lane;
+    wk.mu = s_work + 3 * KL + lane;
+    wk.lag = s_work + 4 * KL + lane;
+    wk.pos = s_pos + lane;
+    wk.boff = s_boff;
+    long gi = (long)blockIdx.x * 64 + lane;
+    const bool live = gi < nc;
+    if (!live) gi = (long)blockIdx.x * 64;
+    const double* thx = thn + gi * dx;
+    double v = logdensity_mband_lane<P>(thx, q, K, N, rec, lagbox, pr, 0, s_tab, wk);
+    if (box) {
+        const int d = dx - 3 * (K - 1), nb = 2 * (K - 1);
+        bool in = true;
+        for (int i = 0; i < nb; i++) {
+            const double x = thx[d + 3 * (i >> 1) + 1 + (i & 1)];
+            in = in && x >= box[i] && x <= box[nb + i];
+        }
+        if (!in) v = -1.0 / 0.0;
+    }
+    if (live) ll[gi] = v;
+}
+
+static hipError_t launch_logdens_mband_chains(const Bctx* c, const BptState* s, const double* thn, long nc, double* ll, hipStream_t st)
+{
+    (void)hipGetLastError();   // HIP's last-error is sticky: drop anything left by earlier calls
+    if (nc <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((nc + 63) / 64)), block(64);
+    const size_t lds = mband_chains_lds_bytes(c->K);
+    const double* box = s->has_box ? s->d_box.get() : nullptr;
+    auto go = [&](auto P) {
+        hipLaunchKernelGGL((k_logdens_carma_mband_chains<decltype(P)::value>), grid, block, lds, st, thn, c->dx, c->q, c->K, c->N,
+                           c->d_rec.as<const double4>(), c->d_boff.as<const int>(), c->d_lagbox.as<const double>(), box, c->pr, nc, ll);
+        return hipGetLastError();
+    };
+    if (c->p == 1) return go(std::integral_constant<int, 1>{});   // (for_order starts at 2: CAR(1) is the generic body at P = 1 here)
+    return for_order(c->p, hipErrorInvalidValue, go);
+}
+
+// the sampler state of h, or null with the error set: `who` was called before carma_bands_pt_create (need_start: or before the
+// chains have starting values)
+static BptState* bpt_state(carma_bands* h, const char* who, bool need_start)
+{
+    if (!h) {
+        set_error("%s: null context", who);
+        return nullptr;
+    }
+    BptState* s = reinterpret_cast<Bctx*>(h)->bpt.get();
+    if (!s) {
+        set_error("%s: call carma_bands_pt_create first", who);
+        return nullptr;
+    }
+    if (need_start && !s->started) {
+        set_error("%s: chains have no starting values (carma_bands_pt_start / carma_bands_pt_set_chains)", who);
+        return nullptr;
+    }
+    return s;
+}
+
+static std::vector<BandView> band_views(const Bctx* c)
+{
+    std::vector<BandView> v((size_t)c->K);
+    for (int b = 0; b < c->K; b++) v[b] = BandView{c->ts[b].data(), c->ys[b].data(), c->n[b]};
+    return v;
+}
+
+// the log-density a chain of the sampler has at thx [m][dx]: the library's, with the prior, and -inf outside the band box
+static int bpt_logdens_host(carma_bands* h, const BptState* s, const double* thx, size_t m, double* out)
+{
+    Bctx* c = reinterpret_cast<Bctx*>(h);
+    const int rc = carma_bands_logdensity_batch(h, thx, (int)m, 0, out);
+    if (rc != CARMA_OK || !s->has_box) return rc;
+    const size_t nb = 2 * (size_t)(c->K - 1);
+    for (size_t i = 0; i < m; i++)
+        if (!mband_pt_in_box(thx + i * c->dx, c->d, c->K, s->box.data(), s->box.data() + nb)) out[i] = -std::numeric_limits<double>::infinity();
+    return CARMA_OK;
+}
+
+// niter iterations, a chunk in flight at a time.  thin > 0: save the coldest chains every thin iterations from sample *save_offset on
+static int bpt_iterate(Bctx* c, long niter, int do_exchange, int thin, long* save_offset)
+{
+    BptState* s = c->bpt.get();
+    const long chunk0 = mband_pt_chunk_iters(c->N);
+    const PtLaneK1 k1 = [c, s](const double* thn, long nc, double* ll, hipStream_t st) {
+        return launch_logdens_mband_chains(c, s, thn, nc, ll, st);
+    };
+    long left = niter;
+    while (left > 0) {
+        const long ch = pt_next_chunk(left, chunk0, thin);
+        const PtLaunch L = pt_ens_launch(s, c->dx, c->q, c->N, ch, do_exchange, thin, save_offset ? *save_offset : 0);
+        hipError_t e = launch_pt_lane_k1(c->p, L, s->d_scratch, k1, pt_ens_buffers(s), !s->factor_loaded, c->stream);
+        if (e == hipSuccess) {
+            s->factor_loaded = true;
+            s->chol_stale = true;
+            e = hipStreamSynchronize(c->stream);
+        }
+        if (e != hipSuccess) return hip_fail(e, "carma_bands_pt: sampler launch");
+        pt_ens_advance(s, ch, thin, save_offset);
+        left -= ch;
+    }
+    return CARMA_OK;
+}
+
+}  // namespace carma
+
+using namespace carma;
+
+extern "C" {
+
+int carma_bands_pt_default_box(const carma_bands* h, double* band_lo, double* band_hi)
+{
+    if (!h || !band_lo || !band_hi) {
+        set_error("carma_bands_pt_default_box: null context or output");
+        return CARMA_EINVAL;
+    }
+    const Bctx* c = reinterpret_cast<const Bctx*>(h);
+    const std::vector<BandView> bands = band_views(c);
+    mband_pt_default_box(bands.data(), c->K, band_lo, band_hi);
+    return CARMA_OK;
+}
+
+int carma_bands_pt_create(carma_bands* h, int ntemps, int nreplicas, const double* temperatures, int adapt_iters, uint64_t seed,
+                          const double* band_lo, const double* band_hi)
+{
+    if (!h) {
+        set_error("carma_bands_pt_create: null context");
+        return CARMA_EINVAL;
+    }
+    Bctx* c = reinterpret_cast<Bctx*>(h);
+    const std::string bad = mband_pt_check_create(ntemps, nreplicas, adapt_iters, c->dx, c->K, c->n[0], band_lo, band_hi);
+    if (!bad.empty()) {
+        set_error("carma_bands_pt_create: %s", bad.c_str());
+        return CARMA_EINVAL;
+    }
+    hipError_t e = hipSetDevice(c->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    c->bpt.reset(new BptState());         // (the state of an earlier call goes, with every buffer it holds)
+    BptState* s = c->bpt.get();
+    s->maxiter = adapt_iters;
+    s->seed = seed;
+    std::vector<double> temps;
+    default_ladder(ntemps, temperatures, temps);
+    const int dx = c->dx;
+    const size_t nchain = (size_t)nreplicas * ntemps, nb = 2 * (size_t)(c->K - 1);
+    const std::vector<BandView> bands = band_views(c);
+    std::vector<double> R0((size_t)dx * dx), chol(nchain * dx * dx);
+    mband_pt_initial_factor(bands.data(), c->K, c->d, R0.data());
+    for (size_t k = 0; k < nchain; k++) std::memcpy(&chol[k * dx * dx], R0.data(), sizeof(double) * dx * dx);
+    s->has_box = band_lo != nullptr && nb > 0;
+    if (s->has_box) {
+        s->box.assign(band_lo, band_lo + nb);
+        s->box.insert(s->box.end(), band_hi, band_hi + nb);
+    }
+    e = pt_ens_create(s, ntemps, nreplicas, dx, temps, chol.data());
+    if (e == hipSuccess) e = s->d_scratch.alloc(pt_lane_scratch_doubles(dx, (long)nchain));
+    if (e == hipSuccess && s->has_box) e = s->d_box.alloc(2 * nb);
+    if (e == hipSuccess && s->has_box) e = hipMemcpy(s->d_box, s->box.data(), sizeof(double) * 2 * nb, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        c->bpt.reset();
+        return hip_fail(e, "carma_bands_pt_create");
+    }
+    return CARMA_OK;
+}
+
+int carma_bands_pt_set_chains(carma_bands* h, const double* theta, const double* logpost)
+{
+    BptState* s = bpt_state(h, "carma_bands_pt_set_chains", false);
+    if (!s) return CARMA_EINVAL;
+    if (!theta) {
+        set_error("carma_bands_pt_set_chains: null theta");
+        return CARMA_EINVAL;
+    }
+    Bctx* c = reinterpret_cast<Bctx*>(h);
+    const size_t nchain = s->nchain();
+    std::vector<double> lp(nchain);
+    if (logpost) {
+        std::memcpy(lp.data(), logpost, sizeof(double) * nchain);
+    } else {
+        const int rc = bpt_logdens_host(h, s, theta, nchain, lp.data());
+        if (rc != CARMA_OK) return rc;
+    }
+    hipError_t e = hipSetDevice(c->device);
+    if (e == hipSuccess) e = pt_ens_set_chains(s, c->dx, theta, lp.data());
+    if (e != hipSuccess) return hip_fail(e, "carma_bands_pt_set_chains");
+    s->started = true;
+    return CARMA_OK;
+}
+
+int carma_bands_pt_get_chains(carma_bands* h, double* theta, double* logpost)
+{
+    BptState* s = bpt_state(h, "carma_bands_pt_get_chains", false);
+    if (!s) return CARMA_EINVAL;
+    Bctx* c = reinterpret_cast<Bctx*>(h);
+    hipError_t e = hipSetDevice(c->device);
+    if (e == hipSuccess) e = pt_ens_get_chains(s, c->dx, theta, logpost);
+    if (e != hipSuccess) return hip_fail(e, "carma_bands_pt_get_chains");
+    return CARMA_OK;
+}
+
+int carma_bands_pt_start(carma_bands* h, const double* init)
+{
+    BptState* s = bpt_state(h, "carma_bands_pt_start", false);
+    if (!s) return CARMA_EINVAL;
+    Bctx* c = reinterpret_cast<Bctx*>(h);
+    const int dx = c->dx;
+    const size_t nchain = s->nchain();
+    std::vector<double> theta(nchain * dx), lp(nchain, -std::numeric_limits<double>::infinity());
+    std::vector<char> done(nchain, 0);
+    // the init row is honoured when its log-density is finite (src/samplers.cpp:75-93): it becomes every chain of the run
+    if (init) {
+        double l0 = 0.0;
+        const int rc = bpt_logdens_host(h, s, init, 1, &l0);
+        if (rc != CARMA_OK) return rc;
+        if (std::isfinite(l0))
+            for (size_t k = 0; k < nchain; k++) {
+                std::memcpy(&theta[k * dx], init, sizeof(double) * dx);
+                lp[k] = l0;
+                done[k] = 1;
+            }
+    }
+    const std::vector<BandView> bands = band_views(c);
+    const int rc = find_starts(
+        nchain, dx, theta.data(), lp.data(), done.data(),
+        [&](size_t k, int round, double* out) {
+            mband_pt_draw_start(bands.data(), c->K, c->pr, c->p, c->q, c->lagbox.data(), s->seed, (uint64_t)k, round, out);
+        },
+        [&](const double* cand, const size_t*, size_t m, double* out) { return bpt_logdens_host(h, s, cand, m, out); });
+    if (rc != CARMA_OK) return rc;
+    for (size_t k = 0; k < nchain; k++)
+        if (!done[k]) {
+            set_error("carma_bands_pt_start: no finite starting value found for chain %zu (temperature %zu of replica %zu)", k,
+                      k % (size_t)s->T, k / (size_t)s->T);
+            return CARMA_EINVAL;
+        }
+    return carma_bands_pt_set_chains(h, theta.data(), lp.data());
+}
+
+int carma_bands_pt_get_factor(carma_bands* h, double* chol)
+{
+    BptState* s = bpt_state(h, "carma_bands_pt_get_factor", false);
+    if (!s) return CARMA_EINVAL;
+    if (!chol) {
+        set_error("carma_bands_pt_get_factor: null chol");
+        return CARMA_EINVAL;
+    }
+    Bctx* c = reinterpret_cast<Bctx*>(h);
+    hipError_t e = hipSetDevice(c->device);
+    if (e == hipSuccess) e = pt_ens_get_factor(s, c->dx, c->stream, chol);
+    if (e != hipSuccess) return hip_fail(e, "carma_bands_pt_get_factor");
+    return CARMA_OK;
+}
+
+int carma_bands_pt_set_factor(carma_bands* h, const double* chol)
+{
+    BptState* s = bpt_state(h, "carma_bands_pt_set_factor", false);
+    if (!s) return CARMA_EINVAL;
+    if (!chol) {
+        set_error("carma_bands_pt_set_factor: null chol");
+        return CARMA_EINVAL;
+    }
+    Bctx* c = reinterpret_cast<Bctx*>(h);
+    hipError_t e = hipSetDevice(c->device);
+    if (e == hipSuccess) e = pt_ens_set_factor(s, c->dx, c->stream, chol);
+    if (e != hipSuccess) return hip_fail(e, "carma_bands_pt_set_factor");
+    return CARMA_OK;
+}
+
+int carma_bands_pt_iterate(carma_bands* h, long niter, int do_exchange)
+{
+    BptState* s = bpt_state(h, "carma_bands_pt_iterate", true);
+    if (!s) return CARMA_EINVAL;
+    if (niter < 0) {
+        set_error("carma_bands_pt_iterate: niter < 0");
+        return CARMA_EINVAL;
+    }
+    Bctx* c = reinterpret_cast<Bctx*>(h);
+    const hipError_t e = hipSetDevice(c->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    return bpt_iterate(c, niter, do_exchange, 0, nullptr);
+}
+
+int carma_bands_pt_sample(carma_bands* h, int nsamples, int thin, double* samples, double* logposts)
+{
+    BptState* s = bpt_state(h, "carma_bands_pt_sample", true);
+    if (!s) return CARMA_EINVAL;
+    if (nsamples < 1 || thin < 1 || !samples || !logposts) {
+        set_error("carma_bands_pt_sample: bad argument (nsamples >= 1, thin >= 1, non-null outputs)");
+        return CARMA_EINVAL;
+    }
+    Bctx* c = reinterpret_cast<Bctx*>(h);
+    hipError_t e = hipSetDevice(c->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    long capacity = 0;
+    e = s->reserve_samples(c->dx, nsamples, &capacity);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("carma_bands_pt_sample: no device memory for the sample buffer: %zu bytes asked for (%ld ladders x %d samples x %d)",
+                  sizeof(double) * (size_t)s->R * nsamples * (c->dx + 1), (long)s->R, nsamples, c->dx);
+        return CARMA_ENOMEM;
+    }
+    long off = 0;
+    int rc = bpt_iterate(c, (long)nsamples * thin, 1, thin, &off);
+    if (rc == CARMA_OK) {
+        e = pt_ens_fetch_samples(s, c->dx, nsamples, samples, logposts);
+        if (e != hipSuccess) rc = hip_fail(e, "carma_bands_pt_sample: D2H");
+    }
+    s->cap = capacity;
+    return rc;
+}
+
+int carma_bands_pt_stats(carma_bands* h, double* accept_rate, double* swap_rate, int reset)
+{
+    BptState* s = bpt_state(h, "carma_bands_pt_stats", false);
+    if (!s) return CARMA_EINVAL;
+    Bctx* c = reinterpret_cast<Bctx*>(h);
+    hipError_t e = hipSetDevice(c->device);
+    if (e == hipSuccess) e = pt_ens_stats(s, accept_rate, swap_rate, reset);
+    if (e != hipSuccess) return hip_fail(e, "carma_bands_pt_stats");
+    return CARMA_OK;
+}
+
+long carma_bands_pt_iterations_done(const carma_bands* h)
+{
+    if (!h || !reinterpret_cast<const Bctx*>(h)->bpt) return CARMA_EINVAL;
+    return (long)reinterpret_cast<const Bctx*>(h)->bpt->iter;
+}
+
+int carma_bands_pt_logdensity(carma_bands* h, const double* theta, double* out)
+{
+    BptState* s = bpt_state(h, "carma_bands_pt_logdensity", false);
+    if (!s) return CARMA_EINVAL;
+    if (!theta || !out) {
+        set_error("carma_bands_pt_logdensity: null theta or out");
+        return CARMA_EINVAL;
+    }
+    Bctx* c = reinterpret_cast<Bctx*>(h);
+    const size_t nchain = s->nchain(), GUARD = 64;
+    // [nc][dx] proposals, [nc] results, then GUARD words nobody may write: a kernel whose idle lanes stored would show here
+    std::vector<double> res(nchain + GUARD, 0.0);
+    const double mark = -12345.678;
+    std::fill(res.begin() + nchain, res.end(), mark);
+    hipError_t e = hipSetDevice(c->device);
+    if (e == hipSuccess) e = c->d_theta.need(sizeof(double) * (nchain * c->dx + nchain + GUARD));
+    double *d_th = c->d_theta.as<double>(), *d_ll = d_th + nchain * c->dx;
+    if (e == hipSuccess) e = hipMemcpyAsync(d_th, theta, sizeof(double) * nchain * c->dx, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_ll, res.data(), sizeof(double) * res.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_logdens_mband_chains(c, s, d_th, (long)nchain, d_ll, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(res.data(), d_ll, sizeof(double) * res.size(), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return hip_fail(e, "carma_bands_pt_logdensity");
+    for (size_t k = nchain; k < res.size(); k++)
+        if (res[k] != mark) {
+            set_error("carma_bands_pt_logdensity: the kernel wrote past its %zu results", nchain);
+            return CARMA_EHIP;
+        }
+    std::memcpy(out, res.data(), sizeof(double) * nchain);
+    return CARMA_OK;
+}
+
+int carma_bands_pt_kernel_name(const carma_bands* h, char* buf, int len)
+{
+    if (!h || !buf || len < 1) return CARMA_EINVAL;
+    const Bctx* c = reinterpret_cast<const Bctx*>(h);
+    return snprintf(buf, len, "k_logdens_carma_mband_chains<%d>", c->p) > 0 ? CARMA_OK : CARMA_EINVAL;
+}
+
+int carma_bands_pt_run(carma_bands* h, int ntemps, int nreplicas, int sample_size, int burnin, int thin, const double* init,
+                       uint64_t seed, const double* band_lo, const double* band_hi, double* samples, double* logposts)
+{
+    int rc = carma_bands_pt_create(h, ntemps, nreplicas, nullptr, burnin, seed, band_lo, band_hi);
+    if (rc == CARMA_OK) rc = carma_bands_pt_start(h, init);
+    if (rc == CARMA_OK) rc = carma_bands_pt_iterate(h, burnin, 1);                     // Sampler::Run burn-in (samplers.cpp:97)
+    if (rc == CARMA_OK) rc = carma_bands_pt_sample(h, sample_size, thin, samples, logposts);   // :101-108
+    return rc;
+}
+
+}  // extern "C"

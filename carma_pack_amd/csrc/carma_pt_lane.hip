@@ -44,8 +44,8 @@
 
 namespace carma {
 
-constexpr int RAM_DMAX = 16;                                 // d = 3 + p + q <= 16
-constexpr int RAM_DS = 17;                                   // stride of a lane's vector in LDS (odd)
+// (RAM_DMAX = 16, d = 3 + p + q of one series, and RAM_DMAX_WIDE = 37, the widest multi-band vector: carma_shape_plan.h)
+constexpr int RAM_DS = 17;                                  // stride of a lane's vector in LDS (odd)
 
 struct RamState {                                            // chain-minor working state (device pointers)
     double* th;      // [d][nc]
@@ -311,10 +311,157 @@ __global__ __launch_bounds__(256) void k_ram_finish(PtLaunch L, RamState S, cons
     }
 }
 
+// ---- the WIDE bookkeeping: run-time d <= RAM_DMAX_WIDE (the extended vector of a multi-band fit, 17 ... 37 entries; any d >= 4
+// with PT_RAM_WIDE_MIN lowered, which is how the tests hold these kernels against the templated ones).  A factor of up to 703
+// doubles per chain cannot live in registers, and a register array indexed by a run-time d goes to scratch (carma_mband.h met the
+// same): the factor is STREAMED from its chain-minor rows, one row of the triangle at a time (every access of a wave one contiguous
+// 512-byte segment), and the per-lane vectors -- the draws and the sums v of the proposal; v, the current value and the sweep's
+// staging of the finish -- are lane-contiguous LDS arrays [d][64], a lane touching nothing but its own column outside the sweep.
+// One wave per workgroup: 2 x 37 x 64 doubles + the sweep's words = 40 KiB of static LDS.
+// Same PtLaunch / PtBuffers, same Philox keys, same formulas in the same operation order as the templated kernels above.
+constexpr int RAM_WL = 64;                                   // lanes of a workgroup of the wide kernels
+
+__global__ __launch_bounds__(RAM_WL) void k_ram_propose_wide(PtLaunch L, RamState S)
+{
+    __shared__ double s_z[RAM_DMAX_WIDE * RAM_WL], s_acc[RAM_DMAX_WIDE * RAM_WL];
+    const RamLane x = ram_lane(L);
+    const int d = L.d, lane = threadIdx.x;
+    const uint64_t iter = L.iter0;
+    const RngKey key{L.seed0, L.seed1, x.chain};
+    double znorm2 = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < d; k++) {
+        const double zk = rng_student_t8(key, iter, (uint32_t)k);
+        s_z[k * RAM_WL + lane] = zk;
+        s_acc[k * RAM_WL + lane] = 0.0;
+        znorm2 += zk * zk;
+    }
+    if (!x.active) return;
+    S.z2[x.gi] = znorm2;
+    // v_j = sum_{k <= j} R_kj z_k, k ascending for every j: row k of the triangle adds its term to the sums j >= k
+    const double* Rk = S.R + x.gi;
+#pragma unroll 1
+    for (int k = 0; k < d; k++) {
+        const double zk = s_z[k * RAM_WL + lane];
+#pragma unroll 4
+        for (int j = k; j < d; j++) {
+            double acc = s_acc[j * RAM_WL + lane];
+            acc += Rk[(long)(j - k) * S.nc] * zk;
+            s_acc[j * RAM_WL + lane] = acc;
+        }
+        Rk += (long)(d - k) * S.nc;
+    }
+#pragma unroll 1
+    for (int j = 0; j < d; j++) {
+        const double acc = s_acc[j * RAM_WL + lane];
+        S.v[(long)j * S.nc + x.gi] = acc;
+        S.thn[x.gi * d + j] = S.th[(long)j * S.nc + x.gi] + acc;
+    }
+}
+
+__global__ __launch_bounds__(RAM_WL) void k_ram_finish_wide(PtLaunch L, RamState S, const double* __restrict__ temps,
+                                                            unsigned* __restrict__ naccept, unsigned* __restrict__ nswap,
+                                                            double* __restrict__ samples, double* __restrict__ sample_lp)
+{
+    __shared__ double s_v[RAM_DMAX_WIDE * RAM_WL];           // v = R^T z, then the rank-1 vector of the adaptation
+    __shared__ double s_th[RAM_DMAX_WIDE * RAM_WL];          // the lanes' current values: the staging of the sweep
+    __shared__ double s_lp[RAM_WL], s_logu[RAM_WL], s_dbeta[RAM_WL];
+    __shared__ int s_src[RAM_WL];
+    __shared__ unsigned long long s_mask[RAM_WL];
+    const RamLane x = ram_lane(L);
+    const int d = L.d, T = L.T, lane = threadIdx.x;
+    const uint64_t iter = L.iter0;
+    const RngKey key{L.seed0, L.seed1, x.chain};
+    const bool adapt = (long)iter < (long)L.maxiter;
+    const double ll = S.ll[x.gi];
+    double lp = S.lp[x.gi];
+    const double z2_in = adapt ? S.z2[x.gi] : 1.0;
+    const bool exch = L.do_exchange && L.T > 1;
+    const unsigned nacc_in = naccept[x.gi], nswap_in = exch ? nswap[x.gi] : 0u;
+    double alpha = (ll - lp) / temps[x.c];
+    bool accept = false;
+    if (!((alpha - alpha) == 0.0)) {
+        alpha = 0.0;                                         // steps.cpp:41-46
+    } else {
+        const double u = rng_uniform(key, iter, RNG_ACCEPT, 0);
+        alpha = fmin(exp(alpha), 1.0);
+        accept = u < alpha;
+    }
+    // the proposal K1 evaluated is th + v, bit for bit (k_ram_propose_wide stored that sum as thn[chain][.])
+#pragma unroll 4
+    for (int j = 0; j < d; j++) {
+        const double vj = S.v[(long)j * S.nc + x.gi];
+        double thj = S.th[(long)j * S.nc + x.gi];
+        if (accept) thj += vj;
+        s_v[j * RAM_WL + lane] = vj;
+        s_th[j * RAM_WL + lane] = thj;
+    }
+    if (accept) {                                            // parameter_.Save(new_value) (steps.cpp:77)
+        lp = ll;
+        if (x.active) naccept[x.gi] = nacc_in + 1u;
+    }
+    // ---- adaptation while niter < maxiter: the rank-1 update of k_ram_finish, a row of the factor in flight at a time
+    if (adapt) {
+        const double step = fmin(1.0, (double)d / pow((double)iter, 2.0 / 3.0));   // iter = 0 -> 1
+        const double fac = sqrt(step * fabs(alpha - 0.25)) / sqrt(z2_in);
+        const double sign = alpha < 0.25 ? -1.0 : 1.0;
+#pragma unroll 4
+        for (int j = 0; j < d; j++) s_v[j * RAM_WL + lane] *= fac;
+        double* Rk = S.R + x.gi;                             // R_kk of this lane's chain
+#pragma unroll 1
+        for (int k = 0; k < d; k++) {
+            const double Rkk = Rk[0], vk = s_v[k * RAM_WL + lane];
+            const double xx = fma(sign * vk, vk, Rkk * Rkk);
+            const double rs = rsqrt_nr(xx), iR = recip(Rkk);
+            const double rr = xx * rs;
+            const double cc = rr * iR, ss = vk * iR, ic = Rkk * rs;
+            if (x.active) Rk[0] = rr;
+#pragma unroll 4
+            for (int j = k + 1; j < d; j++) {
+                const double vj = s_v[j * RAM_WL + lane];
+                const double Rkj = (Rk[(long)(j - k) * S.nc] + sign * ss * vj) * ic;
+                if (x.active) Rk[(long)(j - k) * S.nc] = Rkj;
+                s_v[j * RAM_WL + lane] = cc * vj - ss * Rkj;
+            }
+            Rk += (long)(d - k) * S.nc;
+        }
+    }
+    // ---- ExchangeStep sweep hot -> cold over the ladder's T lanes, as k_ram_finish: one lane per ladder replays the serial
+    // decisions, every lane fetches the column the sweep assigned to its temperature
+    const bool save = L.save_thin > 0 && x.active && x.c0 == 0 && L.save_offset < L.sample_cap;
+    bool moved = accept;                                     // the lane's value in global memory is out of date
+    int col = lane;                                          // the column of s_th this lane's temperature holds
+    if (exch) {
+        s_lp[lane] = lp;
+        s_src[lane] = x.c0;
+        s_dbeta[lane] = x.c > 0 ? 1.0 / temps[x.c] - 1.0 / temps[x.c - 1] : 0.0;
+        s_logu[lane] = x.c > 0 ? log(rng_uniform(key, iter, RNG_SWAP, 0)) : 0.0;   // keyed by the hotter chain's global slot
+        wave_sync();
+        const int lb = x.lbase;
+        if (x.active && x.c0 == 0) s_mask[lb] = exchange_decide_mask(T, s_lp + lb, s_dbeta + lb, s_logu + lb, s_src + lb);
+        wave_sync();
+        if (x.active && ((s_mask[lb] >> x.c0) & 1ull)) nswap[x.gi] = nswap_in + 1u;   // ExchangeStep's count, per hotter temperature
+        const int from = s_src[lane];
+        moved = moved || from != x.c0;
+        lp = s_lp[lane];
+        col = lb + from;
+    }
+    if (moved && x.active) {
+        S.lp[x.gi] = lp;
+#pragma unroll 4
+        for (int j = 0; j < d; j++) S.th[(long)j * S.nc + x.gi] = s_th[j * RAM_WL + col];
+    }
+    if (save) {                                              // Sampler::SaveValues: the coldest chain's value and log-posterior
+#pragma unroll 4
+        for (int j = 0; j < d; j++) samples[(x.lad * L.sample_cap + L.save_offset) * d + j] = s_th[j * RAM_WL + col];
+        sample_lp[x.lad * L.sample_cap + L.save_offset] = lp;
+    }
+}
+
 // doubles of working state for nchain chains of dimension d (RamState)
 size_t pt_lane_scratch_doubles(int d, long nchain)
 {
-    if (d < 1 || d > RAM_DMAX || nchain < 1) return 0;
+    if (d < 1 || d > RAM_DMAX_WIDE || nchain < 1) return 0;
     return ((size_t)3 * d + (size_t)d * (d + 1) / 2 + 3) * (size_t)nchain;
 }
 
@@ -357,7 +504,11 @@ hipError_t launch_pt_lane_k1(int p, const PtLaunch& L, double* scratch, const Pt
                              hipStream_t st)
 {
     (void)hipGetLastError();
-    if (p < 1 || L.T < 1 || L.T > 64 || L.d < 4 || L.d > RAM_DMAX || (p == 1) != (L.d == 4)) return hipErrorInvalidValue;
+    // (a single-series vector has d = 3 + p + q entries, 4 exactly for CAR(1); a caller whose chains carry more than the CARMA
+    // part -- the band terms of carma_mband_pt.hip -- has a wider one)
+    if (p < 1 || L.T < 1 || L.T > 64 || (L.d <= 3 + p + L.q && (p == 1) != (L.d == 4))) return hipErrorInvalidValue;
+    const RamKernels kind = ram_kernels_plan(L.d, shape_switches());
+    if (kind == RamKernels::NONE) return hipErrorInvalidValue;
     const long nc = (long)L.R * L.T;
     const RamState S = ram_state(scratch, L.d, nc);
     const int LPW = 64 / L.T;
@@ -373,10 +524,20 @@ hipError_t launch_pt_lane_k1(int p, const PtLaunch& L, double* scratch, const Pt
         const bool save = L.save_thin > 0 && ((it + 1) % L.save_thin) == 0;
         Li.save_thin = save ? 1 : 0;
         Li.save_offset = save ? L.save_offset + (it + 1) / L.save_thin - 1 : 0;
-        // (later proposals ride on the finish kernel of the iteration before -- where that kernel holds the factor, v, the value AND
-        // the draws in registers: d <= 12.  Beyond, the fused form spills -- 296 bytes per lane at d = 13, 1136 at d = 16, where it
-        // takes 88 us for 16 384 chains against 21 + 27 for the two kernels: profiles/r04/lane_sampler_kernels_p7_v1.txt)
-        const bool fused = L.d <= 12;
+        // (which bookkeeping serves d: ram_kernels_plan, carma_shape_plan.h.  FUSED: later proposals ride on the finish kernel of
+        // the iteration before; WIDE: the run-time-d kernels, a wave per workgroup, a propose and a finish launch per iteration)
+        if (kind == RamKernels::WIDE) {
+            hipLaunchKernelGGL(k_ram_propose_wide, dim3((unsigned)waves), dim3(RAM_WL), 0, st, Li, S);
+            e = hipGetLastError();
+            if (e == hipSuccess) e = k1(S.thn, nc, S.ll, st);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(k_ram_finish_wide, dim3((unsigned)waves), dim3(RAM_WL), 0, st, Li, S, b.temps, b.naccept, b.nswap,
+                                   b.samples, b.sample_lp);
+                e = hipGetLastError();
+            }
+            continue;
+        }
+        const bool fused = kind == RamKernels::FUSED;
         if (it == 0 || !fused)
             e = ram_launch_d(L.d, [&](auto dc) {
                 hipLaunchKernelGGL((k_ram_propose<decltype(dc)::value>), dim3(grid), dim3(256), 0, st, Li, S);

@@ -30,6 +30,7 @@ struct ShapeSwitches {
     long car1_scan_max = TUNE_UNSET;
     long pt_row_wgs_per_cu = TUNE_UNSET, pt_row_rot = TUNE_UNSET, pt_row_xcd_map = TUNE_UNSET;
     long pt_plain = TUNE_UNSET;  // CARMA_PT_PLAIN: 1 plain, 0 producer/consumer
+    long pt_ram_wide_min = TUNE_UNSET;   // PT_RAM_WIDE_MIN: smallest chain dimension the wide RAM bookkeeping serves (unset: 17)
 };
 
 // ---- series flags (carma_types.h, SERIES_*) ------------------------------------------------------------------------------------
@@ -304,6 +305,29 @@ inline PtFamily pt_family(int p, int T, long R, int n, const DeviceFacts& f, con
     }
     if (p >= 2 && force != PtForce::LADDER && pt_row_capacity(T, n, f, sw) >= R * ((T + 3) / 4)) return PtFamily::ROW;
     return PtFamily::LADDER;
+}
+
+// ---- lane sampler: the RAM bookkeeping kernels (carma_pt_lane.hip) -------------------------------------------------------------
+// Which propose / finish kernels an iteration of the lane sampler launches around K1, for chains of dimension d.
+//   FUSED  k_ram_finish<D,true>: the proposal of the following iteration rides on the finish kernel, where that kernel holds the
+//          factor, v, the value AND the draws in registers: d <= 12.  Beyond, the fused form spills -- 296 bytes per lane at
+//          d = 13, 1136 at d = 16, where it takes 88 us for 16 384 chains against 21 + 27 for the two kernels
+//          (profiles/r04/lane_sampler_kernels_p7_v1.txt)
+//   SPLIT  k_ram_propose<D> + k_ram_finish<D,false>: 13 <= d <= 16 (RAM_DMAX, the widest single-series vector, 3 + 7 + 6)
+//   WIDE   k_ram_propose_wide + k_ram_finish_wide, run-time d: the factor streamed from memory a row at a time, the vectors in
+//          LDS.  From d = 17 (a multi-band vector, 3 + p + q + 3 (K - 1) <= RAM_DMAX_WIDE), where no templated kernel exists;
+//          PT_RAM_WIDE_MIN lowers the threshold (down to 4) so that the tests run the wide kernels against the templated ones.
+//   NONE   no kernel serves d
+constexpr int RAM_DMIN = 4, RAM_DMAX = 16, RAM_DMAX_WIDE = 37, RAM_DFUSED_MAX = 12;
+constexpr int RAM_WIDE_MIN_DEFAULT = RAM_DMAX + 1;
+enum class RamKernels { NONE = 0, FUSED = 1, SPLIT = 2, WIDE = 3 };
+inline RamKernels ram_kernels_plan(int d, const ShapeSwitches& sw)
+{
+    if (d < RAM_DMIN || d > RAM_DMAX_WIDE) return RamKernels::NONE;
+    long wide_min = sw.pt_ram_wide_min != TUNE_UNSET ? sw.pt_ram_wide_min : RAM_WIDE_MIN_DEFAULT;
+    if (wide_min > RAM_WIDE_MIN_DEFAULT) wide_min = RAM_WIDE_MIN_DEFAULT;   // (nothing but the wide form exists beyond RAM_DMAX)
+    if (d >= wide_min) return RamKernels::WIDE;
+    return d <= RAM_DFUSED_MAX ? RamKernels::FUSED : RamKernels::SPLIT;
 }
 
 // ---- row sampler (k_pt_row) ----------------------------------------------------------------------------------------------------

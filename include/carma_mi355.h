@@ -110,7 +110,8 @@ int carma_logdensity_kernel_name(const carma_ctx* h, int B, char* buf, int len);
  * launch asks; afterwards only this call moves them (process-wide, thread-safe).  CARMA_EINVAL for an unknown name.
  * "CSIM_CHUNK_PATHS": paths per chunk of carma_simulate_cond_* (0: as many as its scratch cap holds; results do not depend on it).
  * "SMOOTH_CHUNK_MODELS": models per chunk of carma_smooth_* (0: as many whole waves as its scratch cap holds; results do not depend on it).
- * "MBAND_SMOOTH_CHUNK_ROWS": parameter vectors per chunk of carma_bands_smooth (0: as many whole waves as its scratch cap holds; results do not depend on it). */
+ * "MBAND_SMOOTH_CHUNK_ROWS": parameter vectors per chunk of carma_bands_smooth (0: as many whole waves as its scratch cap holds; results do not depend on it).
+ * "PT_RAM_WIDE_MIN": smallest chain dimension whose bookkeeping the lane samplers give to the wide kernels (default 17; 4: every chain). */
 int carma_tune_set(const char* name, long value);
 
 /*
@@ -239,6 +240,51 @@ int carma_bands_smooth(carma_bands* h, const double* theta /* [B][dx] */, int B,
                        double* mean /* [B][M] or NULL */, double* var /* [B][M] or NULL */,
                        double* band_mean /* [M] or NULL */, double* band_var /* [M] or NULL */,
                        int* invalid /* [B] or NULL */);
+
+/*
+ * The parallel-tempering sampler of a MULTI-BAND fit (the carma_mpt_* set on a carma_bands handle, one run): nreplicas independent
+ * ladders of ntemps chains on the extended vector [dx], one chain per lane -- the bookkeeping kernels of the large-ensemble
+ * sampler (carma_pt_lane.hip; their wide, run-time-dimension form from dx = 17) around a log-density kernel that evaluates every
+ * chain with the prior (k_logdens_carma_mband_chains: inside the box the bits of carma_bands_logdensity_batch).  A chain's
+ * random streams are keyed by ladder * T + temperature.  dx <= 37, which every legal handle satisfies.
+ * THE BAND BOX.  The log-density is flat in log a_b and mu_b, and as log a_b -> -inf the likelihood tends to a positive constant:
+ *   the posterior is improper and a hot chain may leave for good.  The sampler confines (log a_b, mu_b) to a box: band_lo /
+ *   band_hi = [nbands - 1][2], lo <= hi, outside which a chain's log-density is -inf; both NULL: no box.
+ *   carma_bands_pt_default_box writes the box the Python layer uses: log a_b within log 1000 of log(std y_b / std y_0) (0 where that
+ *   is undefined), mu_b within [min y_b - span_b, max y_b + span_b], span_b = max y_b - min y_b (max(1, |y_b|) where that is 0).
+ * carma_bands_pt_create: temperatures = [ntemps] or NULL (100^(i / (ntemps - 1))).  The initial proposal factor is diagonal: the
+ *   CARMA block as carma_pt_create takes it from band 0; per band the lag entry is the median time step of band 0, the log a
+ *   entry 0.01, the mu entry sqrt(var y_b / n_b) (0.01 for fewer than 2 data).  CARMA_EINVAL before any device work, with a
+ *   message: ntemps outside 1 ... 64, more chains than a launch indexes, dx > 37, a box with lo > hi or one half of it NULL, fewer
+ *   than 2 data in band 0.
+ * carma_bands_pt_start: init = [dx] or NULL; a finite init row becomes every chain of the run, otherwise every chain draws: the
+ *   CARMA part as carma_pt_start draws it on band 0, then every lag uniform in its box, log a_b = log(std y_b / std y_0) (0 where undefined)
+ *   and mu_b = mean y_b; candidates that are not finite (or outside the box) are retried in rounds.
+ * carma_bands_pt_set_chains / _get_chains: theta = [R][T][dx], logpost = [R][T] (NULL on set: computed, -inf outside the box).
+ * carma_bands_pt_get_factor / _set_factor: [R][T][dx*dx].  _iterate / _sample / _stats / _iterations_done: as the carma_mpt_
+ *   calls; samples = [R][nsamples][dx].  Every call but _create and _default_box is CARMA_EINVAL before carma_bands_pt_create,
+ *   iterate / sample also before the chains have starting values; the handle stays usable.
+ * carma_bands_pt_logdensity: the log-densities of chain states theta = [R][T][dx] through the sampler's kernel, out = [R][T].
+ * carma_bands_pt_run: create, start, burn-in (adapting), sample.
+ */
+int carma_bands_pt_default_box(const carma_bands* h, double* band_lo /* [K-1][2] */, double* band_hi /* [K-1][2] */);
+int carma_bands_pt_create(carma_bands* h, int ntemps, int nreplicas, const double* temperatures /* [ntemps] or NULL */,
+                          int adapt_iters, uint64_t seed, const double* band_lo /* [K-1][2] or NULL */,
+                          const double* band_hi /* [K-1][2] or NULL */);
+int carma_bands_pt_start(carma_bands* h, const double* init /* [dx] or NULL */);
+int carma_bands_pt_set_chains(carma_bands* h, const double* theta /* [R][T][dx] */, const double* logpost /* [R][T] or NULL */);
+int carma_bands_pt_get_chains(carma_bands* h, double* theta, double* logpost);
+int carma_bands_pt_get_factor(carma_bands* h, double* chol);
+int carma_bands_pt_set_factor(carma_bands* h, const double* chol);
+int carma_bands_pt_iterate(carma_bands* h, long niter, int do_exchange);
+int carma_bands_pt_sample(carma_bands* h, int nsamples, int thin, double* samples /* [R][nsamples][dx] */, double* logposts);
+int carma_bands_pt_stats(carma_bands* h, double* accept_rate, double* swap_rate, int reset);
+long carma_bands_pt_iterations_done(const carma_bands* h);
+int carma_bands_pt_logdensity(carma_bands* h, const double* theta /* [R][T][dx] */, double* out /* [R][T] */);
+int carma_bands_pt_kernel_name(const carma_bands* h, char* buf, int len);
+int carma_bands_pt_run(carma_bands* h, int ntemps, int nreplicas, int sample_size, int burnin, int thin,
+                       const double* init /* [dx] or NULL */, uint64_t seed, const double* band_lo, const double* band_hi,
+                       double* samples, double* logposts);
 
 /*
  * The parallel-tempering sampler over MANY SERIES (the carma_pt_* set on a carma_mctx).  A RUN is one sampler -- nreplicas
