@@ -9,12 +9,12 @@ C ABI; it fails loudly if the library has not been built.
   carma_pack_amd.parallel    one-process-per-GPU sharding helpers (torch.distributed)
 """
 from . import _lib  # noqa: F401  (raises ImportError when the HIP library is missing)
-from ._lib import (BandsContext, CarmaDeviceError, CarmaError, Context, MultiContext, kfilter_car1, kfilter_carma, kfilter_carma_batch,  # noqa: F401
+from ._lib import (BandsContext, BandsSetContext, CarmaDeviceError, CarmaError, Context, MultiContext, kfilter_car1, kfilter_carma, kfilter_carma_batch,  # noqa: F401
                    simulate_cond_car1, simulate_cond_carma, smooth_car1, smooth_carma)
-from .carma_pack import (CarmaBandsModel, CarmaBandsSample, CarmaModel, CarmaModelSet, CarmaSample, Car1Sample, car1_process, car1_process_batch,  # noqa: F401
+from .carma_pack import (CarmaBandsModel, CarmaBandsSample, CarmaBandsSet, CarmaModel, CarmaModelSet, CarmaSample, Car1Sample, car1_process, car1_process_batch,  # noqa: F401
                          carma_process, carma_process_batch, carma_variance, get_ar_roots, mle_to_model, power_spectrum)
 
-__all__ = ["Context", "MultiContext", "BandsContext", "CarmaBandsModel", "CarmaBandsSample", "kfilter_carma", "kfilter_carma_batch", "kfilter_car1", "CarmaError", "CarmaDeviceError", "CarmaModel", "CarmaModelSet",
+__all__ = ["Context", "MultiContext", "BandsContext", "BandsSetContext", "CarmaBandsModel", "CarmaBandsSample", "CarmaBandsSet", "kfilter_carma", "kfilter_carma_batch", "kfilter_car1", "CarmaError", "CarmaDeviceError", "CarmaModel", "CarmaModelSet",
            "CarmaSample", "Car1Sample", "get_ar_roots", "power_spectrum", "carma_variance", "car1_process",
            "carma_process", "carma_process_batch", "car1_process_batch", "mle_to_model", "simulate_cond_carma", "simulate_cond_car1",
            "smooth_carma", "smooth_car1"]

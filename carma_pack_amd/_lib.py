@@ -72,6 +72,16 @@ SIGNATURES = {
     "carma_bands_logdensity_batch_dev": (_I, [_V, _V, _I, _I, _V, _V]),
     "carma_bands_mle_batched": (_I, [_V, _V, _I, _V, _V, _V] + _MLE_TAIL),
     "carma_bands_smooth": (_I, [_V, _dp, _I, _I, _dp, _I, _dp, _dp, _dp, _dp, _ip]),
+    "carma_bandset_create": (_V, [_dp, _dp, _dp, _lp, _I, _I, _I, _I, _dp, _dp, _dp, _I]),
+    "carma_bandset_destroy": (None, [_V]),
+    "carma_bandset_nobjects": (_I, [_V]),
+    "carma_bandset_nbands": (_I, [_V]),
+    "carma_bandset_dim": (_I, [_V]),
+    "carma_bandset_n": (_I, [_V, _I, _I]),
+    "carma_bandset_get_prior": (_I, [_V, _I, _dp]),
+    "carma_bandset_logdensity_batch": (_I, [_V, _dp, _ip, _I, _I, _dp]),
+    "carma_bandset_kernel_name": (_I, [_V, _S, _I]),
+    "carma_bandset_mle_batched": (_I, [_V, _V, _V, _I, _V, _V, _V] + _MLE_TAIL),
     "carma_bands_pt_default_box": (_I, [_V, _dp, _dp]),
     "carma_bands_pt_create": (_I, [_V, _I, _I, _dp, _I, _U64, _dp, _dp]),
     "carma_bands_pt_start": (_I, [_V, _dp]),
@@ -1075,6 +1085,89 @@ class BandsContext(_Handle, _Sampler):
         if one:
             mean, var, inv = mean[0], var[0], bool(inv[0])
         return (mean, var, bm, bv, inv) if moments else (mean, var, inv)
+
+
+class BandsSetContext(_Handle):
+    """Owns one carma_bandset: S multi-band objects of the same K bands and order resident in HBM, each prepared as BandsContext
+    prepares its one object; a call carries evaluations of any of them (k_logdens_carma_mband_ms, one object per wave).
+
+    objects: a list of S lists of K (t, y, yerr); lag_bounds: [K - 1] pairs (lo, hi) for every object or [S, K - 1] pairs, one
+    list per object; max_stdev: None (BandsContext's default per object), one number or [S].  An object that lacks a band
+    belongs to another set."""
+    _destroy = "carma_bandset_destroy"
+
+    def __init__(self, objects, p, q=0, lag_bounds=None, max_stdev=None, device=None):
+        objects = [list(o) for o in objects]
+        if not objects:
+            raise ValueError("BandsSetContext needs at least one object")
+        S, K = len(objects), len(objects[0])
+        for s, o in enumerate(objects):
+            if len(o) != K or K < 1:
+                raise ValueError("object %d has %d bands, object 0 has %d: the objects of a set share their bands" % (s, len(o), K))
+        ys, offsets, t_all, y_all, e_all = _concat_series([b for o in objects for b in o], "BandsSetContext", "band")
+        lb = np.zeros((S, 0, 2)) if lag_bounds is None else as_f64(lag_bounds)
+        if lb.size == (K - 1) * 2:
+            lb = np.broadcast_to(lb.reshape(1, K - 1, 2), (S, K - 1, 2))
+        if lb.size != S * (K - 1) * 2:
+            raise ValueError("lag_bounds must hold one (lo, hi) pair for each of the %d bands after the first, for all objects or "
+                             "for each of the %d objects" % (K - 1, S))
+        lb = as_f64(lb).reshape(S, K - 1, 2)
+        lo, hi = (as_f64(lb[:, :, 0]), as_f64(lb[:, :, 1])) if K > 1 else (None, None)
+        if max_stdev is None:
+            ms = as_f64([_default_max_stdev(ys[s * K]) for s in range(S)])
+        else:
+            ms = as_f64(np.broadcast_to(as_f64(max_stdev), (S,)))
+        self.device = _dev(device)
+        self._h = _created(lib.carma_bandset_create(ptr(t_all), ptr(y_all), ptr(e_all), _lptr(offsets), S, K, int(p), int(q),
+                                                    _optr(lo), _optr(hi), ptr(ms), self.device), "carma_bandset_create")
+        self.p, self.q = int(p), int(q)
+        self.nobjects = lib.carma_bandset_nobjects(self._h)
+        self.nbands = lib.carma_bandset_nbands(self._h)
+        self.dx = lib.carma_bandset_dim(self._h)
+        self.d = self.dx - 3 * (self.nbands - 1)
+        self.n = np.array([[lib.carma_bandset_n(self._h, s, b) for b in range(K)] for s in range(S)], dtype=np.int64)
+        self.lag_bounds = lb.copy()
+
+    def prior(self, s):
+        out = np.empty(3)
+        check(lib.carma_bandset_get_prior(self._h, int(s), ptr(out)), "carma_bandset_get_prior")
+        return tuple(out)
+
+    def _which(self, which, B):
+        """which (one index per row, or one for all) as the library takes it; the range is the library's check."""
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(which, dtype=np.int64), (B,)), dtype=np.int32)
+
+    def logdensity(self, thetas, which, ignore_prior=False, out=None):
+        """Log-density of thetas[i] on object which[i], one launch (carma_bandset_logdensity_batch).  out: a float64 array of at
+        least B entries to write the results to (the first B)."""
+        thetas, one = _theta_rows(thetas, self.dx)
+        B = thetas.shape[0]
+        w = self._which(which, B)
+        if out is None:
+            out = np.empty(B)
+        elif out.dtype != np.float64 or not out.flags.c_contiguous or out.size < B:
+            raise ValueError("out must be a contiguous float64 array of at least %d entries" % B)
+        check(lib.carma_bandset_logdensity_batch(self._h, ptr(thetas), _iptr(w), B, int(bool(ignore_prior)), ptr(out)),
+              "carma_bandset_logdensity_batch")
+        return float(out[0]) if one else out.reshape(-1)[:B]
+
+    def kernel_name(self):
+        return _kernel_name("carma_bandset_kernel_name", self._h)
+
+    def mle_batched(self, x0, which, lo=None, hi=None, fixed_lag=None, maxiter=2000, mem=8, ftol=2.220446049250313e-09, gtol=1e-5,
+                    fd_step=1e-6, ignore_prior=True):
+        """carma_bandset_mle_batched: BandsContext.mle_batched with start i on object which[i] and its own box lo[i], hi[i]
+        ([B, dx], or [dx] for every start; None or non-finite = unbounded; lags stay in the boxes of their object).  fixed_lag
+        [B, K - 1] as BandsContext.mle_batched.  Returns (x [B, dx], fun [B], nit [B], nfev [B], status [B])."""
+        x0, B = _mle_x0(x0, self.dx)
+        w = self._which(which, B)
+        lo = np.ascontiguousarray(np.broadcast_to(as_f64(-np.inf if lo is None else lo), x0.shape))
+        hi = np.ascontiguousarray(np.broadcast_to(as_f64(np.inf if hi is None else hi), x0.shape))
+        fl = None if fixed_lag is None else as_f64(fixed_lag).reshape(B, self.nbands - 1)
+        out, tail = _mle_tail(B, self.dx, maxiter, mem, ftol, gtol, fd_step, ignore_prior)
+        check(lib.carma_bandset_mle_batched(self._h, ptr(x0), w.ctypes.data_as(C.c_void_p), B, ptr(lo), ptr(hi), _optr(fl), *tail),
+              "carma_bandset_mle_batched")
+        return out
 
 
 def kfilter_car1(time, y, yerr, sigsqr, omega, device=None):

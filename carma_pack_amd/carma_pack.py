@@ -15,7 +15,7 @@ from scipy.optimize import minimize
 
 from . import _carmcmc as carmcmcLib
 
-__all__ = ["CarmaModel", "CarmaModelSet", "CarmaBandsModel", "CarmaBandsSample", "CarmaSample", "Car1Sample", "MCMCSample", "get_ar_roots", "power_spectrum",
+__all__ = ["CarmaModel", "CarmaModelSet", "CarmaBandsModel", "CarmaBandsSample", "CarmaBandsSet", "CarmaSample", "Car1Sample", "MCMCSample", "get_ar_roots", "power_spectrum",
            "carma_variance", "car1_process", "carma_process", "carma_process_batch", "car1_process_batch", "mle_to_model"]
 
 
@@ -1228,6 +1228,11 @@ class CarmaBandsModel(object):
         uniform in their boxes, log a_b = log(std y_b / std y_0), mu_b = mean y_b."""
         t0, y0, e0 = self.bands[0]
         _, st, bnds = CarmaModel(t0, y0, e0, p=self.p, q=self.q)._mle_problem(self.p, self.q, ntrials, seed)
+        return self._extend_starts(st, bnds, seed)
+
+    def _extend_starts(self, st, bnds, seed):
+        """_starts behind its CARMA part: st [ntrials, d] and the box bnds of band 0's CarmaModel."""
+        y0 = self.bands[0][1]
         rng = np.random.default_rng(seed)
         x0 = np.empty((st.shape[0], self.dx))
         x0[:, :self.d] = st
@@ -1376,6 +1381,179 @@ class CarmaBandsModel(object):
         t, y, e, band = (np.concatenate(a) for a in (ts, ys, es, bs))
         order = np.lexsort((band, t))
         return t[order], y[order], e[order], band[order]
+
+
+class CarmaBandsSet(object):
+    """Many multi-band objects, each fitted on its own: the AGN of a survey field seen in the same K filters, the systems of a
+    lens-monitoring campaign.  get_mle / lag_profile of every object with the starts of ALL objects optimised together in ONE
+    lock-step run on a set context (BandsSetContext, carma_bandset_mle_batched): every optimiser step is one launch for the whole
+    set, and an object's results are those of its own CarmaBandsModel, bit for bit.
+
+    objects: a list of S lists of K (time, y, ysig) -- every object in the same K bands (one that lacks a band belongs to
+    another set); each becomes a CarmaBandsModel (self.models).  lag_bounds: None (each object's default), one list of K - 1
+    (lo, hi) pairs for all objects, or a list of S such lists."""
+
+    def __init__(self, objects, p=1, q=0, lag_bounds=None):
+        objects = [list(o) for o in objects]
+        if not objects:
+            raise ValueError("CarmaBandsSet needs at least one object")
+        K = len(objects[0])
+        for s, o in enumerate(objects):
+            if len(o) != K:
+                raise ValueError("object %d has %d bands, object 0 has %d: the objects of a set share their bands" % (s, len(o), K))
+        S = len(objects)
+        if lag_bounds is None:
+            lbs = [None] * S
+        else:
+            lb = np.asarray(lag_bounds, dtype=float)
+            if lb.size == 2 * (K - 1) and lb.ndim <= 2:
+                lbs = [lb.reshape(K - 1, 2)] * S
+            elif lb.size == 2 * S * (K - 1):
+                lbs = list(lb.reshape(S, K - 1, 2))
+            else:
+                raise ValueError("lag_bounds must hold %d (lo, hi) pair(s), for all objects or for each of the %d objects"
+                                 % (K - 1, S))
+        self.models = []
+        for s, o in enumerate(objects):
+            try:
+                self.models.append(CarmaBandsModel(o, p=p, q=q, lag_bounds=lbs[s]))
+            except ValueError as ex:
+                raise ValueError("object %d: %s" % (s, ex))
+        self.p, self.q, self.K, self.nobjects = int(p), int(q), K, S
+        self.d, self.dx = self.models[0].d, self.models[0].dx
+        self._ctx = None
+        self.timing = {}
+
+    def context(self):
+        """The BandsSetContext over every object (created once; lag boxes and max_stdev as each CarmaBandsModel.context() has
+        them)."""
+        if self._ctx is None:
+            from ._lib import BandsSetContext
+            self._ctx = BandsSetContext([m.bands for m in self.models], self.p, self.q,
+                                        lag_bounds=np.stack([m.lag_bounds for m in self.models]),
+                                        max_stdev=[carmcmcLib._pop_max_stdev(m.bands[0][1]) for m in self.models])
+        return self._ctx
+
+    def _which(self, which, B):
+        w = np.broadcast_to(np.asarray(which, dtype=np.int64), (B,))
+        if B and (w.min() < 0 or w.max() >= self.nobjects):
+            raise ValueError("object index out of range [0, %d)" % self.nobjects)
+        return w
+
+    def _logdensity(self, theta, which, ignore_prior):
+        theta = np.asarray(theta, dtype=float)
+        rows = np.atleast_2d(theta)
+        w = self._which(which, rows.shape[0])
+        out = self.context().logdensity(rows, w, ignore_prior=ignore_prior)
+        return float(out[0]) if theta.ndim == 1 else out
+
+    def loglik(self, theta, which):
+        """CarmaBandsModel.loglik of theta[i] on object which[i] (one index per row, or one for all), every row in one launch."""
+        return self._logdensity(theta, which, self.p > 1)
+
+    def logpost(self, theta, which):
+        """CarmaBandsModel.logpost of theta[i] on object which[i], every row in one launch."""
+        return self._logdensity(theta, which, False)
+
+    def _boxes(self):
+        """(lo, hi) [S, dx]: each object's optimiser box, as CarmaBandsModel._starts gives it."""
+        lo, hi = np.empty((self.nobjects, self.dx)), np.empty((self.nobjects, self.dx))
+        for s, m in enumerate(self.models):
+            t0, y0, e0 = m.bands[0]
+            b = CarmaModel.__new__(CarmaModel)
+            b.time, b.y = t0, y0
+            _, lo[s], hi[s] = m._extend_starts(np.empty((0, self.d)), b._mle_bounds(self.p, self.q), None)
+        return lo, hi
+
+    def get_mle(self, ntrials=100, seed=None, starts=None, return_all=False):
+        """CarmaBandsModel.get_mle of every object.  starts None: each object's starts drawn exactly as its CarmaBandsModel
+        draws them (same seed); "set": the CARMA part of all objects' starts from ONE multi-series sampler run over the
+        objects' band 0 (CarmaModelSet's starts="set"; other draws than None gives), the band columns drawn as for None; else
+        an array [S, ntrials, dx].  All S x ntrials starts are then optimised in ONE lock-step run.  Returns a list of S results
+        (return_all: S lists of ntrials).  self.timing holds the seconds spent drawing starts and optimising."""
+        import time as _time
+        if isinstance(starts, str) and starts != "set":
+            raise ValueError("starts must be None, 'set' or an array [S, ntrials, dx], got %r" % starts)
+        S = self.nobjects
+        t0 = _time.perf_counter()
+        if starts is None:
+            starts = np.stack([m._starts(ntrials, seed)[0] for m in self.models])
+        elif isinstance(starts, str):
+            band0 = CarmaModelSet([m.bands[0] for m in self.models], p=self.p, q=self.q)
+            carma = band0._set_starts(self.p, self.q, ntrials, seed)
+            starts = np.stack([m._extend_starts(carma[s], b0._mle_bounds(self.p, self.q), seed)[0]
+                               for s, (m, b0) in enumerate(zip(self.models, band0.models))])
+        else:
+            starts = np.asarray(starts, dtype=float)
+            if starts.ndim != 3 or starts.shape[0] != S or starts.shape[2] != self.dx:
+                raise ValueError("starts must be [%d, ntrials, %d], got %r" % (S, self.dx, starts.shape))
+        lo, hi = self._boxes()
+        t1 = _time.perf_counter()
+        nt = starts.shape[1]
+        which = np.repeat(np.arange(S), nt)
+        xs, fs, nits, nfevs, sts = self.context().mle_batched(starts.reshape(S * nt, self.dx), which, lo[which], hi[which],
+                                                              ignore_prior=self.p > 1)
+        t2 = _time.perf_counter()
+        self.timing = {"starts_s": t1 - t0, "optimise_s": t2 - t1}
+        out = []
+        for s in range(S):
+            k = slice(s * nt, (s + 1) * nt)
+            res = CarmaBandsModel._results(xs[k], fs[k], nits[k], nfevs[k], sts[k])
+            if not return_all:
+                res = [r for r in res if np.isfinite(r.fun) and r.fun < 1e299] or res
+                res = min(res, key=lambda r: r.fun)
+            out.append(res)
+        return out
+
+    def _lag_grids(self, lags):
+        """lags of lag_profile -> S arrays [L_s, K - 1], each checked against its object's boxes.  One grid for all objects
+        ([L] for two bands, else [L, K - 1]), or a list (not an array) of S grids."""
+        K, S = self.K, self.nobjects
+        per = isinstance(lags, (list, tuple)) and len(lags) == S and all(np.ndim(g) >= (1 if K == 2 else 2) for g in lags)
+        grids = []
+        for s, g in enumerate(lags if per else [lags] * S):
+            g = np.asarray(g, dtype=float)
+            g = g.reshape(-1, 1) if K == 2 and g.ndim == 1 else np.atleast_2d(g)
+            if g.shape[1] != K - 1:
+                raise ValueError("lags must be [L] for two bands or [L, %d], for all objects or a list of one per object" % (K - 1))
+            lb = self.models[s].lag_bounds
+            if not np.all((g >= lb[:, 0]) & (g <= lb[:, 1])):
+                raise ValueError("object %d: every lag must lie inside its box (lag_bounds)" % s)
+            grids.append(g)
+        return grids
+
+    def lag_profile(self, lags, ntrials=8, seed=None):
+        """CarmaBandsModel.lag_profile of every object: `lags` is one grid for all objects or a list of one grid per object;
+        all S x L x ntrials starts run in ONE lock-step call.  Returns a list of S (loglik [L], x [L, dx])."""
+        import time as _time
+        if self.K < 2:
+            raise ValueError("lag_profile needs at least two bands")
+        grids = self._lag_grids(lags)
+        t0 = _time.perf_counter()
+        x0s, los, his, fixed, which = [], [], [], [], []
+        for s, (m, g) in enumerate(zip(self.models, grids)):
+            x0, lo, hi = m._starts(ntrials, seed)
+            nt, L = x0.shape[0], g.shape[0]
+            x0s.append(np.tile(x0, (L, 1)))
+            los.append(np.tile(lo, (L * nt, 1)))
+            his.append(np.tile(hi, (L * nt, 1)))
+            fixed.append(np.repeat(g, nt, axis=0))
+            which.append(np.full(L * nt, s))
+        t1 = _time.perf_counter()
+        xs, fs, nits, nfevs, sts = self.context().mle_batched(np.concatenate(x0s), np.concatenate(which), np.concatenate(los),
+                                                              np.concatenate(his), fixed_lag=np.concatenate(fixed),
+                                                              ignore_prior=self.p > 1)
+        t2 = _time.perf_counter()
+        self.timing = {"starts_s": t1 - t0, "optimise_s": t2 - t1}
+        out, k = [], 0
+        for g in grids:
+            L, nt = g.shape[0], x0s[len(out)].shape[0] // g.shape[0]
+            f = fs[k:k + L * nt]
+            f = np.where(np.isfinite(f), f, 1e300).reshape(L, nt)
+            best = f.argmin(axis=1)
+            out.append((-f[np.arange(L), best], xs[k:k + L * nt].reshape(L, nt, self.dx)[np.arange(L), best]))
+            k += L * nt
+        return out
 
 
 class CarmaBandsSample(MCMCSample):

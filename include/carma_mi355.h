@@ -242,6 +242,49 @@ int carma_bands_smooth(carma_bands* h, const double* theta /* [B][dx] */, int B,
                        int* invalid /* [B] or NULL */);
 
 /*
+ * MANY MULTI-BAND OBJECTS in one handle (no counterpart in the reference): the S objects of a survey field, each ONE process in
+ * the same K bands, fitted each on its own -- with the evaluations of all of them in one launch.  K, p and q are shared by the
+ * set, so dx is one number; an object that lacks a band belongs to another set.
+ *
+ * carma_bandset_create: offsets = [S K + 1]; band b of object s is time / y / yerr [offsets[s K + b], offsets[s K + b + 1]).
+ *   Every object is prepared exactly as carma_bands_create prepares its one object (sorted and de-duplicated per band, the time
+ *   origin the earliest time of ITS bands, the prior bounds from its band 0 and max_stdev[s]; max_stdev NULL: 10 sqrt(var(y))
+ *   of band 0 as given, 0 for a single datum): a set of one object holds the records and the prior of a carma_bands handle of
+ *   that object.  lag_lo / lag_hi = [S][K - 1] (may be NULL for one band).  The argument checks are those of carma_bands_create
+ *   per object, reported before any device work with the object's index in carma_last_error().  Returns NULL on error.
+ * carma_bandset_n: data of band b of object s after sort / dedup.  carma_bandset_get_prior: the bounds of object s.
+ * carma_bandset_logdensity_batch: B evaluations, theta = [B][dx], evaluation i on object[i], out = [B] in the caller's order.
+ *   One wave per workgroup on ONE object (k_logdens_carma_mband_ms): 64 evaluations of an object a wave, the longest object
+ *   first; an object with m evaluations in a call takes ceil(m / 64) waves, the last padded (a single evaluation: 63 pad
+ *   lanes).  An evaluation has the bits carma_bands_logdensity_batch gives it on a handle of its object alone, whatever else
+ *   the call carries.  An object[i] outside [0, S) is CARMA_EINVAL before any device work and names i; the handle stays
+ *   usable.  B = 0 is CARMA_OK.  The per-call device and pinned buffers belong to the handle and grow on demand.
+ * carma_bandset_mle_batched: carma_bands_mle_batched with start i on object[i] and its own box lo[i], hi[i] ([B][dx]; NULL or
+ *   non-finite entries = unbounded): the lag entries are cut to the lag boxes of object[i], and a start of which that leaves
+ *   nothing is CARMA_EINVAL and named (not with fixed_lag, which does not read them).  fixed_lag = [B][K - 1] or NULL, as
+ *   carma_bands_mle_batched.  Every optimiser step is ONE carma_bandset_logdensity_batch over the active starts of all objects; a
+ *   start's x, fun, nit and status are those of carma_bands_mle_batched on its object alone (nfev may differ: how many stencils
+ *   ride along with a line search depends on the number of starts in flight).
+ */
+typedef struct carma_bandset carma_bandset;
+carma_bandset* carma_bandset_create(const double* time, const double* y, const double* yerr, const long* offsets /* [S*K+1] */,
+                                    int nobjects, int nbands, int p, int q, const double* lag_lo /* [S][K-1] */,
+                                    const double* lag_hi /* [S][K-1] */, const double* max_stdev /* [S] or NULL */, int device);
+void carma_bandset_destroy(carma_bandset* h);
+int carma_bandset_nobjects(const carma_bandset* h);
+int carma_bandset_nbands(const carma_bandset* h);
+int carma_bandset_dim(const carma_bandset* h);          /* dx */
+int carma_bandset_n(const carma_bandset* h, int s, int b);
+int carma_bandset_get_prior(const carma_bandset* h, int s, double* out3 /* max_stdev, max_freq, min_freq */);
+int carma_bandset_logdensity_batch(carma_bandset* h, const double* theta /* [B][dx] */, const int* object /* [B] */, int B,
+                                   int ignore_prior, double* out /* [B] */);
+int carma_bandset_kernel_name(const carma_bandset* h, char* buf, int len);
+int carma_bandset_mle_batched(carma_bandset* h, const double* x0 /* [B][dx] */, const int* object /* [B] */, int B,
+                              const double* lo /* [B][dx] */, const double* hi /* [B][dx] */,
+                              const double* fixed_lag /* [B][K-1] or NULL */, int maxiter, int mem, double ftol, double gtol,
+                              double fd_step, int ignore_prior, double* x, double* fun, int* nit, int* nfev, int* status);
+
+/*
  * The parallel-tempering sampler of a MULTI-BAND fit (the carma_mpt_* set on a carma_bands handle, one run): nreplicas independent
  * ladders of ntemps chains on the extended vector [dx], one chain per lane -- the bookkeeping kernels of the large-ensemble
  * sampler (carma_pt_lane.hip; their wide, run-time-dimension form from dx = 17) around a log-density kernel that evaluates every
