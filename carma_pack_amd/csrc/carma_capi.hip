@@ -117,51 +117,6 @@ int hip_fail(hipError_t e, const char* what)
                                                                                                     : CARMA_EHIP;
 }
 
-// KalmanFilter::init (src/include/kfilter.hpp:43-76): sort by time when any dt < 0, then keep
-// sample 0 and every sample whose dt to its predecessor in the sorted series is non-zero.
-void sort_dedup(std::vector<double>& t, std::vector<double>& y, std::vector<double>& e)
-{
-    const size_t n = t.size();
-    bool need_sort = false;
-    for (size_t i = 1; i < n; i++) need_sort |= (t[i] - t[i - 1] < 0);
-    if (need_sort) {
-        std::vector<size_t> idx(n);
-        std::iota(idx.begin(), idx.end(), 0);
-        std::stable_sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return t[a] < t[b]; });
-        std::vector<double> t2(n), y2(n), e2(n);
-        for (size_t i = 0; i < n; i++) {
-            t2[i] = t[idx[i]];
-            y2[i] = y[idx[i]];
-            e2[i] = e[idx[i]];
-        }
-        t.swap(t2);
-        y.swap(y2);
-        e.swap(e2);
-    }
-    std::vector<char> keep(n, 1);
-    bool dup = false;
-    for (size_t i = 1; i < n; i++) {
-        if (t[i] - t[i - 1] == 0) {
-            keep[i] = 0;
-            dup = true;
-        }
-    }
-    if (dup) {
-        size_t m = 0;
-        for (size_t i = 0; i < n; i++) {
-            if (keep[i]) {
-                t[m] = t[i];
-                y[m] = y[i];
-                e[m] = e[i];
-                m++;
-            }
-        }
-        t.resize(m);
-        y.resize(m);
-        e.resize(m);
-    }
-}
-
 // series records {dt_k, y_k, yerr_k^2, t_k}
 std::vector<double> pack_series(const std::vector<double>& t, const std::vector<double>& y, const std::vector<double>& e)
 {
@@ -186,16 +141,6 @@ std::vector<double> pack_series(const std::vector<double>& t, const std::vector<
         s[5 * nt + k] = s[4 * k + 1];
     }
     return s;
-}
-
-// SetPrior (src/include/carpack.hpp:201-207) on a sorted, deduplicated series
-void set_prior_bounds(Prior& pr, const double* t, long n, double max_stdev)
-{
-    pr.max_stdev = max_stdev;
-    double dtmin = std::numeric_limits<double>::infinity();
-    for (long i = 1; i < n; i++) dtmin = std::min(dtmin, t[i] - t[i - 1]);
-    pr.max_freq = 1.0 / dtmin;
-    pr.min_freq = 1.0 / (*std::max_element(t, t + n) - *std::min_element(t, t + n));
 }
 
 int select_device(int device)
@@ -323,10 +268,7 @@ int carma_ctx_get_data(const carma_ctx* h, double* time, double* y, double* yerr
 int carma_ctx_get_prior(const carma_ctx* h, double* out3)
 {
     if (!h || !out3) return CARMA_EINVAL;
-    const Ctx* c = reinterpret_cast<const Ctx*>(h);
-    out3[0] = c->pr.max_stdev;
-    out3[1] = c->pr.max_freq;
-    out3[2] = c->pr.min_freq;
+    prior_out3(reinterpret_cast<const Ctx*>(h)->pr, out3);
     return CARMA_OK;
 }
 

@@ -13,6 +13,7 @@
 #include "carma_devbuf.h"
 #include "carma_launch.h"
 #include "carma_model_pack.h"
+#include "carma_prep.h"
 #include "carma_pt_state.h"
 #include "carma_types.h"
 
@@ -36,10 +37,9 @@ struct Ctx {
 };
 
 void set_error(const char* fmt, ...);
-// series preparation shared by carma_ctx_create and carma_mctx_create (carma_capi.hip)
-void sort_dedup(std::vector<double>& t, std::vector<double>& y, std::vector<double>& e);
+// series preparation shared by carma_ctx_create and carma_mctx_create: sort_dedup, set_prior_bounds and the default max_stdev
+// are host-only text in carma_prep.h; the packer is in carma_capi.hip
 std::vector<double> pack_series(const std::vector<double>& t, const std::vector<double>& y, const std::vector<double>& e);
-void set_prior_bounds(Prior& pr, const double* t, long n, double max_stdev);
 int hip_fail(hipError_t e, const char* what);
 int select_device(int device);
 // Enqueue `niter` iterations of the sampler kernel on `st` (no synchronisation).  thin > 0: save the coldest chain

@@ -23,10 +23,7 @@
 // Plain C++ over doubles: compiled for the host by the test harness as well (tests/emu/emu_mband.cpp).
 #pragma once
 #include "carma_lane.h"
-
-#include <algorithm>
-#include <limits>
-#include <vector>
+#include "carma_prep.h"   // mband_pack, the packer of the records this filter reads (host only)
 
 namespace carma {
 
@@ -42,6 +39,37 @@ struct MbandWork {
     const int* boff;                 // [K + 1], shared by the lanes: band b is records [boff[b], boff[b + 1]), the last a sentinel
     static constexpr size_t bytes(int K) { return (size_t)K * MBAND_LANES * (5 * sizeof(double) + sizeof(int)); }
 };
+
+// Dynamic LDS of a one-wave workgroup whose lanes merge `nstreams` streams (the K bands; the smoother's forward kernel adds the
+// requested times as stream K): the math tables, the work arrays [5][nstreams][64] doubles and [nstreams][64] ints, the band
+// offsets padded to 16 ints.  Every carve is a multiple of 16 bytes.  mband_lds_carve lays out what this counts.
+constexpr size_t mband_lds_bytes(int nstreams) { return sizeof(double) * MATH_TAB_N + MbandWork::bytes(nstreams) + sizeof(int) * 16; }
+
+#if defined(__HIPCC__)
+// THE carve of that block, for every kernel of the multi-band path: s_dyn is the base of dynamic LDS; boff = [.][K + 1] are the
+// band offsets in global memory, row obj those of the wave's object (0 where a launch has one object).  All lanes of the workgroup
+// call it: it fills the tables, copies the object's offsets and runs the barrier.  wk comes back offset by the lane; the return
+// value is the tables of the table-based exp / sincos (carma_math.h).
+CARMA_DEV const double* mband_lds_carve(double* s_dyn, int nstreams, int K, int lane, const int* boff, long obj, MbandWork& wk)
+{
+    const size_t KL = (size_t)nstreams * MBAND_LANES;
+    double* s_tab = s_dyn;
+    double* s_work = s_dyn + MATH_TAB_N;
+    int* s_pos = reinterpret_cast<int*>(s_work + 5 * KL);
+    int* s_boff = s_pos + KL;
+    math_tab_fill(s_tab);
+    if (lane <= K) s_boff[lane] = boff[obj * (K + 1) + lane];
+    __syncthreads();
+    wk.y = s_work + lane;
+    wk.e2 = s_work + KL + lane;
+    wk.a = s_work + 2 * KL + lane;
+    wk.mu = s_work + 3 * KL + lane;
+    wk.lag = s_work + 4 * KL + lane;
+    wk.pos = s_pos + lane;
+    wk.boff = s_boff;
+    return s_tab;
+}
+#endif
 
 // Reset + N merged Updates -> log-likelihood sum (no prior).  rec: {t, y, yerr^2, -} of all bands (MbandWork::boff);
 // wk.a / wk.mu / wk.lag are set by the caller, the heads by this function.
@@ -208,31 +236,6 @@ CARMA_DEV double logdensity_mband_lane(const double* thx, int q, int K, int N, c
     ll += log_prior(m.scale, pr.measerr_dof);
     if (m.sing || !m.valid || !ok) ll = -1.0 / 0.0;
     return ll;
-}
-
-// The record buffer of K bands (each sorted and de-duplicated already; n_b >= 1): {t - t0, y, yerr^2, 0} per datum, t0 the
-// earliest time of all bands, and a sentinel {+inf, 0, 1, 0} behind every band.  boff = [K + 1].  Host only.
-inline void mband_pack(const std::vector<std::vector<double>>& t, const std::vector<std::vector<double>>& y,
-                       const std::vector<std::vector<double>>& yerr, std::vector<double>& rec, std::vector<int>& boff)
-{
-    const int K = (int)t.size();
-    double t0 = std::numeric_limits<double>::infinity();
-    for (int b = 0; b < K; b++) t0 = std::min(t0, t[b][0]);
-    boff.assign(K + 1, 0);
-    rec.clear();
-    for (int b = 0; b < K; b++) {
-        for (size_t i = 0; i < t[b].size(); i++) {
-            rec.push_back(t[b][i] - t0);
-            rec.push_back(y[b][i]);
-            rec.push_back(yerr[b][i] * yerr[b][i]);
-            rec.push_back(0.0);
-        }
-        rec.push_back(std::numeric_limits<double>::infinity());
-        rec.push_back(0.0);
-        rec.push_back(1.0);
-        rec.push_back(0.0);
-        boff[b + 1] = (int)(rec.size() / 4);
-    }
 }
 
 }  // namespace carma

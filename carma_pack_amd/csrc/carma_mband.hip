@@ -25,35 +25,16 @@ namespace carma {
 
 static_assert(MBAND_KMAX == CARMA_KBANDS_MAX, "carma_mband.h and include/carma_mi355.h disagree on the number of bands");
 
-// dynamic LDS of a workgroup: tables, work arrays, band offsets (padded to 16 ints)
-static size_t mband_lds_bytes(int K) { return sizeof(double) * MATH_TAB_N + MbandWork::bytes(K) + sizeof(int) * 16; }
-
 template <int P>
 __global__ __launch_bounds__(64) void k_logdens_carma_mband(const double* __restrict__ theta, int dx, int q, int K, int N,
                                                            const double4* __restrict__ rec, const int* __restrict__ boff,
                                                            const double* __restrict__ lagbox, Prior pr, int B, int ignore_prior,
                                                            double* __restrict__ out)
 {
-    // all LDS is dynamic, every carve a multiple of 16 bytes: the tables of the table-based exp / sincos (carma_math.h), the work
-    // arrays [5][K][64] doubles and [K][64] ints, the band offsets
-    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];   // all LDS is dynamic (mband_lds_bytes)
     const int lane = threadIdx.x;
-    const size_t KL = (size_t)K * MBAND_LANES;
-    double* s_tab = s_dyn;
-    double* s_work = s_dyn + MATH_TAB_N;
-    int* s_pos = reinterpret_cast<int*>(s_work + 5 * KL);
-    int* s_boff = s_pos + KL;
-    math_tab_fill(s_tab);
-    if (lane <= K) s_boff[lane] = boff[lane];
-    __syncthreads();
     MbandWork wk;
-    wk.y = s_work + lane;
-    wk.e2 = s_work + KL + lane;
-    wk.a = s_work + 2 * KL + lane;
-    wk.mu = s_work + 3 * KL + lane;
-    wk.lag = s_work + 4 * KL + lane;
-    wk.pos = s_pos + lane;
-    wk.boff = s_boff;
+    const double* s_tab = mband_lds_carve(s_dyn, K, K, lane, boff, 0, wk);
     long e = (long)blockIdx.x * 64 + lane;
     const bool live = e < B;
     if (!live) e = (long)blockIdx.x * 64;                    // pad lanes recompute the wave's first evaluation and write nothing
@@ -91,9 +72,8 @@ carma_bands* carma_bands_create(const double* time, const double* y, const doubl
         set_error("carma_bands_create: %s", bad.c_str());
         return nullptr;
     }
-    // every band prepared as carma_ctx_create prepares a series (host only: all argument errors come before any device work)
+    // (host only: all argument errors come before any device work)
     const int K = nbands;
-    std::vector<std::vector<double>> ts(K), ys(K), es(K);
     Bctx* c = new Bctx();
     c->device = device;
     c->p = p;
@@ -101,43 +81,19 @@ carma_bands* carma_bands_create(const double* time, const double* y, const doubl
     c->d = 3 + p + q;
     c->K = K;
     c->dx = mband_dim(c->d, K);
-    c->n.resize(K);
-    for (int b = 0; b < K; b++) {
-        ts[b].assign(time + offsets[b], time + offsets[b + 1]);
-        ys[b].assign(y + offsets[b], y + offsets[b + 1]);
-        es[b].assign(yerr + offsets[b], yerr + offsets[b + 1]);
-        sort_dedup(ts[b], ys[b], es[b]);
-        c->n[b] = (int)ts[b].size();
-        c->N += c->n[b];
-    }
-    if (c->N < 2) {
+    if (!mband_prepare(time, y, yerr, offsets, K, lag_lo, lag_hi, &max_stdev, c->o)) {
         set_error("carma_bands_create: fewer than 2 data after the duplicate times of each band are dropped");
         delete c;
         return nullptr;
     }
-    c->pr.measerr_dof = 50.0;   // src/include/carpack.hpp:63
-    set_prior_bounds(c->pr, ts[0].data(), c->n[0], max_stdev);
-    for (int b = 0; b + 1 < K; b++) {
-        c->lagbox.push_back(lag_lo[b]);
-        c->lagbox.push_back(lag_hi[b]);
-    }
-    std::vector<double> rec;
-    mband_pack(ts, ys, es, rec, c->boff);
-    c->t0 = ts[0][0];                                         // (as mband_pack takes it: requested times get the same shift)
-    for (int b = 1; b < K; b++) c->t0 = std::min(c->t0, ts[b][0]);
-    c->ts = ts;
-    c->ys = ys;
     if (select_device(device) != CARMA_OK) {
         delete c;
         return nullptr;
     }
-    hipError_t e = c->d_rec.alloc(sizeof(double) * rec.size());
-    if (e == hipSuccess) e = hipMemcpy(c->d_rec.as<void>(), rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = c->d_boff.alloc(sizeof(int) * (K + 1));
-    if (e == hipSuccess) e = hipMemcpy(c->d_boff.as<void>(), c->boff.data(), sizeof(int) * (K + 1), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = c->d_lagbox.alloc(sizeof(double) * 2 * MBAND_KMAX);
-    if (e == hipSuccess && K > 1)
-        e = hipMemcpy(c->d_lagbox.as<void>(), c->lagbox.data(), sizeof(double) * c->lagbox.size(), hipMemcpyHostToDevice);
+    hipError_t e = to_device(c->d_rec, c->o.rec);
+    if (e == hipSuccess) e = to_device(c->d_boff, c->o.boff);
+    if (e == hipSuccess) e = to_device(c->d_lagbox, c->o.lagbox, sizeof(double) * 2 * MBAND_KMAX);
+    std::vector<double>().swap(c->o.rec);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         hip_fail(e, "carma_bands_create");
@@ -162,16 +118,13 @@ int carma_bands_nbands(const carma_bands* h) { return h ? reinterpret_cast<const
 int carma_bands_n(const carma_bands* h, int b)
 {
     if (!h || b < 0 || b >= reinterpret_cast<const Bctx*>(h)->K) return CARMA_EINVAL;
-    return reinterpret_cast<const Bctx*>(h)->n[b];
+    return reinterpret_cast<const Bctx*>(h)->o.n[b];
 }
 
 int carma_bands_get_prior(const carma_bands* h, double* out3)
 {
     if (!h || !out3) return CARMA_EINVAL;
-    const Prior& pr = reinterpret_cast<const Bctx*>(h)->pr;
-    out3[0] = pr.max_stdev;
-    out3[1] = pr.max_freq;
-    out3[2] = pr.min_freq;
+    prior_out3(reinterpret_cast<const Bctx*>(h)->o.pr, out3);
     return CARMA_OK;
 }
 
@@ -184,8 +137,8 @@ int carma_bands_logdensity_batch_dev(carma_bands* h, const double* d_theta, int 
     if (B == 0) return CARMA_OK;
     Bctx* c = reinterpret_cast<Bctx*>(h);
     (void)hipGetLastError();   // HIP's last-error is sticky: drop anything left by earlier calls
-    const hipError_t e = launch_logdens_mband(c->p, d_theta, B, c->dx, c->q, c->K, c->N, c->d_rec.as<const double4>(),
-                                              c->d_boff.as<const int>(), c->d_lagbox.as<const double>(), c->pr, ignore_prior, d_out,
+    const hipError_t e = launch_logdens_mband(c->p, d_theta, B, c->dx, c->q, c->K, c->o.N, c->d_rec.as<const double4>(),
+                                              c->d_boff.as<const int>(), c->d_lagbox.as<const double>(), c->o.pr, ignore_prior, d_out,
                                               reinterpret_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail(e, "carma_bands_logdensity_batch_dev: launch");
     return CARMA_OK;
@@ -227,23 +180,19 @@ int carma_bands_mle_batched(carma_bands* h, const double* x0, int B, const doubl
     }
     Bctx* c = reinterpret_cast<Bctx*>(h);
     const int K = c->K, d = c->d, dx = c->dx;
-    if (fixed_lag)
-        for (long i = 0; i < (long)B * (K - 1); i++)
-            if (!std::isfinite(fixed_lag[i])) {
-                set_error("carma_bands_mle_batched: fixed_lag of start %ld, band %ld is not finite", i / (K - 1), i % (K - 1) + 1);
-                return CARMA_EINVAL;
-            }
+    const long nf = mband_fixed_lag_bad(fixed_lag, B, K);
+    if (nf >= 0) {
+        set_error("carma_bands_mle_batched: fixed_lag of start %ld, band %ld is not finite", nf / (K - 1), nf % (K - 1) + 1);
+        return CARMA_EINVAL;
+    }
     const double inf = std::numeric_limits<double>::infinity();
     std::vector<double> lo, hi;
     fill_box(lo_in, dx, -inf, lo);
     fill_box(hi_in, dx, inf, hi);
-    for (int b = 1; b < K; b++) {                             // a lag never leaves its box, with or without the prior
-        lo[d + 3 * (b - 1)] = std::max(lo[d + 3 * (b - 1)], c->lagbox[2 * (b - 1)]);
-        hi[d + 3 * (b - 1)] = std::min(hi[d + 3 * (b - 1)], c->lagbox[2 * (b - 1) + 1]);
-        if (!fixed_lag && lo[d + 3 * (b - 1)] > hi[d + 3 * (b - 1)]) {
-            set_error("carma_bands_mle_batched: lo / hi leave nothing of the lag box of band %d", b);
-            return CARMA_EINVAL;
-        }
+    int band = 0;
+    if (mband_cut_boxes(lo.data(), hi.data(), nullptr, 1, d, K, c->o.lagbox.data(), fixed_lag != nullptr, &band) >= 0) {
+        set_error("carma_bands_mle_batched: lo / hi leave nothing of the lag box of band %d", band);
+        return CARMA_EINVAL;
     }
     auto dens = [h, ignore_prior](const double* thx, int npts, double* out) {
         return carma_bands_logdensity_batch(h, thx, npts, ignore_prior, out);

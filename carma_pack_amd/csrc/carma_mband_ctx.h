@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "carma_devbuf.h"
+#include "carma_mband_plan.h"
 #include "carma_pt_state.h"
 #include "carma_types.h"
 
@@ -19,18 +20,15 @@ struct BptState : PtEnsemble {
     DevBuf<double> d_box;             // ... on the device
 };
 
-// Multi-band context: the records of all bands in one buffer, a sentinel behind each band
+// Multi-band context: one prepared object (MbandObject, carma_mband_plan.h: n, N, boff, lagbox, pr, t0 and the bands' sorted
+// times and values, the sampler's starting values; its records are dropped once they are on the device) and its device state
 struct Bctx {
     int device = 0;
-    int p = 0, q = 0, d = 0, K = 0, dx = 0, N = 0;
-    std::vector<int> n, boff;         // [K] data per band, [K + 1] first record of a band (mband_pack)
-    std::vector<double> lagbox;       // [K - 1][2]
-    double t0 = 0.0;                  // the time origin mband_pack subtracted: the earliest time of all bands
-    Prior pr{};
-    DevMem d_rec, d_boff, d_lagbox;
+    int p = 0, q = 0, d = 0, K = 0, dx = 0;
+    MbandObject o;
+    DevMem d_rec, d_boff, d_lagbox;   // the records of all bands in one buffer, a sentinel behind each band
     DevMem d_theta, d_out;            // per-call buffers of the host-pointer entry point, grown on demand
     hipStream_t stream = nullptr;
-    std::vector<std::vector<double>> ts, ys;   // [K] the bands' times and values after sort / dedup (the sampler's starting values)
     std::unique_ptr<BptState> bpt;    // the sampler, after carma_bands_pt_create
 };
 

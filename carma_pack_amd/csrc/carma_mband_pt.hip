@@ -25,9 +25,6 @@ namespace carma {
 
 static_assert(MBAND_PT_DMAX == RAM_DMAX_WIDE, "carma_mband_pt_plan.h and carma_shape_plan.h disagree on the widest chain");
 
-// dynamic LDS of a workgroup, as k_logdens_carma_mband carves it: tables, work arrays, band offsets (padded to 16 ints)
-static size_t mband_chains_lds_bytes(int K) { return sizeof(double) * MATH_TAB_N + MbandWork::bytes(K) + sizeof(int) * 16; }
-
 // K1 of the bands sampler: ONE CHAIN PER LANE, chain gi = 64 blockIdx.x + threadIdx.x; thn = [nc][dx] chain-major (the proposals
 // the bookkeeping kernels write), ll = [nc].  The body is logdensity_mband_lane with the prior, as k_logdens_carma_mband calls it:
 // inside the box a chain gets that kernel's bits.  box = [2][K - 1][2], lo then hi of (log a_b, mu_b), or null: a chain with a
@@ -38,24 +35,10 @@ __global__ __launch_bounds__(64) void k_logdens_carma_mband_chains(const double*
                                                                   const double* __restrict__ lagbox, const double* __restrict__ box,
                                                                   Prior pr, long nc, double* __restrict__ ll)
 {
-    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];   // all LDS is dynamic (mband_lds_bytes)
     const int lane = threadIdx.x;
-    const size_t KL = (size_t)K * MBAND_LANES;
-    double* s_tab = s_dyn;
-    double* s_work = s_dyn + MATH_TAB_N;
-    int* s_pos = reinterpret_cast<int*>(s_work + 5 * KL);
-    int* s_boff = s_pos + KL;
-    math_tab_fill(s_tab);
-    if (lane <= K) s_boff[lane] = boff[lane];
-    __syncthreads();
     MbandWork wk;
-    wk.y = s_work + lane;
-    wk.e2 = s_work + KL + lane;
-    wk.a = s_work + 2 * KL + lane;
-    wk.mu = s_work + 3 * KL + lane;
-    wk.lag = s_work + 4 * KL + lane;
-    wk.pos = s_pos + lane;
-    wk.boff = s_boff;
+    const double* s_tab = mband_lds_carve(s_dyn, K, K, lane, boff, 0, wk);
     long gi = (long)blockIdx.x * 64 + lane;
     const bool live = gi < nc;
     if (!live) gi = (long)blockIdx.x * 64;
@@ -78,11 +61,11 @@ static hipError_t launch_logdens_mband_chains(const Bctx* c, const BptState* s, 
     (void)hipGetLastError();   // HIP's last-error is sticky: drop anything left by earlier calls
     if (nc <= 0) return hipSuccess;
     const dim3 grid((unsigned)((nc + 63) / 64)), block(64);
-    const size_t lds = mband_chains_lds_bytes(c->K);
+    const size_t lds = mband_lds_bytes(c->K);
     const double* box = s->has_box ? s->d_box.get() : nullptr;
     auto go = [&](auto P) {
-        hipLaunchKernelGGL((k_logdens_carma_mband_chains<decltype(P)::value>), grid, block, lds, st, thn, c->dx, c->q, c->K, c->N,
-                           c->d_rec.as<const double4>(), c->d_boff.as<const int>(), c->d_lagbox.as<const double>(), box, c->pr, nc, ll);
+        hipLaunchKernelGGL((k_logdens_carma_mband_chains<decltype(P)::value>), grid, block, lds, st, thn, c->dx, c->q, c->K, c->o.N,
+                           c->d_rec.as<const double4>(), c->d_boff.as<const int>(), c->d_lagbox.as<const double>(), box, c->o.pr, nc, ll);
         return hipGetLastError();
     };
     if (c->p == 1) return go(std::integral_constant<int, 1>{});   // (for_order starts at 2: CAR(1) is the generic body at P = 1 here)
@@ -112,7 +95,7 @@ static BptState* bpt_state(carma_bands* h, const char* who, bool need_start)
 static std::vector<BandView> band_views(const Bctx* c)
 {
     std::vector<BandView> v((size_t)c->K);
-    for (int b = 0; b < c->K; b++) v[b] = BandView{c->ts[b].data(), c->ys[b].data(), c->n[b]};
+    for (int b = 0; b < c->K; b++) v[b] = BandView{c->o.ts[b].data(), c->o.ys[b].data(), c->o.n[b]};
     return v;
 }
 
@@ -132,14 +115,14 @@ static int bpt_logdens_host(carma_bands* h, const BptState* s, const double* thx
 static int bpt_iterate(Bctx* c, long niter, int do_exchange, int thin, long* save_offset)
 {
     BptState* s = c->bpt.get();
-    const long chunk0 = mband_pt_chunk_iters(c->N);
+    const long chunk0 = mband_pt_chunk_iters(c->o.N);
     const PtLaneK1 k1 = [c, s](const double* thn, long nc, double* ll, hipStream_t st) {
         return launch_logdens_mband_chains(c, s, thn, nc, ll, st);
     };
     long left = niter;
     while (left > 0) {
         const long ch = pt_next_chunk(left, chunk0, thin);
-        const PtLaunch L = pt_ens_launch(s, c->dx, c->q, c->N, ch, do_exchange, thin, save_offset ? *save_offset : 0);
+        const PtLaunch L = pt_ens_launch(s, c->dx, c->q, c->o.N, ch, do_exchange, thin, save_offset ? *save_offset : 0);
         hipError_t e = launch_pt_lane_k1(c->p, L, s->d_scratch, k1, pt_ens_buffers(s), !s->factor_loaded, c->stream);
         if (e == hipSuccess) {
             s->factor_loaded = true;
@@ -179,7 +162,7 @@ int carma_bands_pt_create(carma_bands* h, int ntemps, int nreplicas, const doubl
         return CARMA_EINVAL;
     }
     Bctx* c = reinterpret_cast<Bctx*>(h);
-    const std::string bad = mband_pt_check_create(ntemps, nreplicas, adapt_iters, c->dx, c->K, c->n[0], band_lo, band_hi);
+    const std::string bad = mband_pt_check_create(ntemps, nreplicas, adapt_iters, c->dx, c->K, c->o.n[0], band_lo, band_hi);
     if (!bad.empty()) {
         set_error("carma_bands_pt_create: %s", bad.c_str());
         return CARMA_EINVAL;
@@ -274,7 +257,7 @@ int carma_bands_pt_start(carma_bands* h, const double* init)
     const int rc = find_starts(
         nchain, dx, theta.data(), lp.data(), done.data(),
         [&](size_t k, int round, double* out) {
-            mband_pt_draw_start(bands.data(), c->K, c->pr, c->p, c->q, c->lagbox.data(), s->seed, (uint64_t)k, round, out);
+            mband_pt_draw_start(bands.data(), c->K, c->o.pr, c->p, c->q, c->o.lagbox.data(), s->seed, (uint64_t)k, round, out);
         },
         [&](const double* cand, const size_t*, size_t m, double* out) { return bpt_logdens_host(h, s, cand, m, out); });
     if (rc != CARMA_OK) return rc;

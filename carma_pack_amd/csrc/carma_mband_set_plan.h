@@ -1,6 +1,7 @@
-// carma_mband_set_plan.h -- the host-only decisions of the calls on a SET of multi-band objects (carma_mband_set.hip): the layout
-// and the argument checks of carma_bandset_create, the per-start boxes of carma_bandset_mle_batched and the evaluator it hands to
-// mle_loop.  No HIP: the tests compile it stand-alone (tests/mbandset/mbandset_host.cpp).
+// carma_mband_set_plan.h -- the host-only decisions of the calls on a SET of multi-band objects (carma_mband_set.hip): the layout,
+// the argument checks and the preparation of carma_bandset_create and the evaluator carma_bandset_mle_batched hands to the
+// optimiser's driver (mband_mle_drive; the per-start boxes are mband_cut_boxes, both of carma_mband_plan.h).  No HIP: the tests
+// compile it stand-alone (tests/mbandset/mbandset_host.cpp).
 //
 // A set is S objects that share K, p and q, so dx is one number: object s is bands [s K, (s + 1) K) of one offset table
 // [S K + 1] over the caller's arrays.  An object that lacks a band belongs to another set.  The launch plan of the set's
@@ -58,24 +59,36 @@ inline std::string mbandset_check_create(const double* time, const double* y, co
     return "";
 }
 
-// The boxes of carma_bandset_mle_batched: lo / hi = [B][dx] (no NULLs, +-inf = unbounded); the lag entries of start i are cut to
-// the lag box of object[i] (lagbox = [S][K - 1][2]).  -1, or the first start of which nothing is left (band: which lag); with
-// fixed lags the lag entries are not read and nothing is refused.
-inline long mbandset_cut_boxes(double* lo, double* hi, const int* object, int B, int d, int K, const double* lagbox, bool fixed,
-                               int* band)
+// The prepared objects of a set side by side: object s as mband_prepare leaves it alone, its records from record off[s]
+struct MbandSet {
+    std::vector<int> n;               // [S][K] data per band after sort / dedup
+    std::vector<int> N;               // [S] data per object: the trip count of its waves
+    std::vector<int> boff;            // [S][K + 1] first record of a band, relative to the object's first
+    std::vector<long> off;            // [S] first record of object s: the running record count
+    std::vector<double> lagbox;       // [S][K - 1][2]
+    std::vector<Prior> pr;            // [S]
+    std::vector<double> rec;          // the records of all objects (an object keeps its own t0: the earliest time of ITS bands)
+};
+
+// mband_prepare of every object of a set that mbandset_check_create has passed (max_stdev = [S], or null: every object takes
+// the default).  -1, or the first object of which fewer than 2 data are left.
+inline int mbandset_prepare(const double* time, const double* y, const double* yerr, const long* offsets, int S, int K,
+                            const double* lag_lo, const double* lag_hi, const double* max_stdev, MbandSet& m)
 {
-    const int dx = mband_dim(d, K);
-    for (long i = 0; i < B; i++)
-        for (int b = 1; b < K; b++) {
-            const size_t j = (size_t)i * dx + d + 3 * (b - 1);
-            const double* box = lagbox + ((size_t)object[i] * (K - 1) + (b - 1)) * 2;
-            lo[j] = std::max(lo[j], box[0]);
-            hi[j] = std::min(hi[j], box[1]);
-            if (!fixed && lo[j] > hi[j]) {
-                if (band) *band = b;
-                return i;
-            }
-        }
+    m = MbandSet();
+    MbandObject o;
+    for (int s = 0; s < S; s++) {
+        if (!mband_prepare(time, y, yerr, offsets + (size_t)s * K, K, lag_lo + (size_t)s * (K - 1), lag_hi + (size_t)s * (K - 1),
+                           max_stdev ? max_stdev + s : nullptr, o))
+            return s;
+        m.off.push_back((long)(m.rec.size() / 4));
+        m.rec.insert(m.rec.end(), o.rec.begin(), o.rec.end());
+        m.n.insert(m.n.end(), o.n.begin(), o.n.end());
+        m.N.push_back(o.N);
+        m.boff.insert(m.boff.end(), o.boff.begin(), o.boff.end());
+        m.lagbox.insert(m.lagbox.end(), o.lagbox.begin(), o.lagbox.end());
+        m.pr.push_back(o.pr);
+    }
     return -1;
 }
 
@@ -109,30 +122,20 @@ struct EvalBandsSet : EvalBands<SetDens<Dens>> {
     }
 };
 
-// carma_bandset_mle_batched behind its argument checks: B starts x0 = [B][dx], start i on object[i] in its own box lo / hi =
-// [B][dx] (mbandset_cut_boxes done).  With fixed_lag = [B][K - 1] the lag entries of x0, lo and hi are not read and x_out
-// carries the fixed lags unchanged, as mband_mle_run.
+// mband_cut_boxes with a box per start: lo / hi = [B][dx], row i cut to the lag boxes of object[i]
+inline long mbandset_cut_boxes(double* lo, double* hi, const int* object, int B, int d, int K, const double* lagbox, bool fixed, int* band)
+{
+    return mband_cut_boxes(lo, hi, object, B, d, K, lagbox, fixed, band);
+}
+
+// mband_mle_drive on a set: start i on object[i] in its own box lo / hi = [B][dx] (mbandset_cut_boxes done)
 template <class Dens>
 int mbandset_mle_run(Dens dens, int d, int K, const double* x0, const int* object, int B, const double* lo, const double* hi,
                      const double* fixed_lag, int maxiter, int mem, double ftol, double gtol, double fd_step, double* x_out,
                      double* fun_out, int* nit, int* nfev, int* status)
 {
     EvalBandsSet<Dens> fun(dens, d, K, object, fixed_lag);
-    const int dx = mband_dim(d, K);
-    if (!fixed_lag)
-        return mle_loop(fun, dx, x0, B, lo, hi, (size_t)dx, maxiter, mem, ftol, gtol, fd_step, x_out, fun_out, nit, nfev, status);
-    const int dr = mband_free_dim(d, K, true);
-    std::vector<double> xr((size_t)B * dr), lor((size_t)B * dr), hir((size_t)B * dr), xo((size_t)B * dr);
-    for (int i = 0; i < B; i++) {
-        fun.reduce(x0 + (size_t)i * dx, &xr[(size_t)i * dr]);
-        fun.reduce(lo + (size_t)i * dx, &lor[(size_t)i * dr]);
-        fun.reduce(hi + (size_t)i * dx, &hir[(size_t)i * dr]);
-    }
-    const int rc = mle_loop(fun, dr, xr.data(), B, lor.data(), hir.data(), (size_t)dr, maxiter, mem, ftol, gtol, fd_step, xo.data(),
-                            fun_out, nit, nfev, status);
-    if (rc != CARMA_OK) return rc;
-    for (int i = 0; i < B; i++) fun.expand(&xo[(size_t)i * dr], fixed_lag + (size_t)i * (K - 1), x_out + (size_t)i * dx);
-    return CARMA_OK;
+    return mband_mle_drive(fun, d, K, x0, B, lo, hi, B, fixed_lag, maxiter, mem, ftol, gtol, fd_step, x_out, fun_out, nit, nfev, status);
 }
 
 }  // namespace carma

@@ -27,9 +27,6 @@
 
 namespace carma {
 
-// dynamic LDS of the forward kernel: tables, work arrays of K + 1 streams, band offsets (padded to 16 ints)
-static size_t mband_smooth_lds_bytes(int K) { return sizeof(double) * MATH_TAB_N + MbandWork::bytes(K + 1) + sizeof(int) * 16; }
-
 // theta = [rows][dx]; req = [M + 1] records of the requested times; sc: the chunk's scratch
 template <int P>
 __global__ __launch_bounds__(64) void k_smooth_mband_fwd(const double* __restrict__ theta, int dx, int q, int K, int N, int M, int bo,
@@ -38,24 +35,10 @@ __global__ __launch_bounds__(64) void k_smooth_mband_fwd(const double* __restric
                                                         long ps, size_t ws)
 {
     static_assert(mband_smooth_fields<P>() == 2 * P + P / 2 + 5, "record layout");
-    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];   // all LDS is dynamic (mband_lds_bytes of K + 1 streams)
     const int lane = threadIdx.x;
-    const size_t KL = (size_t)(K + 1) * MBAND_LANES;
-    double* s_tab = s_dyn;
-    double* s_work = s_dyn + MATH_TAB_N;
-    int* s_pos = reinterpret_cast<int*>(s_work + 5 * KL);
-    int* s_boff = s_pos + KL;
-    math_tab_fill(s_tab);
-    if (lane <= K) s_boff[lane] = boff[lane];
-    __syncthreads();
     MbandWork wk;
-    wk.y = s_work + lane;
-    wk.e2 = s_work + KL + lane;
-    wk.a = s_work + 2 * KL + lane;
-    wk.mu = s_work + 3 * KL + lane;
-    wk.lag = s_work + 4 * KL + lane;
-    wk.pos = s_pos + lane;
-    wk.boff = s_boff;
+    const double* s_tab = mband_lds_carve(s_dyn, K + 1, K, lane, boff, 0, wk);
     long e = (long)blockIdx.x * 64 + lane;
     if (e >= rows) e = (long)blockIdx.x * 64;                 // pad lanes walk the wave's first row, into slots of their own
     MbandSmoothLane<P> s;
@@ -99,7 +82,7 @@ struct MbandSmoothArgs {
 static hipError_t launch_smooth_mband(int p, const MbandSmoothArgs& a, hipStream_t st)
 {
     const dim3 grid((unsigned)((a.rows + 63) / 64)), block(64);
-    const size_t lds = mband_smooth_lds_bytes(a.K);
+    const size_t lds = mband_lds_bytes(a.K + 1);               // the requested times are stream K
     auto go = [&](auto P) {
         constexpr int PP = decltype(P)::value;
         static_assert(mband_smooth_fields<PP>() == mband_smooth_nfields(PP), "carma_mband_smooth.h and its planner disagree on the record");
@@ -124,14 +107,14 @@ extern "C" int carma_bands_smooth(carma_bands* h, const double* theta, int B, in
 {
     static const char* const who = "carma_bands_smooth";
     Bctx* c = reinterpret_cast<Bctx*>(h);
-    const std::string bad = mband_smooth_check(h != nullptr, c ? c->K : 0, c ? c->N : 0, theta, B, band, tout, M, mean, var, band_mean,
+    const std::string bad = mband_smooth_check(h != nullptr, c ? c->K : 0, c ? c->o.N : 0, theta, B, band, tout, M, mean, var, band_mean,
                                                band_var);
     if (!bad.empty()) {
         set_error("%s: %s", who, bad.c_str());
         return CARMA_EINVAL;
     }
-    const int ng = c->N + M;
-    const MbandSmoothTimes tm = mband_smooth_times(tout, M, c->t0);
+    const int ng = c->o.N + M;
+    const MbandSmoothTimes tm = mband_smooth_times(tout, M, c->o.t0);
     const long forced = tune_get(TUNE_MBAND_SMOOTH_CHUNK_ROWS);
     const MbandSmoothChunks ch = mband_smooth_chunks(c->p, ng, B, forced == TUNE_UNSET ? 0 : forced);
     const MbandSmoothStrides sd = mband_smooth_strides(c->p, ng);
@@ -158,7 +141,7 @@ extern "C" int carma_bands_smooth(carma_bands* h, const double* theta, int B, in
         a.dx = c->dx;
         a.q = c->q;
         a.K = c->K;
-        a.N = c->N;
+        a.N = c->o.N;
         a.M = M;
         a.bo = band;
         a.rows = (int)std::min<long>(ch.rows, B - r0);

@@ -312,7 +312,7 @@ int carma_mpredict(carma_mctx* h, const int* series, int M, const double* sigsqr
     }
     if (singular) std::fill(singular, singular + M, 0);
     if (T == 0) return CARMA_OK;
-    const MpredictPlan pl = mpredict_plan(p == 1 ? 0 : group_of(p), series, M, c->S, c->n.data(), toff, c->plan.b);
+    const MpredictPlan pl = mpredict_plan(p == 1 ? 0 : group_of(p), series, M, c->S, c->n.data(), toff, c->wb.plan.b);
     const long W = pl.W;
     hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");

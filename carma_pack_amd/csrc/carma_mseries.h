@@ -30,34 +30,11 @@ struct Mctx {
     const long* offs() const { return d_off.as<const long>(); }
     const int* ns() const { return d_n.as<const int>(); }
     const Prior* prs() const { return d_pr.as<const Prior>(); }
-    // per-call buffers, grown on demand: parameter vectors [cap_B][d], results [cap_B], plan [cap_W] + [cap_W][64]
-    DevMem d_theta, d_out, d_wser, d_eidx;
-    PinnedBuf<char> h_stage;          // pinned: the same four, in this order
-    long cap_B = 0, cap_W = 0;
+    WaveBatch wb;                     // per-call buffers and launch plan of carma_mlogdensity_batch (carma_devbuf.h)
     hipStream_t stream = nullptr;
-    MlogdensPlan plan;                // workspace of the launch plans (carma_mseries_plan.h), kept between calls
     // carma_mkfilter / carma_mpredict / carma_msmooth: parameters and times (doubles), plan tables (ints, longs), tiles, results,
     // flags; grown by DevMem::need
     DevMem k_par, k_int, k_long, k_tile, k_res, k_sing;
-
-    size_t stage_bytes(long B, long W) const { return sizeof(double) * (size_t)B * (d + 1) + sizeof(int) * (size_t)W * 65; }
-    int ensure(long B, long W)
-    {
-        if (B <= cap_B && W <= cap_W) return CARMA_OK;
-        const long nB = std::max(std::max(B, cap_B), 1024L), nW = std::max(std::max(W, cap_W), 64L);
-        for (DevMem* b : {&d_theta, &d_out, &d_wser, &d_eidx}) b->release();
-        h_stage.release();
-        cap_B = cap_W = 0;
-        hipError_t e = d_theta.alloc(sizeof(double) * (size_t)nB * d);
-        if (e == hipSuccess) e = d_out.alloc(sizeof(double) * (size_t)nB);
-        if (e == hipSuccess) e = d_wser.alloc(sizeof(int) * (size_t)nW);
-        if (e == hipSuccess) e = d_eidx.alloc(sizeof(int) * (size_t)nW * 64);
-        if (e == hipSuccess) e = h_stage.alloc(stage_bytes(nB, nW));
-        if (e != hipSuccess) return hip_fail(e, "carma_mlogdensity_batch: buffers");
-        cap_B = nB;
-        cap_W = nW;
-        return CARMA_OK;
-    }
 };
 
 // The items of carma_mkfilter / carma_mpredict / carma_msmooth -> par [M][3 p + 2] (p = 1: [M][3]: sigsqr, omega, mu) in the

@@ -143,16 +143,7 @@ carma_mctx* carma_mctx_create(const double* time, const double* y, const double*
             delete c;
             return nullptr;
         }
-        double ms = 0.0;
-        if (max_stdev) {
-            ms = max_stdev[s];
-        } else {                                              // 10 sqrt(var(y, ddof=1)) of the series as given (Context's default)
-            double mean = 0.0, ss = 0.0;
-            for (long k = a; k < b; k++) mean += y[k];
-            mean /= (double)(b - a);
-            for (long k = a; k < b; k++) ss += (y[k] - mean) * (y[k] - mean);
-            ms = 10.0 * std::sqrt(ss / (double)(b - a - 1));
-        }
+        const double ms = max_stdev ? max_stdev[s] : default_max_stdev(y + a, b - a);   // (of the series as given)
         c->pr[s].measerr_dof = 50.0;   // src/include/carpack.hpp:63
         set_prior_bounds(c->pr[s], ts.data(), ns, ms);
         packed[s] = pack_series(ts, ys, es);
@@ -175,14 +166,10 @@ carma_mctx* carma_mctx_create(const double* time, const double* y, const double*
         std::memcpy(&rec[(size_t)c->off[s] * 4], packed[s].data(), sizeof(double) * 4 * nr);
         std::vector<double>().swap(packed[s]);
     }
-    hipError_t e = c->d_rec.alloc(sizeof(double) * rec.size());
-    if (e == hipSuccess) e = hipMemcpy(c->d_rec.as<void>(), rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = c->d_off.alloc(sizeof(long) * nseries);
-    if (e == hipSuccess) e = hipMemcpy(c->d_off.as<void>(), c->off.data(), sizeof(long) * nseries, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = c->d_n.alloc(sizeof(int) * nseries);
-    if (e == hipSuccess) e = hipMemcpy(c->d_n.as<void>(), c->n.data(), sizeof(int) * nseries, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = c->d_pr.alloc(sizeof(Prior) * nseries);
-    if (e == hipSuccess) e = hipMemcpy(c->d_pr.as<void>(), c->pr.data(), sizeof(Prior) * nseries, hipMemcpyHostToDevice);
+    hipError_t e = to_device(c->d_rec, rec);
+    if (e == hipSuccess) e = to_device(c->d_off, c->off);
+    if (e == hipSuccess) e = to_device(c->d_n, c->n);
+    if (e == hipSuccess) e = to_device(c->d_pr, c->pr);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         hip_fail(e, "carma_mctx_create");
@@ -224,10 +211,7 @@ int carma_mctx_get_data(const carma_mctx* h, int s, double* time, double* y, dou
 int carma_mctx_get_prior(const carma_mctx* h, int s, double* out3)
 {
     if (!h || !out3 || s < 0 || s >= reinterpret_cast<const Mctx*>(h)->S) return CARMA_EINVAL;
-    const Prior& pr = reinterpret_cast<const Mctx*>(h)->pr[s];
-    out3[0] = pr.max_stdev;
-    out3[1] = pr.max_freq;
-    out3[2] = pr.min_freq;
+    prior_out3(reinterpret_cast<const Mctx*>(h)->pr[s], out3);
     return CARMA_OK;
 }
 
@@ -239,44 +223,18 @@ int carma_mlogdensity_batch(carma_mctx* h, const double* theta, const int* serie
     }
     if (B == 0) return CARMA_OK;
     Mctx* c = reinterpret_cast<Mctx*>(h);
-    const int S = c->S, d = c->d;
-    // launch plan (carma_mseries_plan.h), in the context's workspace: the waves are counted first, they size the staging block
-    MlogdensPlan& pl = c->plan;
-    const long bad = mlogdens_plan_count(series, B, S, c->n.data(), c->repdt.data(), pl);
-    if (bad >= 0) {
-        set_error("carma_mlogdensity_batch: series[%ld] = %d out of range (nseries = %d)", bad, series[bad], S);
-        return CARMA_EINVAL;
-    }
-    const long W = pl.W, w_plain = pl.w_plain;                // waves of the REPDT = false launch: the first w_plain
-    hipError_t e = hipSetDevice(c->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    int rc = c->ensure(B, W);
-    if (rc != CARMA_OK) return rc;
-    double* h_th = reinterpret_cast<double*>(c->h_stage.get());
-    double* h_out = h_th + (size_t)c->cap_B * d;
-    int* h_wser = reinterpret_cast<int*>(h_out + c->cap_B);
-    int* h_eidx = h_wser + c->cap_W;
-    std::memcpy(h_th, theta, sizeof(double) * (size_t)B * d);
-    mlogdens_plan_fill(pl, h_wser, h_eidx);                   // straight into the pinned block
-    hipStream_t st = c->stream;
-    double *d_theta = c->d_theta.as<double>(), *d_out = c->d_out.as<double>();
-    int *d_wser = c->d_wser.as<int>(), *d_eidx = c->d_eidx.as<int>();
-    e = hipMemcpyAsync(d_theta, h_th, sizeof(double) * (size_t)B * d, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_wser, h_wser, sizeof(int) * (size_t)W, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_eidx, h_eidx, sizeof(int) * (size_t)W * 64, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return hip_fail(e, "carma_mlogdensity_batch: H2D");
-    (void)hipGetLastError();   // HIP's last-error is sticky: drop anything left by earlier calls
-    e = launch_logdens_ms(c->p, false, d_theta, d, c->q, c->rec(), c->offs(), c->ns(), c->prs(), d_wser, d_eidx, w_plain, ignore_prior,
-                          d_out, st);
-    if (e == hipSuccess)
-        e = launch_logdens_ms(c->p, true, d_theta, d, c->q, c->rec(), c->offs(), c->ns(), c->prs(), d_wser + w_plain,
-                              d_eidx + (size_t)w_plain * 64, W - w_plain, ignore_prior, d_out, st);
-    if (e != hipSuccess) return hip_fail(e, "carma_mlogdensity_batch: launch");
-    e = hipMemcpyAsync(h_out, d_out, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return hip_fail(e, "carma_mlogdensity_batch: D2H");
-    std::memcpy(out, h_out, sizeof(double) * (size_t)B);
-    return CARMA_OK;
+    const int d = c->d;
+    // the plan's first w_plain waves are the REPDT = false launch, the others the REPDT = true one
+    auto enqueue = [&](const double* d_theta, const int* d_wser, const int* d_eidx, long W, long w_plain, double* d_out, hipStream_t st) {
+        hipError_t e = launch_logdens_ms(c->p, false, d_theta, d, c->q, c->rec(), c->offs(), c->ns(), c->prs(), d_wser, d_eidx, w_plain,
+                                         ignore_prior, d_out, st);
+        if (e == hipSuccess)
+            e = launch_logdens_ms(c->p, true, d_theta, d, c->q, c->rec(), c->offs(), c->ns(), c->prs(), d_wser + w_plain,
+                                  d_eidx + (size_t)w_plain * 64, W - w_plain, ignore_prior, d_out, st);
+        return e;
+    };
+    return wave_batch_run(c->wb, "carma_mlogdensity_batch", c->device, c->stream, theta, d, series, B, c->S, "series", "nseries",
+                          c->n.data(), c->repdt.data(), out, enqueue);
 }
 
 int carma_mlogdensity_kernel_name(const carma_mctx* h, char* buf, int len)

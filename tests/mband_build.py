@@ -42,8 +42,8 @@ def emu():
 
 @functools.lru_cache(None)
 def mle_host():
-    deps = [MLE_SRC, os.path.join(CSRC, "carma_mband_plan.h"), os.path.join(CSRC, "carma_mle_loop.h"),
-            os.path.join(ROOT, "include", "carma_mi355.h")]
+    deps = [MLE_SRC, os.path.join(ROOT, "include", "carma_mi355.h")] + [os.path.join(CSRC, f) for f in (
+        "carma_mband_plan.h", "carma_prep.h", "carma_types.h", "carma_mle_loop.h")]
     if _stale(MLE_SO, deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-I", CSRC, "-fPIC", "-shared",
                                "-o", MLE_SO, MLE_SRC])

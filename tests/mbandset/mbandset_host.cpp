@@ -2,7 +2,8 @@
 // (carma_pack_amd/csrc/carma_mband_set_plan.h) behind plain C entry points: the create checks, the per-start boxes, the lock-step
 // optimiser on a log-density that calls back into the test -- so that tests/test_mbandset_cpu.py can run it on an objective whose
 // answer is known and see the object of every point the evaluator hands on -- and the launch plan as carma_bandset_logdensity_batch
-// asks for it (carma_mseries_plan.h, lengths = the objects' N, one cadence class).  Host code, built by g++ (tests/mbandset_build.py).
+// asks for it (carma_mseries_plan.h, lengths = the objects' N, one cadence class) -- and the preparation of the objects, of the set
+// as a whole and of one object alone, as bytes.  Host code, built by g++ (tests/mbandset_build.py).
 #include "carma_mband_set_plan.h"
 
 typedef int (*mbandset_dens_cb)(const double* thx, const int* object, int npts, double* out, void* user);
@@ -44,4 +45,49 @@ extern "C" long mbandset_plan_host(const int* object, int B, int S, const int* N
     if (bad >= 0) return -2 - bad;
     if (pl.W <= cap_w) carma::mlogdens_plan_fill(pl, wave_obj, eval_idx);
     return pl.W;
+}
+
+// What the preparation leaves of object s, as bytes: its records, boff [K + 1], n [K], N, lagbox [K - 1][2] and the three prior
+// numbers carma_*_get_prior hands out.  alone = 0: the slice of the set prepared as a whole (mbandset_prepare; max_stdev = [S] or
+// null); alone = 1: the object prepared on its own, as carma_bands_create gets it -- its data rebased to offset 0, max_stdev[s]
+// or null (mband_prepare).  Returns the byte count, -1 when fewer than 2 data are left, -2 when buf is too small.
+extern "C" long mbandset_prepared_host(const double* time, const double* y, const double* yerr, const long* offsets, int S, int K,
+                                       const double* lag_lo, const double* lag_hi, const double* max_stdev, int s, int alone,
+                                       unsigned char* buf, long cap)
+{
+    std::vector<unsigned char> out;
+    auto put = [&out](const void* p, size_t bytes) {
+        const unsigned char* b = static_cast<const unsigned char*>(p);
+        out.insert(out.end(), b, b + bytes);
+    };
+    double pr3[3];
+    if (alone) {
+        long loc[CARMA_KBANDS_MAX + 1];
+        carma::mbandset_object_offsets(offsets, s, K, loc);
+        const long base = offsets[(size_t)s * K];
+        carma::MbandObject o;
+        if (!carma::mband_prepare(time + base, y + base, yerr + base, loc, K, lag_lo + (size_t)s * (K - 1), lag_hi + (size_t)s * (K - 1),
+                                  max_stdev ? max_stdev + s : nullptr, o))
+            return -1;
+        carma::prior_out3(o.pr, pr3);
+        put(o.rec.data(), sizeof(double) * o.rec.size());
+        put(o.boff.data(), sizeof(int) * o.boff.size());
+        put(o.n.data(), sizeof(int) * o.n.size());
+        put(&o.N, sizeof(int));
+        put(o.lagbox.data(), sizeof(double) * o.lagbox.size());
+    } else {
+        carma::MbandSet m;
+        if (carma::mbandset_prepare(time, y, yerr, offsets, S, K, lag_lo, lag_hi, max_stdev, m) >= 0) return -1;
+        const size_t r0 = (size_t)m.off[s] * 4, r1 = s + 1 < S ? (size_t)m.off[s + 1] * 4 : m.rec.size();
+        carma::prior_out3(m.pr[s], pr3);
+        put(m.rec.data() + r0, sizeof(double) * (r1 - r0));
+        put(m.boff.data() + (size_t)s * (K + 1), sizeof(int) * (K + 1));
+        put(m.n.data() + (size_t)s * K, sizeof(int) * K);
+        put(&m.N[s], sizeof(int));
+        put(m.lagbox.data() + (size_t)s * 2 * (K - 1), sizeof(double) * 2 * (K - 1));
+    }
+    put(pr3, sizeof(pr3));
+    if ((long)out.size() > cap) return -2;
+    std::memcpy(buf, out.data(), out.size());
+    return (long)out.size();
 }

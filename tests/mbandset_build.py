@@ -26,7 +26,8 @@ def _p(a, t=_dp):
 @functools.lru_cache(None)
 def host():
     deps = [SRC, os.path.join(ROOT, "include", "carma_mi355.h")] + [os.path.join(CSRC, f) for f in (
-        "carma_mband_set_plan.h", "carma_mband_plan.h", "carma_mle_loop.h", "carma_mseries_plan.h", "carma_smooth_plan.h")]
+        "carma_mband_set_plan.h", "carma_mband_plan.h", "carma_prep.h", "carma_types.h", "carma_mle_loop.h", "carma_mseries_plan.h",
+        "carma_smooth_plan.h")]
     if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-I", CSRC, "-fPIC", "-shared",
                                "-o", SO, SRC])
@@ -38,6 +39,8 @@ def host():
                                     C.c_double, C.c_double, C.c_double, _dp, _dp, _ip, _ip, _ip]
     L.mbandset_plan_host.argtypes = [_ip, C.c_int, C.c_int, _ip, _ip, _ip, C.c_long]
     L.mbandset_plan_host.restype = C.c_long
+    L.mbandset_prepared_host.argtypes = [_dp, _dp, _dp, _lp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, C.c_char_p, C.c_long]
+    L.mbandset_prepared_host.restype = C.c_long
     return L
 
 
@@ -58,6 +61,19 @@ def check_create(time, y, yerr, offsets, S, K, p, q, lag_lo, lag_hi):
     rc = host().mbandset_check_create_host(_p(time), _p(y), _p(yerr), _p(offsets, _lp), S, K, p, q, _p(lo), _p(hi), msg, 512)
     assert (rc == 0) == (msg.value == b"")
     return msg.value.decode()
+
+
+def prepared(objects, lag_lo, lag_hi, max_stdev, s, alone):
+    """The bytes the preparation leaves of object s (records, boff, n, N, lagbox, the three prior numbers): its slice of the set
+    prepared as a whole, or -- alone -- the object prepared on its own as carma_bands_create gets it.  max_stdev: [S] or None."""
+    t, y, e, off = flat_set(objects)
+    S, K = len(objects), len(objects[0])
+    lo, hi = (np.ascontiguousarray(a, dtype=float).reshape(S, K - 1) for a in (lag_lo, lag_hi))
+    ms = None if max_stdev is None else np.ascontiguousarray(max_stdev, dtype=float).reshape(S)
+    buf = C.create_string_buffer(1 << 16)
+    nb = host().mbandset_prepared_host(_p(t), _p(y), _p(e), _p(off, _lp), S, K, _p(lo), _p(hi), _p(ms), s, int(alone), buf, len(buf))
+    assert nb > 0, nb
+    return buf.raw[:nb]
 
 
 def cut_boxes(lo, hi, which, d, K, lagbox, fixed=False):

@@ -16,7 +16,7 @@ CSRC = os.path.join(ROOT, "carma_pack_amd", "csrc")
 MAIN_SRC = os.path.join(HERE, "hostmem", "hostmem_main.cpp")
 MAIN_EXE = os.path.join(HERE, "hostmem", "hostmem_main")
 DEPS = [MAIN_SRC, os.path.join(CSRC, "carma_devbuf.h"), os.path.join(CSRC, "carma_model_pack.h"),
-        os.path.join(CSRC, "carma_pt_state.h"),
+        os.path.join(CSRC, "carma_pt_state.h"), os.path.join(CSRC, "carma_mseries_plan.h"), os.path.join(CSRC, "carma_smooth_plan.h"),
         os.path.join(ROOT, "include", "carma_mi355.h")]
 FLAGS = ["-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I", CSRC]
 

@@ -73,6 +73,37 @@ def test_one_datum_in_all_is_refused_per_object():
     assert MB.check_create(t, y, e, off, 2, 1, 1, 0, None, None) == "object 1: need at least 2 data in all"
 
 
+# ---- the preparation: the set's slice of an object is the object's own preparation, byte for byte ---------------------------
+def test_set_prepares_every_object_as_the_single_object_call_does():
+    """S = 3 objects of K = 3 bands of 7, 1 and 12 data; one band is given unsorted, one has a repeated time.  The records from
+    off[s], boff, n, N, lagbox and the three prior numbers of object s in the set equal, as bytes, what the object gives when it
+    is prepared alone.  The set's C ABI takes max_stdev for every object or for none, so "one object given, the others on the
+    default" is checked as both: every object once with max_stdev given and once on the default."""
+    rng = np.random.default_rng(23)
+    objs = [[R._band(rng, n, t0=0.25 * b + s) for b, n in enumerate((7, 1, 12))] for s in range(3)]
+    t, y, e = objs[1][2]
+    perm = rng.permutation(12)
+    assert not np.all(np.diff(t[perm]) > 0)
+    objs[1][2] = (t[perm], y[perm], e[perm])                  # object 1, band 2: unsorted
+    t, y, e = (a.copy() for a in objs[2][0])
+    t[4] = t[3]                                               # object 2, band 0: a repeated time (6 data are left of 7)
+    objs[2][0] = (t, y, e)
+    lo = np.array([[-1.0, -2.0], [-0.5, 0.0], [-3.0, 1.0]])
+    hi = np.array([[1.0, 2.0], [0.5, 4.0], [3.0, 1.5]])
+    for ms in (None, np.array([3.5, 0.75, 12.0])):
+        got = [MB.prepared(objs, lo, hi, ms, s, alone=False) for s in range(3)]
+        for s in range(3):
+            assert got[s] == MB.prepared(objs, lo, hi, ms, s, alone=True), (s, ms)
+        assert len(set(got)) == 3                             # ... and the objects differ
+        # the layout of the bytes: 7 + 1 + 12 data (6 + 1 + 12 with the repeated time) and 3 sentinels, 4 doubles a record
+        for s, ndata in enumerate((20, 20, 19)):
+            assert len(got[s]) == 8 * 4 * (ndata + 3) + 4 * (4 + 3 + 1) + 8 * 4 + 8 * 3
+            assert ms is None or np.frombuffer(got[s][-24:])[0] == ms[s]                 # max_stdev: the first prior number
+    # the default of an object is 10 sqrt(var(y, ddof=1)) of its band 0 as given (to rounding: the loops' order is the library's)
+    dflt = [np.frombuffer(MB.prepared(objs, lo, hi, None, s, alone=True)[-24:])[0] for s in range(3)]
+    np.testing.assert_allclose(dflt, [10.0 * np.std(o[0][1], ddof=1) for o in objs], rtol=1e-13)
+
+
 # ---- the boxes of carma_bandset_mle_batched -----------------------------------------------------------------------------------
 def test_boxes_are_cut_to_the_lag_boxes_of_each_starts_object():
     d, K = 4, 3
