@@ -82,6 +82,7 @@ SIGNATURES = {
     "carma_bandset_logdensity_batch": (_I, [_V, _dp, _ip, _I, _I, _dp]),
     "carma_bandset_kernel_name": (_I, [_V, _S, _I]),
     "carma_bandset_mle_batched": (_I, [_V, _V, _V, _I, _V, _V, _V] + _MLE_TAIL),
+    "carma_bandset_smooth": (_I, [_V, _dp, _ip, _ip, _I, _dp, _lp, _dp, _dp, _ip]),
     "carma_bands_pt_default_box": (_I, [_V, _dp, _dp]),
     "carma_bands_pt_create": (_I, [_V, _I, _I, _dp, _I, _U64, _dp, _dp]),
     "carma_bands_pt_start": (_I, [_V, _dp]),
@@ -164,8 +165,8 @@ SIGNATURES = {
     "carma_comm_size": (_I, [_V]),
 }
 EXPORTS = list(SIGNATURES)
-# (the switches tune_reset puts back; carma_tune_set knows further keys, "MBAND_SMOOTH_CHUNK_ROWS" of BandsContext.smooth among
-# them, which a caller moves and resets itself)
+# (the switches tune_reset puts back; carma_tune_set knows further keys, "MBAND_SMOOTH_CHUNK_ROWS" of BandsContext.smooth and
+# "MBANDSET_SMOOTH_CHUNK_WAVES" of BandsSetContext.smooth among them, which a caller moves and resets itself)
 TUNE_SWITCHES = ("WIN_ROWS", "WIN2_EVALS", "PT_ROW_WIN", "CSIM_CHUNK_PATHS", "SMOOTH_CHUNK_MODELS")
 
 
@@ -1168,6 +1169,36 @@ class BandsSetContext(_Handle):
         check(lib.carma_bandset_mle_batched(self._h, ptr(x0), w.ctypes.data_as(C.c_void_p), B, ptr(lo), ptr(hi), _optr(fl), *tail),
               "carma_bandset_mle_batched")
         return out
+
+    def smooth(self, thetas, which, band, times, return_invalid=False):
+        """carma_bandset_smooth: BandsContext.smooth of B rows on any objects of the set in ONE call: row i is the curve of band
+        band[i] of object which[i] under thetas[i] ([B, dx]) at the observer times times[i] (any order, repeats allowed, at
+        least one).  which, band: one index per row, or one for all rows; times: a list of B arrays, or one array for all rows.
+        Returns (means, vars): lists of B arrays shaped as times[i] -- a row has the bits BandsContext.smooth gives it on a
+        context of its object alone.  An invalid row (repeated AR root, non-finite lag, scale or offset) is NaN and raises
+        CarmaError -- or, with return_invalid, is flagged in a third return value, a bool array [B]."""
+        thetas, _ = _theta_rows(thetas, self.dx)
+        B = thetas.shape[0]
+        w, bo = self._which(which, B), self._which(band, B)
+        if np.ndim(times if isinstance(times, np.ndarray) else 0) > 1 or (isinstance(times, (list, tuple)) and len(times)
+                                                                           and np.ndim(times[0]) > 0):
+            times = [as_f64(np.atleast_1d(t)).ravel() for t in times]
+            if len(times) != B:
+                raise ValueError("BandsSetContext.smooth: times must hold one array per row (%d), got %d" % (B, len(times)))
+        else:
+            times = [as_f64(np.atleast_1d(times)).ravel()] * B
+        toff = _offsets([t.size for t in times])
+        tp = as_f64(np.concatenate(times)) if toff[-1] else np.zeros(1)
+        mean, var = np.empty(max(int(toff[-1]), 1)), np.empty(max(int(toff[-1]), 1))
+        inv = np.zeros(B, dtype=np.int32)
+        check(lib.carma_bandset_smooth(self._h, ptr(thetas), _iptr(w), _iptr(bo), B, ptr(tp), _lptr(toff), ptr(mean), ptr(var),
+                                       _iptr(inv)), "carma_bandset_smooth")
+        if return_invalid:
+            return _split(mean, toff), _split(var, toff), inv.astype(bool)
+        if inv.any():
+            raise CarmaError("BandsSetContext.smooth: a repeated AR root or a non-finite lag, scale or offset for row(s) %s"
+                             % np.flatnonzero(inv)[:8].tolist())
+        return _split(mean, toff), _split(var, toff)
 
 
 def kfilter_car1(time, y, yerr, sigsqr, omega, device=None):

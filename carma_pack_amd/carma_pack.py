@@ -1470,7 +1470,8 @@ class CarmaBandsSet(object):
         draws them (same seed); "set": the CARMA part of all objects' starts from ONE multi-series sampler run over the
         objects' band 0 (CarmaModelSet's starts="set"; other draws than None gives), the band columns drawn as for None; else
         an array [S, ntrials, dx].  All S x ntrials starts are then optimised in ONE lock-step run.  Returns a list of S results
-        (return_all: S lists of ntrials).  self.timing holds the seconds spent drawing starts and optimising."""
+        (return_all: S lists of ntrials).  self.timing holds the seconds spent drawing starts and optimising.  smooth() takes
+        the list this returns and draws every object's interpolated light curves in its K bands, in one call."""
         import time as _time
         if isinstance(starts, str) and starts != "set":
             raise ValueError("starts must be None, 'set' or an array [S, ntrials, dx], got %r" % starts)
@@ -1553,6 +1554,51 @@ class CarmaBandsSet(object):
             best = f.argmin(axis=1)
             out.append((-f[np.arange(L), best], xs[k:k + L * nt].reshape(L, nt, self.dx)[np.arange(L), best]))
             k += L * nt
+        return out
+
+    def smooth(self, thetas, time, band=None):
+        """CarmaBandsModel.smooth of every object, in ONE call for all objects, bands and rows (carma_bandset_smooth).  thetas: a
+        list of S entries, one per object: a vector [dx], an array [B_s, dx] or an object with .x (what get_mle returns); time:
+        one array for all objects or a list of S arrays; band: None (all K bands), an int or a list of bands.  Returns a list of
+        S (mean, var), arrays [nbands, B_s, M_s] -- without the row axis where the entry was a single vector, without the band
+        axis where band is an int; every entry has the bits of models[s].smooth(theta, time, band=b).  ValueError on an invalid
+        row, named by object and row."""
+        S = self.nobjects
+        thetas = list(thetas)
+        if len(thetas) != S:
+            raise ValueError("thetas must hold one entry per object (%d), got %d" % (S, len(thetas)))
+        per = isinstance(time, (list, tuple)) and len(time) == S and all(np.ndim(t) > 0 for t in time)
+        times = [np.asarray(t, dtype=float).ravel() for t in (time if per else [time] * S)]
+        bands = list(range(self.K)) if band is None else [int(b) for b in np.atleast_1d(band)]
+        rows, which, bo, tl, ones = [], [], [], [], []
+        for s, th in enumerate(thetas):
+            x = np.asarray(getattr(th, "x", th), dtype=float)
+            if x.ndim > 2 or x.shape[-1] != self.dx:
+                raise ValueError("object %d: thetas must be [%d] or [B, %d], got %r" % (s, self.dx, self.dx, x.shape))
+            ones.append(x.ndim == 1)
+            x = x.reshape(-1, self.dx)
+            for b in bands:
+                rows.append(x)
+                which += [s] * x.shape[0]
+                bo += [b] * x.shape[0]
+                tl += [times[s]] * x.shape[0]
+        means, variances, inv = self.context().smooth(np.concatenate(rows), which, bo, tl, return_invalid=True)
+        if inv.any():
+            i = int(np.argmax(inv))
+            s, n = which[i], rows[which[i] * len(bands)].shape[0]
+            raise ValueError("CarmaBandsSet.smooth: object %d, row %d has a repeated AR root or a non-finite lag, scale or offset"
+                             % (s, (i - which.index(s)) % n))
+        out, k = [], 0
+        for s in range(S):
+            n = rows[s * len(bands)].shape[0]
+            shape = (len(bands), n, times[s].size)
+            pair = [np.array(a[k:k + len(bands) * n]).reshape(shape) for a in (means, variances)]
+            k += len(bands) * n
+            if ones[s]:
+                pair = [a[:, 0] for a in pair]
+            if band is not None and np.ndim(band) == 0:
+                pair = [a[0] for a in pair]
+            out.append(tuple(pair))
         return out
 
 

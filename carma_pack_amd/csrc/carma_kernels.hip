@@ -715,7 +715,8 @@ static const TuneEntry TUNE_TAB[TUNE_COUNT] = {
     {"CARMA_TUNE_LANE_MIN", 11, TP_DEC},          {"CARMA_TUNE_LPC_MIN", 11, TP_DEC},             {"CARMA_TUNE_LPC_MAX", 11, TP_DEC},
     {"CARMA_TUNE_LPC_ROT", 11, TP_DEC},           {"CARMA_TUNE_CAR1_SCAN_MAX", 11, TP_DEC},       {"CARMA_TUNE_PT_ROW_WGS_PER_CU", 11, TP_DEC},
     {"CARMA_TUNE_PT_ROW_ROT", 11, TP_HEX},        {"CARMA_TUNE_PT_ROW_XCD_MAP", 11, TP_DEC},      {"CARMA_PT_PLAIN", 6, TP_FLAG},
-    {"CARMA_TUNE_MBAND_SMOOTH_CHUNK_ROWS", 11, TP_DEC}, {"CARMA_TUNE_PT_RAM_WIDE_MIN", 11, TP_DEC}};
+    {"CARMA_TUNE_MBAND_SMOOTH_CHUNK_ROWS", 11, TP_DEC}, {"CARMA_TUNE_PT_RAM_WIDE_MIN", 11, TP_DEC},
+    {"CARMA_TUNE_MBANDSET_SMOOTH_CHUNK_WAVES", 11, TP_DEC}};
 static std::atomic<long> g_tune[TUNE_COUNT];
 static std::atomic<int> g_tune_init{0};
 static void tune_init()

@@ -41,14 +41,15 @@ int device_cus();
 // CARMA_TUNE_CSIM_CHUNK_PATHS: paths per chunk of the conditional simulation (carma_csim.hip; 0 or unset: as many as its scratch cap holds).
 // CARMA_TUNE_SMOOTH_CHUNK_MODELS: models per chunk of the one-pass smoother (carma_smooth.hip; 0 or unset: as many whole waves as its scratch cap holds).
 // CARMA_TUNE_MBAND_SMOOTH_CHUNK_ROWS: parameter vectors per chunk of carma_bands_smooth (carma_mband_smooth.hip; 0 or unset: as many whole waves as its scratch cap holds).
+// CARMA_TUNE_MBANDSET_SMOOTH_CHUNK_WAVES: waves per chunk of carma_bandset_smooth (carma_mband_set_smooth.hip; 0 or unset: as many as its scratch cap holds).
 enum {
     TUNE_WIN_ROWS = 0, TUNE_WIN2_EVALS, TUNE_PT_ROW_WIN, TUNE_CSIM_CHUNK_PATHS, TUNE_SMOOTH_CHUNK_MODELS,
     TUNE_P3L_ROWS, TUNE_LANE_MIN, TUNE_LPC_MIN, TUNE_LPC_MAX, TUNE_LPC_ROT, TUNE_CAR1_SCAN_MAX,
     TUNE_PT_ROW_WGS_PER_CU, TUNE_PT_ROW_ROT, TUNE_PT_ROW_XCD_MAP, TUNE_PT_PLAIN, TUNE_MBAND_SMOOTH_CHUNK_ROWS,
-    TUNE_PT_RAM_WIDE_MIN, TUNE_COUNT
+    TUNE_PT_RAM_WIDE_MIN, TUNE_MBANDSET_SMOOTH_CHUNK_WAVES, TUNE_COUNT
 };
 long tune_get(int which);                    // TUNE_UNSET or the override
-int tune_set(const char* name, long value);  // "WIN_ROWS" / "WIN2_EVALS" / "PT_ROW_WIN" / "CSIM_CHUNK_PATHS" / "SMOOTH_CHUNK_MODELS" / "MBAND_SMOOTH_CHUNK_ROWS" (or the full CARMA_TUNE_ name); 0 or -1
+int tune_set(const char* name, long value);  // "WIN_ROWS" / "WIN2_EVALS" / "PT_ROW_WIN" / "CSIM_CHUNK_PATHS" / "SMOOTH_CHUNK_MODELS" / "MBAND_SMOOTH_CHUNK_ROWS" / "MBANDSET_SMOOTH_CHUNK_WAVES" (or the full CARMA_TUNE_ name); 0 or -1
 ShapeSwitches shape_switches();              // the planners' switches (carma_shape_plan.h) as the table holds them now
 
 // k_smooth_band (carma_smooth.hip) on `st`: the moment-matched equal-weight mixture over the rows of mean / var = [K][M] whose flag

@@ -29,21 +29,9 @@
 #include "carma_lane.h"
 #include "carma_mband.h"
 #include "carma_host.h"
-#include "carma_mband_set_plan.h"
+#include "carma_mband_set_ctx.h"
 
 namespace carma {
-
-// A set of multi-band objects: the prepared objects side by side (MbandSet, carma_mband_set_plan.h; its records are dropped once
-// they are on the device) and the set's device state
-struct BSctx {
-    int device = 0;
-    int p = 0, q = 0, d = 0, K = 0, dx = 0, S = 0;
-    MbandSet m;
-    std::vector<char> plain;          // [S] zeros: the launch plan's cadence classes, of which a set has one
-    DevMem d_rec, d_off, d_boff, d_N, d_lagbox, d_pr;
-    WaveBatch wb;                     // per-call buffers and launch plan of carma_bandset_logdensity_batch (carma_devbuf.h)
-    hipStream_t stream = nullptr;
-};
 
 template <int P>
 __global__ __launch_bounds__(64) void k_logdens_carma_mband_ms(const double* __restrict__ theta, int dx, int q, int K,

@@ -67,6 +67,7 @@ struct MbandSet {
     std::vector<long> off;            // [S] first record of object s: the running record count
     std::vector<double> lagbox;       // [S][K - 1][2]
     std::vector<Prior> pr;            // [S]
+    std::vector<double> t0;           // [S] the time origin of object s (MbandObject::t0): what its requested times are shifted by
     std::vector<double> rec;          // the records of all objects (an object keeps its own t0: the earliest time of ITS bands)
 };
 
@@ -88,6 +89,7 @@ inline int mbandset_prepare(const double* time, const double* y, const double* y
         m.boff.insert(m.boff.end(), o.boff.begin(), o.boff.end());
         m.lagbox.insert(m.lagbox.end(), o.lagbox.begin(), o.lagbox.end());
         m.pr.push_back(o.pr);
+        m.t0.push_back(o.t0);
     }
     return -1;
 }

@@ -111,6 +111,7 @@ int carma_logdensity_kernel_name(const carma_ctx* h, int B, char* buf, int len);
  * "CSIM_CHUNK_PATHS": paths per chunk of carma_simulate_cond_* (0: as many as its scratch cap holds; results do not depend on it).
  * "SMOOTH_CHUNK_MODELS": models per chunk of carma_smooth_* (0: as many whole waves as its scratch cap holds; results do not depend on it).
  * "MBAND_SMOOTH_CHUNK_ROWS": parameter vectors per chunk of carma_bands_smooth (0: as many whole waves as its scratch cap holds; results do not depend on it).
+ * "MBANDSET_SMOOTH_CHUNK_WAVES": waves per chunk of carma_bandset_smooth (0: as many as its scratch cap holds; results do not depend on it).
  * "PT_RAM_WIDE_MIN": smallest chain dimension whose bookkeeping the lane samplers give to the wide kernels (default 17; 4: every chain). */
 int carma_tune_set(const char* name, long value);
 
@@ -265,6 +266,20 @@ int carma_bands_smooth(carma_bands* h, const double* theta /* [B][dx] */, int B,
  *   carma_bands_mle_batched.  Every optimiser step is ONE carma_bandset_logdensity_batch over the active starts of all objects; a
  *   start's x, fun, nit and status are those of carma_bands_mle_batched on its object alone (nfev may differ: how many stencils
  *   ride along with a line search depends on the number of starts in flight).
+ * carma_bandset_smooth: carma_bands_smooth of B ROWS on any objects of the set in one call: row i is the curve of band band[i] of
+ *   object[i] under theta[i] ([B][dx]) at the observer times tout[toff[i] ... toff[i + 1]) (toff = [B + 1], at least one time a
+ *   row; any order, repeats allowed); its results go to mean / var at toff[i] - toff[0], in the caller's order of that row's
+ *   times.  The rows that share (object, band, list of times) are a job and fill waves of 64 in the caller's order, a wave
+ *   on ONE job (k_smooth_mband_fwd_ms / k_smooth_mband_bwd_ms), the waves with the most points first; one row alone on its
+ *   (object, band, times) takes a wave of which 63 lanes are pads.  A row has the bits carma_bands_smooth gives it on a handle of
+ *   its object alone, whatever else the call carries.  The semantics are carma_bands_smooth's: the prior is never applied, the
+ *   variance is returned as computed, an invalid row (repeated AR root, non-finite lag, scale or offset) is NaN and sets
+ *   invalid[i]; returns CARMA_OK, or 1 if a row was invalid and `invalid` is NULL.  CARMA_EINVAL before any device work for a null
+ *   handle, B < 1, a null theta / object / band / tout / toff / mean / var, an object[i] outside [0, S) or band[i] outside [0, K)
+ *   (row and value named), a toff that does not grow by at least 1 a row, N_s + M_i beyond an int, or a time that is not finite
+ *   (row and position named; the times are read last); the handle stays usable.  Scratch as carma_bands_smooth per wave, capped
+ *   at 256 MiB a chunk of waves ("MBANDSET_SMOOTH_CHUNK_WAVES" of carma_tune_set forces the waves of a chunk; a row's result
+ *   does not depend on it).
  */
 typedef struct carma_bandset carma_bandset;
 carma_bandset* carma_bandset_create(const double* time, const double* y, const double* yerr, const long* offsets /* [S*K+1] */,
@@ -283,6 +298,9 @@ int carma_bandset_mle_batched(carma_bandset* h, const double* x0 /* [B][dx] */, 
                               const double* lo /* [B][dx] */, const double* hi /* [B][dx] */,
                               const double* fixed_lag /* [B][K-1] or NULL */, int maxiter, int mem, double ftol, double gtol,
                               double fd_step, int ignore_prior, double* x, double* fun, int* nit, int* nfev, int* status);
+int carma_bandset_smooth(carma_bandset* h, const double* theta /* [B][dx] */, const int* object /* [B] */,
+                         const int* band /* [B] */, int B, const double* tout, const long* toff /* [B+1] */, double* mean,
+                         double* var, int* invalid /* [B] or NULL */);
 
 /*
  * The parallel-tempering sampler of a MULTI-BAND fit (the carma_mpt_* set on a carma_bands handle, one run): nreplicas independent
