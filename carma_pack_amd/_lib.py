@@ -97,6 +97,20 @@ SIGNATURES = {
     "carma_bands_pt_logdensity": (_I, [_V, _dp, _dp]),
     "carma_bands_pt_kernel_name": (_I, [_V, _S, _I]),
     "carma_bands_pt_run": (_I, [_V, _I, _I, _I, _I, _I, _dp, _U64, _dp, _dp, _dp, _dp]),
+    "carma_bandset_pt_default_box": (_I, [_V, _I, _dp, _dp]),
+    "carma_bandset_pt_create": (_I, [_V, _ip, _I, _I, _I, _dp, _I, _U64, _dp, _dp]),
+    "carma_bandset_pt_start": (_I, [_V, _dp]),
+    "carma_bandset_pt_set_chains": (_I, [_V, _dp, _dp]),
+    "carma_bandset_pt_get_chains": (_I, [_V, _dp, _dp]),
+    "carma_bandset_pt_get_factor": (_I, [_V, _dp]),
+    "carma_bandset_pt_set_factor": (_I, [_V, _dp]),
+    "carma_bandset_pt_iterate": (_I, [_V, _L, _I]),
+    "carma_bandset_pt_sample": (_I, [_V, _I, _I, _dp, _dp]),
+    "carma_bandset_pt_stats": (_I, [_V, _dp, _dp, _I]),
+    "carma_bandset_pt_iterations_done": (_L, [_V]),
+    "carma_bandset_pt_logdensity": (_I, [_V, _dp, _dp]),
+    "carma_bandset_pt_kernel_name": (_I, [_V, _S, _I]),
+    "carma_bandset_pt_run": (_I, [_V, _ip, _I, _I, _I, _I, _I, _I, _dp, _U64, _dp, _dp, _dp, _dp]),
     "carma_kfilter_carma": (_I, _SERIES + [_I, _D, _dp, _dp, _I, _dp, _dp, _ip, _I]),
     "carma_kfilter_batch_carma": (_I, _SERIES + [_I, _I, _dp, _dp, _dp, _I, _dp, _dp, _dp, _ip, _ip, _I]),
     "carma_kfilter_car1": (_I, _SERIES + [_D, _D, _dp, _dp, _ip, _I]),
@@ -444,7 +458,7 @@ class _Handle:
 class _Sampler:
     """The parallel-tempering calls Context (carma_pt_*, chains [R][T]) and MultiContext (carma_mpt_*, chains [M][R][T]) share:
     `_pt` is the prefix of the C functions, `_pt_lead()` the leading shape (..., R, T) that pt_create / pt_run left.  BandsContext (carma_bands_pt_*, chains [R][T] of dx
-    entries) takes them too."""
+    entries) and BandsSetContext (carma_bandset_pt_*, chains [M][R][T] of dx entries) take them too."""
     _pt = None
 
     def _pt_dim(self):
@@ -453,6 +467,21 @@ class _Sampler:
 
     def _pt_call(self, name, *args):
         check(getattr(lib, self._pt + name)(self._h, *args), self._pt + name)
+
+    # the samplers of many runs per call (MultiContext, BandsSetContext): the run list and the init rows as the C calls take them
+    def _runs(self, index):
+        w = np.asarray(index, dtype=np.int64).ravel()
+        if w.size < 1:
+            raise ValueError("need at least one run")
+        return np.ascontiguousarray(w, dtype=np.int32)
+
+    def _init_rows(self, init, M):
+        if init is None:
+            return None
+        a = as_f64(init)
+        if a.shape != (M, self._pt_dim()):
+            raise ValueError("init must be [%d, %d] (one row per run), got %r" % (M, self._pt_dim(), a.shape))
+        return a
 
     def pt_set_chains(self, theta, logpost=None):
         lead = self._pt_lead()
@@ -881,20 +910,6 @@ class MultiContext(_Handle, _Sampler):
         return out
 
     # ---- parallel-tempering sampler over many series (carma_mpt_*); the rest is _Sampler's --------
-    def _runs(self, series):
-        w = np.asarray(series, dtype=np.int64).ravel()
-        if w.size < 1:
-            raise ValueError("need at least one run")
-        return np.ascontiguousarray(w, dtype=np.int32)
-
-    def _init_rows(self, init, M):
-        if init is None:
-            return None
-        a = as_f64(init)
-        if a.shape != (M, self.d):
-            raise ValueError("init must be [%d, %d] (one row per run), got %r" % (M, self.d, a.shape))
-        return a
-
     def _pt_lead(self):
         if getattr(self, "_mpt_shape", None) is None:
             raise ValueError("call pt_create first")
@@ -1088,14 +1103,88 @@ class BandsContext(_Handle, _Sampler):
         return (mean, var, bm, bv, inv) if moments else (mean, var, inv)
 
 
-class BandsSetContext(_Handle):
+class BandsSetContext(_Handle, _Sampler):
     """Owns one carma_bandset: S multi-band objects of the same K bands and order resident in HBM, each prepared as BandsContext
     prepares its one object; a call carries evaluations of any of them (k_logdens_carma_mband_ms, one object per wave).
 
     objects: a list of S lists of K (t, y, yerr); lag_bounds: [K - 1] pairs (lo, hi) for every object or [S, K - 1] pairs, one
     list per object; max_stdev: None (BandsContext's default per object), one number or [S].  An object that lacks a band
-    belongs to another set."""
-    _destroy = "carma_bandset_destroy"
+    belongs to another set.
+    The sampler (carma_bandset_pt_*): pt_create / pt_start, then _Sampler's calls on chains [M][R][T] of dx entries, run j of
+    the M on object objects[j]."""
+    _destroy, _pt = "carma_bandset_destroy", "carma_bandset_pt_"
+
+    # ---- parallel-tempering sampler over many objects (carma_bandset_pt_*); the rest is _Sampler's --------
+    def _pt_dim(self):
+        return self.dx
+
+    def _pt_lead(self):
+        if getattr(self, "_bspt_shape", None) is None:
+            raise ValueError("call pt_create first")
+        return self._bspt_shape
+
+    def _band_boxes(self, band_box, M):
+        """None, or (lo, hi) [M, K - 1, 2] each ([K - 1, 2]: for every run), columns (log a_b, mu_b) -> the two arrays the C calls
+        take (or None, None)."""
+        if band_box is None:
+            return None, None
+        shape = (M, self.nbands - 1, 2)
+        lo, hi = (as_f64(np.broadcast_to(as_f64(v), shape) if np.ndim(v) == 2 else as_f64(v).reshape(shape)) for v in band_box)
+        return lo, hi
+
+    def pt_default_box(self, s):
+        """(lo, hi) [K - 1, 2] each: the default box of (log a_b, mu_b) of object s (carma_bandset_pt_default_box)."""
+        lo, hi = np.empty((self.nbands - 1, 2)), np.empty((self.nbands - 1, 2))
+        check(lib.carma_bandset_pt_default_box(self._h, int(s), ptr(lo), ptr(hi)), "carma_bandset_pt_default_box")
+        return lo, hi
+
+    def pt_create(self, objects, ntemps, nreplicas, adapt_iters, seed=0, temperatures=None, band_box=None):
+        """One sampler run (nreplicas ladders of ntemps chains on the extended vector) per entry of `objects` (indices into this
+        set, any order, repeats allowed), all advancing in the same launches (carma_bandset_pt_create).  band_box: None (no box)
+        or (lo, hi), [M, K - 1, 2] each -- a box per run -- or [K - 1, 2] each for every run."""
+        w = self._runs(objects)
+        tt = as_f64(temperatures) if temperatures is not None else None
+        if tt is not None and tt.size != int(ntemps):
+            raise ValueError("temperatures must hold ntemps = %d values" % int(ntemps))
+        lo, hi = self._band_boxes(band_box, w.size)
+        self._bspt_shape = None
+        check(lib.carma_bandset_pt_create(self._h, _iptr(w), w.size, int(ntemps), int(nreplicas), _optr(tt), int(adapt_iters),
+                                          _seed(seed), _optr(lo), _optr(hi)), "carma_bandset_pt_create")
+        self._bspt_shape = (int(w.size), int(nreplicas), int(ntemps))
+        self._bspt_objects = w
+
+    def pt_start(self, init=None):
+        """Starting values (carma_bandset_pt_start); init: None or [M, dx], row j for every chain of run j where it is finite."""
+        a = self._init_rows(init, self._pt_lead()[0])
+        check(lib.carma_bandset_pt_start(self._h, _optr(a)), "carma_bandset_pt_start")
+
+    def pt_logdensity(self, theta):
+        """Log-densities of chain states [M][R][T][dx], each on its run's object and in its run's box, through the sampler's own
+        log-density kernel."""
+        lead = self._pt_lead()
+        theta = as_f64(theta).reshape(lead + (self.dx,))
+        out = np.empty(lead)
+        check(lib.carma_bandset_pt_logdensity(self._h, ptr(theta), ptr(out)), "carma_bandset_pt_logdensity")
+        return out
+
+    def pt_kernel_name(self):
+        return _kernel_name("carma_bandset_pt_kernel_name", self._h)
+
+    def pt_run(self, objects, ntemps, nreplicas, sample_size, burnin, thin=1, init=None, seed=0, band_box=None):
+        """Whole Sampler::Run of every run: (samples [M][R][S][dx], logposts [M][R][S]) of the coldest chains
+        (carma_bandset_pt_run)."""
+        w = self._runs(objects)
+        a = self._init_rows(init, w.size)
+        lo, hi = self._band_boxes(band_box, w.size)
+        samples = np.empty((w.size, int(nreplicas), int(sample_size), self.dx))
+        logposts = np.empty((w.size, int(nreplicas), int(sample_size)))
+        self._bspt_shape = None
+        check(lib.carma_bandset_pt_run(self._h, _iptr(w), w.size, int(ntemps), int(nreplicas), int(sample_size), int(burnin),
+                                       int(thin), _optr(a), _seed(seed), _optr(lo), _optr(hi), ptr(samples), ptr(logposts)),
+              "carma_bandset_pt_run")
+        self._bspt_shape = (int(w.size), int(nreplicas), int(ntemps))
+        self._bspt_objects = w
+        return samples, logposts
 
     def __init__(self, objects, p, q=0, lag_bounds=None, max_stdev=None, device=None):
         objects = [list(o) for o in objects]

@@ -1601,6 +1601,90 @@ class CarmaBandsSet(object):
             out.append(tuple(pair))
         return out
 
+    def _run_boxes(self, which, name, bounds):
+        """scale_bounds / offset_bounds of run_mcmc -> a list of len(which) entries, None or [K - 1, 2], each checked by its
+        model's _band_box: None, one [K - 1, 2] for all objects, or [len(which), K - 1, 2]."""
+        if bounds is None:
+            return [None] * len(which)
+        a = np.asarray(bounds, dtype=float)
+        if a.ndim == 2:
+            a = np.broadcast_to(a, (len(which),) + a.shape)
+        if a.ndim != 3 or a.shape[0] != len(which):
+            raise ValueError("%s must be [%d, 2] for all objects or [%d, %d, 2], one per object, got shape %r"
+                             % (name, self.K - 1, len(which), self.K - 1, a.shape))
+        out = []
+        for i, s in enumerate(which):
+            try:
+                pair = self.models[s]._band_box(a[i] if name == "scale_bounds" else None, a[i] if name == "offset_bounds" else None)
+            except ValueError as ex:
+                raise ValueError("object %d: %s" % (s, ex))
+            out.append(pair[0] if name == "scale_bounds" else pair[1])
+        return out
+
+    def run_mcmc(self, nsamples, nburnin=None, ntemperatures=None, nthin=1, init=None, nreplicas=1, seed=None, scale_bounds=None,
+                 offset_bounds=None, which=None):
+        """CarmaBandsModel.run_mcmc of the objects `which` (None: every object) in ONE sampler run (BandsSetContext.pt_run,
+        carma_bandset_pt_run): the ladders of all objects advance in the same launches, one chain per lane, a wave on one object.
+        Defaults as CarmaBandsModel.run_mcmc: nburnin = nsamples / 2, ntemperatures = max(10, p + q).  init: None, [dx] for all
+        objects or [len(which), dx]; scale_bounds / offset_bounds: None (each object's default box), [K - 1, 2] for all objects or
+        [len(which), K - 1, 2].  The default ladder fills 10 of a wave's 64 lanes: nreplicas fills the rest at no cost in time.
+        Returns a list of CarmaBandsSample, one per entry of `which` in the caller's order, each also kept as that model's
+        mcmc_sample."""
+        if int(nsamples) < 1:
+            raise ValueError("nsamples must be at least 1")
+        if int(nthin) < 1 or int(nreplicas) < 1:
+            raise ValueError("nthin and nreplicas must be at least 1")
+        if which is None:
+            which = np.arange(self.nobjects)
+        which = np.asarray(which)
+        if which.ndim != 1 or which.size < 1 or which.dtype.kind not in "iu":
+            raise ValueError("which must be a list of at least one object index")
+        if which.min() < 0 or which.max() >= self.nobjects:
+            raise ValueError("which: object index out of range [0, %d)" % self.nobjects)
+        which = which.astype(np.int64)
+        M = which.size
+        if init is not None:
+            init = np.asarray(init, dtype=float)
+            if init.shape == (self.dx,):
+                init = np.broadcast_to(init, (M, self.dx))
+            if init.shape != (M, self.dx):
+                raise ValueError("init must be [%d] or [%d, %d] (one row per object of which), got %r" % (self.dx, M, self.dx, init.shape))
+        sbs = self._run_boxes(which, "scale_bounds", scale_bounds)
+        obs = self._run_boxes(which, "offset_bounds", offset_bounds)
+        if ntemperatures is None:
+            ntemperatures = max(10, self.p + self.q)
+        if not 1 <= int(ntemperatures) <= 64:
+            raise ValueError("ntemperatures must be 1 ... 64 (a ladder is the lanes of one wave), got %d" % int(ntemperatures))
+        if nburnin is None:
+            nburnin = int(nsamples) // 2
+        if int(nburnin) < 0:
+            raise ValueError("nburnin must not be negative")
+        ctx = self.context()
+        lo, hi = np.empty((M, self.K - 1, 2)), np.empty((M, self.K - 1, 2))
+        for i, s in enumerate(which):
+            lo[i], hi[i] = ctx.pt_default_box(s)
+            if sbs[i] is not None:
+                lo[i, :, 0], hi[i, :, 0] = np.log(sbs[i][:, 0]), np.log(sbs[i][:, 1])
+            if obs[i] is not None:
+                lo[i, :, 1], hi[i, :, 1] = obs[i][:, 0], obs[i][:, 1]
+        # longest object first: the waves in flight together then have similar trip counts
+        order = np.argsort(-ctx.n.sum(axis=1)[which], kind="stable")
+        runs = which[order]
+        samples, logposts = ctx.pt_run(runs, int(ntemperatures), int(nreplicas), int(nsamples), int(nburnin), int(nthin),
+                                       init=None if init is None else init[order], seed=carmcmcLib._seed(seed),
+                                       band_box=(lo[order], hi[order]))
+        # the "loglik" column (prior bounds ignored) of all objects' draws: one launch; the "sigma" column: one more
+        per = samples.shape[1] * samples.shape[2]
+        flat = samples.reshape(-1, self.dx)
+        loglik = ctx.logdensity(flat, np.repeat(runs, per), ignore_prior=True).reshape(M, per)
+        sigma = carmcmcLib.sigma_noise_batch(*CarmaSample._sigma_inputs_of(flat[:, :self.d], self.p, self.q)).reshape(M, per)
+        out = [None] * M
+        for j, i in enumerate(order):
+            m = self.models[which[i]]
+            out[i] = CarmaBandsSample(m, samples[j], logposts[j], loglik=loglik[j], sigma=sigma[j])
+            m.mcmc_sample = out[i]
+        return out
+
 
 class CarmaBandsSample(MCMCSample):
     """The draws of CarmaBandsModel.run_mcmc: every replica's cold chain, replica after replica, n = R x nsamples rows.

@@ -68,6 +68,8 @@ struct MbandSet {
     std::vector<double> lagbox;       // [S][K - 1][2]
     std::vector<Prior> pr;            // [S]
     std::vector<double> t0;           // [S] the time origin of object s (MbandObject::t0): what its requested times are shifted by
+    std::vector<std::vector<double>> ts, ys;   // [S][K] the bands' times and values after sort / dedup (MbandObject::ts / ys:
+                                      // host only, what the set's sampler takes starting values, factors and boxes from)
     std::vector<double> rec;          // the records of all objects (an object keeps its own t0: the earliest time of ITS bands)
 };
 
@@ -90,6 +92,10 @@ inline int mbandset_prepare(const double* time, const double* y, const double* y
         m.lagbox.insert(m.lagbox.end(), o.lagbox.begin(), o.lagbox.end());
         m.pr.push_back(o.pr);
         m.t0.push_back(o.t0);
+        for (int b = 0; b < K; b++) {
+            m.ts.push_back(std::move(o.ts[b]));
+            m.ys.push_back(std::move(o.ys[b]));
+        }
     }
     return -1;
 }

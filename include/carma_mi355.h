@@ -347,6 +347,49 @@ int carma_bands_pt_run(carma_bands* h, int ntemps, int nreplicas, int sample_siz
                        const double* init /* [dx] or NULL */, uint64_t seed, const double* band_lo, const double* band_hi,
                        double* samples, double* logposts);
 
+/* ---- the sampler over a SET of multi-band objects (carma_mband_set_pt.hip) ----
+ * carma_bands_pt_* for MANY objects of a carma_bandset handle in the same launches.  A RUN is one sampler (nreplicas ladders of
+ * ntemps chains on the extended vector) on one object; object[j] is the object of run j (any order, repeats allowed).  The M runs
+ * are the ladders j R ... j R + R - 1 of one ensemble of M R ladders, and run j walks, bit for bit, the trajectory those ladders
+ * walk under carma_bands_pt_* with M R replicas on a handle of its object alone, whatever its neighbours are.  The log-density
+ * kernel gives every run waves of its own (a wave works on one object): ceil(R T / 64) of them.
+ *
+ * carma_bandset_pt_default_box: carma_bands_pt_default_box of one object.
+ * carma_bandset_pt_create: temperatures = [ntemps] or NULL, shared by all runs; band_lo / band_hi = [M][nbands - 1][2], a box per
+ *   run, or both NULL: no box.  The initial proposal factor of a run comes from its own object as in carma_bands_pt_create.
+ *   CARMA_EINVAL before any device work, with a message that names the run and its object: M < 1, an object index out of range,
+ *   more chains (M * nreplicas * ntemps) than a launch indexes, and whatever carma_bands_pt_create refuses for that run.
+ * carma_bandset_pt_start: init = [M][dx] or NULL; a run whose row has a finite log-density on its object (inside its box) starts
+ *   every chain there, the others draw as carma_bands_pt_start draws, keyed by the chain's slot in the ensemble; the pending
+ *   candidates of all runs are evaluated together, one carma_bandset_logdensity_batch a round.
+ * carma_bandset_pt_set_chains / _get_chains: theta = [M][R][T][dx], logpost = [M][R][T] (NULL on set: computed, -inf outside the
+ *   run's box).  _get_factor / _set_factor: [M][R][T][dx*dx].  _iterate / _sample / _stats / _iterations_done: as the carma_mpt_
+ *   calls; samples = [M][R][nsamples][dx], rates = [M][R][T].  Every call but _create and _default_box is CARMA_EINVAL before
+ *   carma_bandset_pt_create, iterate / sample also before the chains have starting values; the handle stays usable.
+ * carma_bandset_pt_logdensity: the log-densities of chain states theta = [M][R][T][dx], each on its run's object and in its run's
+ *   box, through the sampler's kernel; out = [M][R][T].  carma_bandset_pt_kernel_name: that kernel's name.
+ * carma_bandset_pt_run: create, start, burn-in (adapting), sample.
+ */
+int carma_bandset_pt_default_box(const carma_bandset* h, int object, double* band_lo /* [K-1][2] */, double* band_hi /* [K-1][2] */);
+int carma_bandset_pt_create(carma_bandset* h, const int* object /* [M] */, int M, int ntemps, int nreplicas,
+                            const double* temperatures /* [ntemps] or NULL */, int adapt_iters, uint64_t seed,
+                            const double* band_lo /* [M][K-1][2] or NULL */, const double* band_hi /* [M][K-1][2] or NULL */);
+int carma_bandset_pt_start(carma_bandset* h, const double* init /* [M][dx] or NULL */);
+int carma_bandset_pt_set_chains(carma_bandset* h, const double* theta /* [M][R][T][dx] */,
+                                const double* logpost /* [M][R][T] or NULL */);
+int carma_bandset_pt_get_chains(carma_bandset* h, double* theta, double* logpost);
+int carma_bandset_pt_get_factor(carma_bandset* h, double* chol);
+int carma_bandset_pt_set_factor(carma_bandset* h, const double* chol);
+int carma_bandset_pt_iterate(carma_bandset* h, long niter, int do_exchange);
+int carma_bandset_pt_sample(carma_bandset* h, int nsamples, int thin, double* samples /* [M][R][nsamples][dx] */, double* logposts);
+int carma_bandset_pt_stats(carma_bandset* h, double* accept_rate, double* swap_rate, int reset);
+long carma_bandset_pt_iterations_done(const carma_bandset* h);
+int carma_bandset_pt_logdensity(carma_bandset* h, const double* theta /* [M][R][T][dx] */, double* out /* [M][R][T] */);
+int carma_bandset_pt_kernel_name(const carma_bandset* h, char* buf, int len);
+int carma_bandset_pt_run(carma_bandset* h, const int* object /* [M] */, int M, int ntemps, int nreplicas, int sample_size,
+                         int burnin, int thin, const double* init /* [M][dx] or NULL */, uint64_t seed, const double* band_lo,
+                         const double* band_hi, double* samples, double* logposts);
+
 /*
  * The parallel-tempering sampler over MANY SERIES (the carma_pt_* set on a carma_mctx).  A RUN is one sampler -- nreplicas
  * independent ladders of ntemps chains -- on one series of the context; a call takes M runs, series = [M] (an index may repeat,
