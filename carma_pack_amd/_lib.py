@@ -465,6 +465,11 @@ class _Sampler:
         """Entries of a chain's vector: d of a series; a context whose chains carry more (BandsContext: dx) says so here."""
         return self.d
 
+    def _pt_lead(self):
+        if getattr(self, "_pt_shape", None) is None:
+            raise ValueError("call pt_create first")
+        return self._pt_shape
+
     def _pt_call(self, name, *args):
         check(getattr(lib, self._pt + name)(self._h, *args), self._pt + name)
 
@@ -523,6 +528,19 @@ class _Sampler:
 
     def pt_iterations_done(self):
         return getattr(lib, self._pt + "iterations_done")(self._h)
+
+    # the handle-based lane samplers (carma_mpt_*, carma_bands_pt_*, carma_bandset_pt_*) only
+    def pt_logdensity(self, theta):
+        """Log-densities of chain states [...][R][T][dim], each as its chain's run has it (its series or object, its band box),
+        through the sampler's own log-density kernel."""
+        lead = self._pt_lead()
+        theta = as_f64(theta).reshape(lead + (self._pt_dim(),))
+        out = np.empty(lead)
+        self._pt_call("logdensity", ptr(theta), ptr(out))
+        return out
+
+    def pt_kernel_name(self):
+        return _kernel_name(self._pt + "kernel_name", self._h)
 
 
 class Context(_Handle, _Sampler):
@@ -910,11 +928,6 @@ class MultiContext(_Handle, _Sampler):
         return out
 
     # ---- parallel-tempering sampler over many series (carma_mpt_*); the rest is _Sampler's --------
-    def _pt_lead(self):
-        if getattr(self, "_mpt_shape", None) is None:
-            raise ValueError("call pt_create first")
-        return self._mpt_shape
-
     def pt_create(self, series, ntemps, nreplicas, adapt_iters, seed=0, temperatures=None):
         """One sampler run (nreplicas ladders of ntemps chains) per entry of `series` (indices into this context, any order,
         repeats allowed), all advancing in the same launches (carma_mpt_create)."""
@@ -924,24 +937,13 @@ class MultiContext(_Handle, _Sampler):
             raise ValueError("temperatures must hold ntemps = %d values" % int(ntemps))
         check(lib.carma_mpt_create(self._h, _iptr(w), w.size, int(ntemps), int(nreplicas), _optr(tt), int(adapt_iters),
                                    _seed(seed)), "carma_mpt_create")
-        self._mpt_shape = (int(w.size), int(nreplicas), int(ntemps))
+        self._pt_shape = (int(w.size), int(nreplicas), int(ntemps))
         self._mpt_series = w
 
     def pt_start(self, init=None):
         """Starting values (carma_mpt_start); init: None or [M, d], row j for every chain of run j where it is finite."""
         a = self._init_rows(init, self._pt_lead()[0])
         check(lib.carma_mpt_start(self._h, _optr(a)), "carma_mpt_start")
-
-    def pt_logdensity(self, theta):
-        """Log-densities of chain states [M][R][T][d], each on its run's series, through the sampler's own log-density kernel."""
-        lead = self._pt_lead()
-        theta = as_f64(theta).reshape(lead + (self.d,))
-        out = np.empty(lead)
-        check(lib.carma_mpt_logdensity(self._h, ptr(theta), ptr(out)), "carma_mpt_logdensity")
-        return out
-
-    def pt_kernel_name(self):
-        return _kernel_name("carma_mpt_kernel_name", self._h)
 
     def pt_run(self, series, ntemps, nreplicas, sample_size, burnin, thin=1, init=None, seed=0):
         """Whole Sampler::Run of every run: (samples [M][R][S][d], logposts [M][R][S]) of the coldest chains (carma_mpt_run)."""
@@ -951,7 +953,7 @@ class MultiContext(_Handle, _Sampler):
         logposts = np.empty((w.size, int(nreplicas), int(sample_size)))
         check(lib.carma_mpt_run(self._h, _iptr(w), w.size, int(ntemps), int(nreplicas), int(sample_size), int(burnin), int(thin),
                                 _optr(a), _seed(seed), ptr(samples), ptr(logposts)), "carma_mpt_run")
-        self._mpt_shape = (int(w.size), int(nreplicas), int(ntemps))
+        self._pt_shape = (int(w.size), int(nreplicas), int(ntemps))
         self._mpt_series = w
         return samples, logposts
 
@@ -966,11 +968,6 @@ class BandsContext(_Handle, _Sampler):
 
     def _pt_dim(self):
         return self.dx
-
-    def _pt_lead(self):
-        if getattr(self, "_bpt_shape", None) is None:
-            raise ValueError("call pt_create first")
-        return self._bpt_shape
 
     def _band_box(self, band_box):
         """None, or (lo, hi) [K - 1, 2] each, columns (log a_b, mu_b) -> the two arrays the C calls take (or None, None)."""
@@ -992,10 +989,10 @@ class BandsContext(_Handle, _Sampler):
         if tt is not None and tt.size != int(ntemps):
             raise ValueError("temperatures must hold ntemps = %d values" % int(ntemps))
         lo, hi = self._band_box(band_box)
-        self._bpt_shape = None
+        self._pt_shape = None
         check(lib.carma_bands_pt_create(self._h, int(ntemps), int(nreplicas), _optr(tt), int(adapt_iters), _seed(seed), _optr(lo),
                                         _optr(hi)), "carma_bands_pt_create")
-        self._bpt_shape = (int(nreplicas), int(ntemps))
+        self._pt_shape = (int(nreplicas), int(ntemps))
 
     def _init_row(self, init):
         if init is None:
@@ -1009,27 +1006,16 @@ class BandsContext(_Handle, _Sampler):
         """Starting values (carma_bands_pt_start); init: None or [dx], every chain's value where its log-density is finite."""
         check(lib.carma_bands_pt_start(self._h, _optr(self._init_row(init))), "carma_bands_pt_start")
 
-    def pt_logdensity(self, theta):
-        """Log-densities of chain states [R][T][dx] through the sampler's own log-density kernel (with the band box)."""
-        lead = self._pt_lead()
-        theta = as_f64(theta).reshape(lead + (self.dx,))
-        out = np.empty(lead)
-        check(lib.carma_bands_pt_logdensity(self._h, ptr(theta), ptr(out)), "carma_bands_pt_logdensity")
-        return out
-
-    def pt_kernel_name(self):
-        return _kernel_name("carma_bands_pt_kernel_name", self._h)
-
     def pt_run(self, ntemps, nreplicas, sample_size, burnin, thin=1, init=None, seed=0, band_box=None):
         """Whole Sampler::Run: (samples [R][S][dx], logposts [R][S]) of the coldest chains (carma_bands_pt_run)."""
         a = self._init_row(init)
         lo, hi = self._band_box(band_box)
         samples = np.empty((int(nreplicas), int(sample_size), self.dx))
         logposts = np.empty((int(nreplicas), int(sample_size)))
-        self._bpt_shape = None
+        self._pt_shape = None
         check(lib.carma_bands_pt_run(self._h, int(ntemps), int(nreplicas), int(sample_size), int(burnin), int(thin), _optr(a),
                                      _seed(seed), _optr(lo), _optr(hi), ptr(samples), ptr(logposts)), "carma_bands_pt_run")
-        self._bpt_shape = (int(nreplicas), int(ntemps))
+        self._pt_shape = (int(nreplicas), int(ntemps))
         return samples, logposts
 
     def __init__(self, bands, p, q=0, lag_bounds=None, max_stdev=None, device=None):
@@ -1118,11 +1104,6 @@ class BandsSetContext(_Handle, _Sampler):
     def _pt_dim(self):
         return self.dx
 
-    def _pt_lead(self):
-        if getattr(self, "_bspt_shape", None) is None:
-            raise ValueError("call pt_create first")
-        return self._bspt_shape
-
     def _band_boxes(self, band_box, M):
         """None, or (lo, hi) [M, K - 1, 2] each ([K - 1, 2]: for every run), columns (log a_b, mu_b) -> the two arrays the C calls
         take (or None, None)."""
@@ -1147,28 +1128,16 @@ class BandsSetContext(_Handle, _Sampler):
         if tt is not None and tt.size != int(ntemps):
             raise ValueError("temperatures must hold ntemps = %d values" % int(ntemps))
         lo, hi = self._band_boxes(band_box, w.size)
-        self._bspt_shape = None
+        self._pt_shape = None
         check(lib.carma_bandset_pt_create(self._h, _iptr(w), w.size, int(ntemps), int(nreplicas), _optr(tt), int(adapt_iters),
                                           _seed(seed), _optr(lo), _optr(hi)), "carma_bandset_pt_create")
-        self._bspt_shape = (int(w.size), int(nreplicas), int(ntemps))
+        self._pt_shape = (int(w.size), int(nreplicas), int(ntemps))
         self._bspt_objects = w
 
     def pt_start(self, init=None):
         """Starting values (carma_bandset_pt_start); init: None or [M, dx], row j for every chain of run j where it is finite."""
         a = self._init_rows(init, self._pt_lead()[0])
         check(lib.carma_bandset_pt_start(self._h, _optr(a)), "carma_bandset_pt_start")
-
-    def pt_logdensity(self, theta):
-        """Log-densities of chain states [M][R][T][dx], each on its run's object and in its run's box, through the sampler's own
-        log-density kernel."""
-        lead = self._pt_lead()
-        theta = as_f64(theta).reshape(lead + (self.dx,))
-        out = np.empty(lead)
-        check(lib.carma_bandset_pt_logdensity(self._h, ptr(theta), ptr(out)), "carma_bandset_pt_logdensity")
-        return out
-
-    def pt_kernel_name(self):
-        return _kernel_name("carma_bandset_pt_kernel_name", self._h)
 
     def pt_run(self, objects, ntemps, nreplicas, sample_size, burnin, thin=1, init=None, seed=0, band_box=None):
         """Whole Sampler::Run of every run: (samples [M][R][S][dx], logposts [M][R][S]) of the coldest chains
@@ -1178,11 +1147,11 @@ class BandsSetContext(_Handle, _Sampler):
         lo, hi = self._band_boxes(band_box, w.size)
         samples = np.empty((w.size, int(nreplicas), int(sample_size), self.dx))
         logposts = np.empty((w.size, int(nreplicas), int(sample_size)))
-        self._bspt_shape = None
+        self._pt_shape = None
         check(lib.carma_bandset_pt_run(self._h, _iptr(w), w.size, int(ntemps), int(nreplicas), int(sample_size), int(burnin),
                                        int(thin), _optr(a), _seed(seed), _optr(lo), _optr(hi), ptr(samples), ptr(logposts)),
               "carma_bandset_pt_run")
-        self._bspt_shape = (int(w.size), int(nreplicas), int(ntemps))
+        self._pt_shape = (int(w.size), int(nreplicas), int(ntemps))
         self._bspt_objects = w
         return samples, logposts
 

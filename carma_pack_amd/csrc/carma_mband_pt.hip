@@ -6,8 +6,6 @@
 // (ram_kernels_plan).  One run of R replicas x T temperatures; host-only decisions in carma_mband_pt_plan.h.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <limits>
@@ -20,6 +18,7 @@
 #include "carma_host.h"
 #include "carma_mband_ctx.h"
 #include "carma_mband_pt_plan.h"
+#include "carma_pt_front.h"
 
 namespace carma {
 
@@ -72,26 +71,6 @@ static hipError_t launch_logdens_mband_chains(const Bctx* c, const BptState* s, 
     return for_order(c->p, hipErrorInvalidValue, go);
 }
 
-// the sampler state of h, or null with the error set: `who` was called before carma_bands_pt_create (need_start: or before the
-// chains have starting values)
-static BptState* bpt_state(carma_bands* h, const char* who, bool need_start)
-{
-    if (!h) {
-        set_error("%s: null context", who);
-        return nullptr;
-    }
-    BptState* s = reinterpret_cast<Bctx*>(h)->bpt.get();
-    if (!s) {
-        set_error("%s: call carma_bands_pt_create first", who);
-        return nullptr;
-    }
-    if (need_start && !s->started) {
-        set_error("%s: chains have no starting values (carma_bands_pt_start / carma_bands_pt_set_chains)", who);
-        return nullptr;
-    }
-    return s;
-}
-
 static std::vector<BandView> band_views(const Bctx* c)
 {
     std::vector<BandView> v((size_t)c->K);
@@ -111,29 +90,37 @@ static int bpt_logdens_host(carma_bands* h, const BptState* s, const double* thx
     return CARMA_OK;
 }
 
-// niter iterations, a chunk in flight at a time.  thin > 0: save the coldest chains every thin iterations from sample *save_offset on
-static int bpt_iterate(Bctx* c, long niter, int do_exchange, int thin, long* save_offset)
+// The sampler of h as the shared front drives it (carma_pt_front.h): one run, so every chain is of run 0
+static PtFront bpt_front(carma_bands* h)
 {
+    PtFront f;
+    f.name = "carma_bands_pt";
+    if (!h) return f;
+    Bctx* c = reinterpret_cast<Bctx*>(h);
     BptState* s = c->bpt.get();
-    const long chunk0 = mband_pt_chunk_iters(c->o.N);
-    const PtLaneK1 k1 = [c, s](const double* thn, long nc, double* ll, hipStream_t st) {
-        return launch_logdens_mband_chains(c, s, thn, nc, ll, st);
+    f.has_ctx = true;
+    f.device = c->device;
+    f.stream = c->stream;
+    f.p = c->p;
+    f.q = c->q;
+    f.dim = c->dx;
+    f.s = s;
+    f.guard = &c->d_theta;
+    if (!s) return f;
+    f.per_run = s->nchain();
+    f.n = c->o.N;
+    f.chunk0 = mband_pt_chunk_iters(c->o.N);
+    f.k1 = [c, s](const double* thn, long nc, double* ll, hipStream_t st) { return launch_logdens_mband_chains(c, s, thn, nc, ll, st); };
+    f.eval = [h, s](const double* rows, const size_t*, size_t m, double* out) { return bpt_logdens_host(h, s, rows, m, out); };
+    f.draw = [c, s, bands = band_views(c)](size_t k, int round, double* out) {
+        mband_pt_draw_start(bands.data(), c->K, c->o.pr, c->p, c->q, c->o.lagbox.data(), s->seed, (uint64_t)k, round, out);
     };
-    long left = niter;
-    while (left > 0) {
-        const long ch = pt_next_chunk(left, chunk0, thin);
-        const PtLaunch L = pt_ens_launch(s, c->dx, c->q, c->o.N, ch, do_exchange, thin, save_offset ? *save_offset : 0);
-        hipError_t e = launch_pt_lane_k1(c->p, L, s->d_scratch, k1, pt_ens_buffers(s), !s->factor_loaded, c->stream);
-        if (e == hipSuccess) {
-            s->factor_loaded = true;
-            s->chol_stale = true;
-            e = hipStreamSynchronize(c->stream);
-        }
-        if (e != hipSuccess) return hip_fail(e, "carma_bands_pt: sampler launch");
-        pt_ens_advance(s, ch, thin, save_offset);
-        left -= ch;
-    }
-    return CARMA_OK;
+    f.which = [s](size_t k) {
+        char buf[96];
+        snprintf(buf, sizeof(buf), "chain %zu (temperature %zu of replica %zu)", k, k % (size_t)s->T, k / (size_t)s->T);
+        return std::string(buf);
+    };
+    return f;
 }
 
 }  // namespace carma
@@ -199,199 +186,32 @@ int carma_bands_pt_create(carma_bands* h, int ntemps, int nreplicas, const doubl
 
 int carma_bands_pt_set_chains(carma_bands* h, const double* theta, const double* logpost)
 {
-    BptState* s = bpt_state(h, "carma_bands_pt_set_chains", false);
-    if (!s) return CARMA_EINVAL;
-    if (!theta) {
-        set_error("carma_bands_pt_set_chains: null theta");
-        return CARMA_EINVAL;
-    }
-    Bctx* c = reinterpret_cast<Bctx*>(h);
-    const size_t nchain = s->nchain();
-    std::vector<double> lp(nchain);
-    if (logpost) {
-        std::memcpy(lp.data(), logpost, sizeof(double) * nchain);
-    } else {
-        const int rc = bpt_logdens_host(h, s, theta, nchain, lp.data());
-        if (rc != CARMA_OK) return rc;
-    }
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = pt_ens_set_chains(s, c->dx, theta, lp.data());
-    if (e != hipSuccess) return hip_fail(e, "carma_bands_pt_set_chains");
-    s->started = true;
-    return CARMA_OK;
+    return pt_front_set_chains(bpt_front(h), theta, logpost);
 }
 
-int carma_bands_pt_get_chains(carma_bands* h, double* theta, double* logpost)
-{
-    BptState* s = bpt_state(h, "carma_bands_pt_get_chains", false);
-    if (!s) return CARMA_EINVAL;
-    Bctx* c = reinterpret_cast<Bctx*>(h);
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = pt_ens_get_chains(s, c->dx, theta, logpost);
-    if (e != hipSuccess) return hip_fail(e, "carma_bands_pt_get_chains");
-    return CARMA_OK;
-}
+int carma_bands_pt_get_chains(carma_bands* h, double* theta, double* logpost) { return pt_front_get_chains(bpt_front(h), theta, logpost); }
 
-int carma_bands_pt_start(carma_bands* h, const double* init)
-{
-    BptState* s = bpt_state(h, "carma_bands_pt_start", false);
-    if (!s) return CARMA_EINVAL;
-    Bctx* c = reinterpret_cast<Bctx*>(h);
-    const int dx = c->dx;
-    const size_t nchain = s->nchain();
-    std::vector<double> theta(nchain * dx), lp(nchain, -std::numeric_limits<double>::infinity());
-    std::vector<char> done(nchain, 0);
-    // the init row is honoured when its log-density is finite (src/samplers.cpp:75-93): it becomes every chain of the run
-    if (init) {
-        double l0 = 0.0;
-        const int rc = bpt_logdens_host(h, s, init, 1, &l0);
-        if (rc != CARMA_OK) return rc;
-        if (std::isfinite(l0))
-            for (size_t k = 0; k < nchain; k++) {
-                std::memcpy(&theta[k * dx], init, sizeof(double) * dx);
-                lp[k] = l0;
-                done[k] = 1;
-            }
-    }
-    const std::vector<BandView> bands = band_views(c);
-    const int rc = find_starts(
-        nchain, dx, theta.data(), lp.data(), done.data(),
-        [&](size_t k, int round, double* out) {
-            mband_pt_draw_start(bands.data(), c->K, c->o.pr, c->p, c->q, c->o.lagbox.data(), s->seed, (uint64_t)k, round, out);
-        },
-        [&](const double* cand, const size_t*, size_t m, double* out) { return bpt_logdens_host(h, s, cand, m, out); });
-    if (rc != CARMA_OK) return rc;
-    for (size_t k = 0; k < nchain; k++)
-        if (!done[k]) {
-            set_error("carma_bands_pt_start: no finite starting value found for chain %zu (temperature %zu of replica %zu)", k,
-                      k % (size_t)s->T, k / (size_t)s->T);
-            return CARMA_EINVAL;
-        }
-    return carma_bands_pt_set_chains(h, theta.data(), lp.data());
-}
+int carma_bands_pt_start(carma_bands* h, const double* init) { return pt_front_start(bpt_front(h), init); }
 
-int carma_bands_pt_get_factor(carma_bands* h, double* chol)
-{
-    BptState* s = bpt_state(h, "carma_bands_pt_get_factor", false);
-    if (!s) return CARMA_EINVAL;
-    if (!chol) {
-        set_error("carma_bands_pt_get_factor: null chol");
-        return CARMA_EINVAL;
-    }
-    Bctx* c = reinterpret_cast<Bctx*>(h);
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = pt_ens_get_factor(s, c->dx, c->stream, chol);
-    if (e != hipSuccess) return hip_fail(e, "carma_bands_pt_get_factor");
-    return CARMA_OK;
-}
+int carma_bands_pt_get_factor(carma_bands* h, double* chol) { return pt_front_get_factor(bpt_front(h), chol); }
 
-int carma_bands_pt_set_factor(carma_bands* h, const double* chol)
-{
-    BptState* s = bpt_state(h, "carma_bands_pt_set_factor", false);
-    if (!s) return CARMA_EINVAL;
-    if (!chol) {
-        set_error("carma_bands_pt_set_factor: null chol");
-        return CARMA_EINVAL;
-    }
-    Bctx* c = reinterpret_cast<Bctx*>(h);
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = pt_ens_set_factor(s, c->dx, c->stream, chol);
-    if (e != hipSuccess) return hip_fail(e, "carma_bands_pt_set_factor");
-    return CARMA_OK;
-}
+int carma_bands_pt_set_factor(carma_bands* h, const double* chol) { return pt_front_set_factor(bpt_front(h), chol); }
 
-int carma_bands_pt_iterate(carma_bands* h, long niter, int do_exchange)
-{
-    BptState* s = bpt_state(h, "carma_bands_pt_iterate", true);
-    if (!s) return CARMA_EINVAL;
-    if (niter < 0) {
-        set_error("carma_bands_pt_iterate: niter < 0");
-        return CARMA_EINVAL;
-    }
-    Bctx* c = reinterpret_cast<Bctx*>(h);
-    const hipError_t e = hipSetDevice(c->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    return bpt_iterate(c, niter, do_exchange, 0, nullptr);
-}
+int carma_bands_pt_iterate(carma_bands* h, long niter, int do_exchange) { return pt_front_iterate(bpt_front(h), niter, do_exchange); }
 
 int carma_bands_pt_sample(carma_bands* h, int nsamples, int thin, double* samples, double* logposts)
 {
-    BptState* s = bpt_state(h, "carma_bands_pt_sample", true);
-    if (!s) return CARMA_EINVAL;
-    if (nsamples < 1 || thin < 1 || !samples || !logposts) {
-        set_error("carma_bands_pt_sample: bad argument (nsamples >= 1, thin >= 1, non-null outputs)");
-        return CARMA_EINVAL;
-    }
-    Bctx* c = reinterpret_cast<Bctx*>(h);
-    hipError_t e = hipSetDevice(c->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    long capacity = 0;
-    e = s->reserve_samples(c->dx, nsamples, &capacity);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("carma_bands_pt_sample: no device memory for the sample buffer: %zu bytes asked for (%ld ladders x %d samples x %d)",
-                  sizeof(double) * (size_t)s->R * nsamples * (c->dx + 1), (long)s->R, nsamples, c->dx);
-        return CARMA_ENOMEM;
-    }
-    long off = 0;
-    int rc = bpt_iterate(c, (long)nsamples * thin, 1, thin, &off);
-    if (rc == CARMA_OK) {
-        e = pt_ens_fetch_samples(s, c->dx, nsamples, samples, logposts);
-        if (e != hipSuccess) rc = hip_fail(e, "carma_bands_pt_sample: D2H");
-    }
-    s->cap = capacity;
-    return rc;
+    return pt_front_sample(bpt_front(h), nsamples, thin, samples, logposts);
 }
 
 int carma_bands_pt_stats(carma_bands* h, double* accept_rate, double* swap_rate, int reset)
 {
-    BptState* s = bpt_state(h, "carma_bands_pt_stats", false);
-    if (!s) return CARMA_EINVAL;
-    Bctx* c = reinterpret_cast<Bctx*>(h);
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = pt_ens_stats(s, accept_rate, swap_rate, reset);
-    if (e != hipSuccess) return hip_fail(e, "carma_bands_pt_stats");
-    return CARMA_OK;
+    return pt_front_stats(bpt_front(h), accept_rate, swap_rate, reset);
 }
 
-long carma_bands_pt_iterations_done(const carma_bands* h)
-{
-    if (!h || !reinterpret_cast<const Bctx*>(h)->bpt) return CARMA_EINVAL;
-    return (long)reinterpret_cast<const Bctx*>(h)->bpt->iter;
-}
+long carma_bands_pt_iterations_done(const carma_bands* h) { return pt_front_iterations_done(bpt_front(const_cast<carma_bands*>(h))); }
 
-int carma_bands_pt_logdensity(carma_bands* h, const double* theta, double* out)
-{
-    BptState* s = bpt_state(h, "carma_bands_pt_logdensity", false);
-    if (!s) return CARMA_EINVAL;
-    if (!theta || !out) {
-        set_error("carma_bands_pt_logdensity: null theta or out");
-        return CARMA_EINVAL;
-    }
-    Bctx* c = reinterpret_cast<Bctx*>(h);
-    const size_t nchain = s->nchain(), GUARD = 64;
-    // [nc][dx] proposals, [nc] results, then GUARD words nobody may write: a kernel whose idle lanes stored would show here
-    std::vector<double> res(nchain + GUARD, 0.0);
-    const double mark = -12345.678;
-    std::fill(res.begin() + nchain, res.end(), mark);
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = c->d_theta.need(sizeof(double) * (nchain * c->dx + nchain + GUARD));
-    double *d_th = c->d_theta.as<double>(), *d_ll = d_th + nchain * c->dx;
-    if (e == hipSuccess) e = hipMemcpyAsync(d_th, theta, sizeof(double) * nchain * c->dx, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_ll, res.data(), sizeof(double) * res.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_logdens_mband_chains(c, s, d_th, (long)nchain, d_ll, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(res.data(), d_ll, sizeof(double) * res.size(), hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return hip_fail(e, "carma_bands_pt_logdensity");
-    for (size_t k = nchain; k < res.size(); k++)
-        if (res[k] != mark) {
-            set_error("carma_bands_pt_logdensity: the kernel wrote past its %zu results", nchain);
-            return CARMA_EHIP;
-        }
-    std::memcpy(out, res.data(), sizeof(double) * nchain);
-    return CARMA_OK;
-}
+int carma_bands_pt_logdensity(carma_bands* h, const double* theta, double* out) { return pt_front_logdensity(bpt_front(h), theta, out); }
 
 int carma_bands_pt_kernel_name(const carma_bands* h, char* buf, int len)
 {
@@ -403,11 +223,8 @@ int carma_bands_pt_kernel_name(const carma_bands* h, char* buf, int len)
 int carma_bands_pt_run(carma_bands* h, int ntemps, int nreplicas, int sample_size, int burnin, int thin, const double* init,
                        uint64_t seed, const double* band_lo, const double* band_hi, double* samples, double* logposts)
 {
-    int rc = carma_bands_pt_create(h, ntemps, nreplicas, nullptr, burnin, seed, band_lo, band_hi);
-    if (rc == CARMA_OK) rc = carma_bands_pt_start(h, init);
-    if (rc == CARMA_OK) rc = carma_bands_pt_iterate(h, burnin, 1);                     // Sampler::Run burn-in (samplers.cpp:97)
-    if (rc == CARMA_OK) rc = carma_bands_pt_sample(h, sample_size, thin, samples, logposts);   // :101-108
-    return rc;
+    const int rc = carma_bands_pt_create(h, ntemps, nreplicas, nullptr, burnin, seed, band_lo, band_hi);
+    return rc == CARMA_OK ? pt_front_run(bpt_front(h), init, burnin, sample_size, thin, samples, logposts) : rc;
 }
 
 }  // extern "C"

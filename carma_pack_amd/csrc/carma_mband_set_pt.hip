@@ -13,7 +13,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <limits>
@@ -26,6 +25,7 @@
 #include "carma_host.h"
 #include "carma_mband_set_ctx.h"
 #include "carma_mband_set_pt_plan.h"
+#include "carma_pt_front.h"
 
 namespace carma {
 
@@ -96,26 +96,6 @@ static hipError_t launch_logdens_mband_chains_ms(const BSctx* c, const BSptState
     return for_order(c->p, hipErrorInvalidValue, go);
 }
 
-// the sampler state of h, or null with the error set: `who` was called before carma_bandset_pt_create (need_start: or before the
-// chains have starting values)
-static BSptState* bspt_state(carma_bandset* h, const char* who, bool need_start)
-{
-    if (!h) {
-        set_error("%s: null context", who);
-        return nullptr;
-    }
-    BSptState* s = reinterpret_cast<BSctx*>(h)->bspt.get();
-    if (!s) {
-        set_error("%s: call carma_bandset_pt_create first", who);
-        return nullptr;
-    }
-    if (need_start && !s->started) {
-        set_error("%s: chains have no starting values (carma_bandset_pt_start / carma_bandset_pt_set_chains)", who);
-        return nullptr;
-    }
-    return s;
-}
-
 // the bands of object s as the functions of carma_mband_pt_plan.h take them
 static std::vector<BandView> band_views(const BSctx* c, int s)
 {
@@ -153,30 +133,51 @@ static int bspt_logdens_host(carma_bandset* h, const BSptState* s, const double*
     return CARMA_OK;
 }
 
-// niter iterations, a chunk in flight at a time.  thin > 0: save the coldest chains every thin iterations from sample *save_offset
-// on.  The stream is idle when this returns, whatever happened.
-static int bspt_iterate(BSctx* c, long niter, int do_exchange, int thin, long* save_offset)
+// The sampler of h as the shared front drives it (carma_pt_front.h).  A row is evaluated on the object, and inside the box, of its
+// chain's run; chain k draws from ITS object with the generator its slot in the ensemble keys, so run j draws what
+// carma_bands_pt_start draws for ladders j R ... on a handle of its object.
+static PtFront bspt_front(carma_bandset* h)
 {
+    PtFront f;
+    f.name = "carma_bandset_pt";
+    if (!h) return f;
+    BSctx* c = reinterpret_cast<BSctx*>(h);
     BSptState* s = c->bspt.get();
-    const PtLaneK1 k1 = [c, s](const double* thn, long nc, double* ll, hipStream_t st) {
-        return launch_logdens_mband_chains_ms(c, s, thn, nc, ll, st);
+    f.has_ctx = true;
+    f.device = c->device;
+    f.stream = c->stream;
+    f.p = c->p;
+    f.q = c->q;
+    f.dim = c->dx;
+    f.s = s;
+    if (!s) return f;
+    const size_t per_run = (size_t)s->reps * s->T;
+    f.M = (size_t)s->M;
+    f.per_run = per_run;
+    f.n = s->nmax;
+    f.chunk0 = s->chunk0;
+    f.guard = &s->k_res;
+    f.k1 = [c, s](const double* thn, long nc, double* ll, hipStream_t st) { return launch_logdens_mband_chains_ms(c, s, thn, nc, ll, st); };
+    f.eval = [h, s, per_run](const double* rows, const size_t* chain, size_t m, double* out) {
+        std::vector<int> run(m);
+        for (size_t i = 0; i < m; i++) run[i] = (int)((chain ? chain[i] : i) / per_run);
+        return bspt_logdens_host(h, s, rows, run.data(), m, out);
     };
-    long left = niter;
-    while (left > 0) {
-        const long ch = pt_next_chunk(left, s->chunk0, thin);
-        const PtLaunch L = pt_ens_launch(s, c->dx, c->q, s->nmax, ch, do_exchange, thin, save_offset ? *save_offset : 0);
-        hipError_t e = launch_pt_lane_k1(c->p, L, s->d_scratch, k1, pt_ens_buffers(s), !s->factor_loaded, c->stream);
-        if (e == hipSuccess) {
-            s->factor_loaded = true;
-            s->chol_stale = true;
-        }
-        const hipError_t es = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = es;
-        if (e != hipSuccess) return hip_fail(e, "carma_bandset_pt: sampler launch");
-        pt_ens_advance(s, ch, thin, save_offset);
-        left -= ch;
-    }
-    return CARMA_OK;
+    // (the runs' band views are made at the first draw: only start draws)
+    f.draw = [c, s, per_run, views = std::vector<std::vector<BandView>>()](size_t k, int round, double* out) mutable {
+        if (views.empty())
+            for (int j = 0; j < s->M; j++) views.push_back(band_views(c, s->run_obj[j]));
+        const size_t j = k / per_run;
+        const int sj = s->run_obj[j];
+        mband_pt_draw_start(views[j].data(), c->K, c->m.pr[sj], c->p, c->q, c->m.lagbox.data() + (size_t)sj * 2 * (c->K - 1), s->seed,
+                            (uint64_t)k, round, out);
+    };
+    f.which = [s, per_run](size_t k) {
+        char buf[96];
+        snprintf(buf, sizeof(buf), "chain %zu of run %zu (object %d)", k % per_run, k / per_run, s->run_obj[k / per_run]);
+        return std::string(buf);
+    };
+    return f;
 }
 
 }  // namespace carma
@@ -259,223 +260,40 @@ int carma_bandset_pt_create(carma_bandset* h, const int* run_obj, int M, int nte
 
 int carma_bandset_pt_set_chains(carma_bandset* h, const double* theta, const double* logpost)
 {
-    BSptState* s = bspt_state(h, "carma_bandset_pt_set_chains", false);
-    if (!s) return CARMA_EINVAL;
-    if (!theta) {
-        set_error("carma_bandset_pt_set_chains: null theta");
-        return CARMA_EINVAL;
-    }
-    BSctx* c = reinterpret_cast<BSctx*>(h);
-    const size_t nchain = s->nchain(), per_run = (size_t)s->reps * s->T;
-    std::vector<double> lp(nchain);
-    if (logpost) {
-        std::memcpy(lp.data(), logpost, sizeof(double) * nchain);
-    } else {
-        std::vector<int> run(nchain);
-        for (size_t k = 0; k < nchain; k++) run[k] = (int)(k / per_run);
-        const int rc = bspt_logdens_host(h, s, theta, run.data(), nchain, lp.data());
-        if (rc != CARMA_OK) return rc;
-    }
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = pt_ens_set_chains(s, c->dx, theta, lp.data());
-    if (e != hipSuccess) return hip_fail(e, "carma_bandset_pt_set_chains");
-    s->started = true;
-    return CARMA_OK;
+    return pt_front_set_chains(bspt_front(h), theta, logpost);
 }
 
 int carma_bandset_pt_get_chains(carma_bandset* h, double* theta, double* logpost)
 {
-    BSptState* s = bspt_state(h, "carma_bandset_pt_get_chains", false);
-    if (!s) return CARMA_EINVAL;
-    BSctx* c = reinterpret_cast<BSctx*>(h);
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = pt_ens_get_chains(s, c->dx, theta, logpost);
-    if (e != hipSuccess) return hip_fail(e, "carma_bandset_pt_get_chains");
-    return CARMA_OK;
+    return pt_front_get_chains(bspt_front(h), theta, logpost);
 }
 
-int carma_bandset_pt_start(carma_bandset* h, const double* init)
-{
-    BSptState* s = bspt_state(h, "carma_bandset_pt_start", false);
-    if (!s) return CARMA_EINVAL;
-    BSctx* c = reinterpret_cast<BSctx*>(h);
-    const int dx = c->dx, M = s->M;
-    const size_t per_run = (size_t)s->reps * s->T, nchain = s->nchain();
-    std::vector<double> theta(nchain * dx), lp(nchain, -std::numeric_limits<double>::infinity());
-    std::vector<char> done(nchain, 0);
-    std::vector<int> run;
-    // a run's init row is honoured when its log-density on the run's object is finite (and inside the run's box): it becomes
-    // every chain of that run; all M rows in one launch
-    if (init) {
-        std::vector<double> l0((size_t)M);
-        run.resize((size_t)M);
-        for (int j = 0; j < M; j++) run[j] = j;
-        const int rc = bspt_logdens_host(h, s, init, run.data(), (size_t)M, l0.data());
-        if (rc != CARMA_OK) return rc;
-        for (int j = 0; j < M; j++) {
-            if (!std::isfinite(l0[j])) continue;
-            for (size_t k = j * per_run; k < (j + 1) * per_run; k++) {
-                std::memcpy(&theta[k * dx], init + (size_t)j * dx, sizeof(double) * dx);
-                lp[k] = l0[j];
-                done[k] = 1;
-            }
-        }
-    }
-    // Drawn starts: chain k = ladder T + temperature of the ENSEMBLE keys its generator, so run j draws what carma_bands_pt_start
-    // draws for ladders j R ... on a handle of its object; the candidates still pending of ALL runs are evaluated in one launch
-    // per round.
-    std::vector<std::vector<BandView>> views((size_t)M);
-    for (int j = 0; j < M; j++) views[j] = band_views(c, s->run_obj[j]);
-    const int rc = find_starts(
-        nchain, dx, theta.data(), lp.data(), done.data(),
-        [&](size_t k, int round, double* out) {
-            const size_t j = k / per_run;
-            const int sj = s->run_obj[j];
-            mband_pt_draw_start(views[j].data(), c->K, c->m.pr[sj], c->p, c->q, c->m.lagbox.data() + (size_t)sj * 2 * (c->K - 1), s->seed,
-                                (uint64_t)k, round, out);
-        },
-        [&](const double* cand, const size_t* idx, size_t m, double* out) {
-            run.resize(m);
-            for (size_t i = 0; i < m; i++) run[i] = (int)(idx[i] / per_run);
-            return bspt_logdens_host(h, s, cand, run.data(), m, out);
-        });
-    if (rc != CARMA_OK) return rc;
-    for (size_t k = 0; k < nchain; k++)
-        if (!done[k]) {
-            set_error("carma_bandset_pt_start: no finite starting value found for chain %zu of run %zu (object %d)", k % per_run,
-                      k / per_run, s->run_obj[k / per_run]);
-            return CARMA_EINVAL;
-        }
-    return carma_bandset_pt_set_chains(h, theta.data(), lp.data());
-}
+int carma_bandset_pt_start(carma_bandset* h, const double* init) { return pt_front_start(bspt_front(h), init); }
 
-int carma_bandset_pt_get_factor(carma_bandset* h, double* chol)
-{
-    BSptState* s = bspt_state(h, "carma_bandset_pt_get_factor", false);
-    if (!s) return CARMA_EINVAL;
-    if (!chol) {
-        set_error("carma_bandset_pt_get_factor: null chol");
-        return CARMA_EINVAL;
-    }
-    BSctx* c = reinterpret_cast<BSctx*>(h);
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = pt_ens_get_factor(s, c->dx, c->stream, chol);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(c->stream);
-        return hip_fail(e, "carma_bandset_pt_get_factor");
-    }
-    return CARMA_OK;
-}
+int carma_bandset_pt_get_factor(carma_bandset* h, double* chol) { return pt_front_get_factor(bspt_front(h), chol); }
 
-int carma_bandset_pt_set_factor(carma_bandset* h, const double* chol)
-{
-    BSptState* s = bspt_state(h, "carma_bandset_pt_set_factor", false);
-    if (!s) return CARMA_EINVAL;
-    if (!chol) {
-        set_error("carma_bandset_pt_set_factor: null chol");
-        return CARMA_EINVAL;
-    }
-    BSctx* c = reinterpret_cast<BSctx*>(h);
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = pt_ens_set_factor(s, c->dx, c->stream, chol);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(c->stream);
-        return hip_fail(e, "carma_bandset_pt_set_factor");
-    }
-    return CARMA_OK;
-}
+int carma_bandset_pt_set_factor(carma_bandset* h, const double* chol) { return pt_front_set_factor(bspt_front(h), chol); }
 
-int carma_bandset_pt_iterate(carma_bandset* h, long niter, int do_exchange)
-{
-    BSptState* s = bspt_state(h, "carma_bandset_pt_iterate", true);
-    if (!s) return CARMA_EINVAL;
-    if (niter < 0) {
-        set_error("carma_bandset_pt_iterate: niter < 0");
-        return CARMA_EINVAL;
-    }
-    BSctx* c = reinterpret_cast<BSctx*>(h);
-    const hipError_t e = hipSetDevice(c->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    return bspt_iterate(c, niter, do_exchange, 0, nullptr);
-}
+int carma_bandset_pt_iterate(carma_bandset* h, long niter, int do_exchange) { return pt_front_iterate(bspt_front(h), niter, do_exchange); }
 
 int carma_bandset_pt_sample(carma_bandset* h, int nsamples, int thin, double* samples, double* logposts)
 {
-    BSptState* s = bspt_state(h, "carma_bandset_pt_sample", true);
-    if (!s) return CARMA_EINVAL;
-    if (nsamples < 1 || thin < 1 || !samples || !logposts) {
-        set_error("carma_bandset_pt_sample: bad argument (nsamples >= 1, thin >= 1, non-null outputs)");
-        return CARMA_EINVAL;
-    }
-    BSctx* c = reinterpret_cast<BSctx*>(h);
-    hipError_t e = hipSetDevice(c->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    long capacity = 0;
-    e = s->reserve_samples(c->dx, nsamples, &capacity);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("carma_bandset_pt_sample: no device memory for the sample buffer: %zu bytes asked for (%ld ladders x %d samples x %d)",
-                  sizeof(double) * (size_t)s->R * nsamples * (c->dx + 1), (long)s->R, nsamples, c->dx);
-        return CARMA_ENOMEM;
-    }
-    long off = 0;
-    int rc = bspt_iterate(c, (long)nsamples * thin, 1, thin, &off);
-    if (rc == CARMA_OK) {
-        e = pt_ens_fetch_samples(s, c->dx, nsamples, samples, logposts);
-        if (e != hipSuccess) rc = hip_fail(e, "carma_bandset_pt_sample: D2H");
-    }
-    s->cap = capacity;
-    return rc;
+    return pt_front_sample(bspt_front(h), nsamples, thin, samples, logposts);
 }
 
 int carma_bandset_pt_stats(carma_bandset* h, double* accept_rate, double* swap_rate, int reset)
 {
-    BSptState* s = bspt_state(h, "carma_bandset_pt_stats", false);
-    if (!s) return CARMA_EINVAL;
-    BSctx* c = reinterpret_cast<BSctx*>(h);
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = pt_ens_stats(s, accept_rate, swap_rate, reset);
-    if (e != hipSuccess) return hip_fail(e, "carma_bandset_pt_stats");
-    return CARMA_OK;
+    return pt_front_stats(bspt_front(h), accept_rate, swap_rate, reset);
 }
 
 long carma_bandset_pt_iterations_done(const carma_bandset* h)
 {
-    if (!h || !reinterpret_cast<const BSctx*>(h)->bspt) return CARMA_EINVAL;
-    return (long)reinterpret_cast<const BSctx*>(h)->bspt->iter;
+    return pt_front_iterations_done(bspt_front(const_cast<carma_bandset*>(h)));
 }
 
 int carma_bandset_pt_logdensity(carma_bandset* h, const double* theta, double* out)
 {
-    BSptState* s = bspt_state(h, "carma_bandset_pt_logdensity", false);
-    if (!s) return CARMA_EINVAL;
-    if (!theta || !out) {
-        set_error("carma_bandset_pt_logdensity: null theta or out");
-        return CARMA_EINVAL;
-    }
-    BSctx* c = reinterpret_cast<BSctx*>(h);
-    const size_t nchain = s->nchain(), GUARD = 64;
-    // [nc][dx] proposals, [nc] results, then GUARD words nobody may write: a kernel whose pad lanes stored would show here
-    std::vector<double> res(nchain + GUARD, 0.0);
-    const double mark = -12345.678;
-    std::fill(res.begin() + nchain, res.end(), mark);
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = s->k_res.need(sizeof(double) * (nchain * c->dx + nchain + GUARD));
-    double *d_th = s->k_res.as<double>(), *d_ll = d_th + nchain * c->dx;
-    if (e == hipSuccess) e = hipMemcpyAsync(d_th, theta, sizeof(double) * nchain * c->dx, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_ll, res.data(), sizeof(double) * res.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_logdens_mband_chains_ms(c, s, d_th, (long)nchain, d_ll, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(res.data(), d_ll, sizeof(double) * res.size(), hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return hip_fail(e, "carma_bandset_pt_logdensity");
-    for (size_t k = nchain; k < res.size(); k++)
-        if (res[k] != mark) {
-            set_error("carma_bandset_pt_logdensity: the kernel wrote past its %zu results", nchain);
-            return CARMA_EHIP;
-        }
-    std::memcpy(out, res.data(), sizeof(double) * nchain);
-    return CARMA_OK;
+    return pt_front_logdensity(bspt_front(h), theta, out);
 }
 
 int carma_bandset_pt_kernel_name(const carma_bandset* h, char* buf, int len)
@@ -489,11 +307,8 @@ int carma_bandset_pt_run(carma_bandset* h, const int* run_obj, int M, int ntemps
                          const double* init, uint64_t seed, const double* band_lo, const double* band_hi, double* samples,
                          double* logposts)
 {
-    int rc = carma_bandset_pt_create(h, run_obj, M, ntemps, nreplicas, nullptr, burnin, seed, band_lo, band_hi);
-    if (rc == CARMA_OK) rc = carma_bandset_pt_start(h, init);
-    if (rc == CARMA_OK) rc = carma_bandset_pt_iterate(h, burnin, 1);                     // Sampler::Run burn-in (samplers.cpp:97)
-    if (rc == CARMA_OK) rc = carma_bandset_pt_sample(h, sample_size, thin, samples, logposts);   // :101-108
-    return rc;
+    const int rc = carma_bandset_pt_create(h, run_obj, M, ntemps, nreplicas, nullptr, burnin, seed, band_lo, band_hi);
+    return rc == CARMA_OK ? pt_front_run(bspt_front(h), init, burnin, sample_size, thin, samples, logposts) : rc;
 }
 
 }  // extern "C"

@@ -7,16 +7,15 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <limits>
 #include <vector>
 
 #include "grp_device.h"
 #include "carma_core.h"
 #include "carma_lane.h"
 #include "carma_mseries.h"
+#include "carma_pt_front.h"
 
 namespace carma {
 
@@ -90,57 +89,46 @@ static hipError_t launch_logdens_chains_ms(const Mctx* c, const MptState* s, con
     return hipSuccess;
 }
 
-// the sampler state of h, or null with the error set: `who` was called before carma_mpt_create (need_start: or before the
-// chains have starting values)
-static MptState* mpt_state(carma_mctx* h, const char* who, bool need_start)
+// The sampler of h as the shared front drives it (carma_pt_front.h).  A row is evaluated by carma_mlogdensity_batch on the series of
+// its chain's run; chain k draws from ITS series with the generator its slot in the ensemble keys.
+static PtFront mpt_front(carma_mctx* h)
 {
-    if (!h) {
-        set_error("%s: null context", who);
-        return nullptr;
-    }
-    MptState* s = reinterpret_cast<Mctx*>(h)->mpt.get();
-    if (!s) {
-        set_error("%s: call carma_mpt_create first", who);
-        return nullptr;
-    }
-    if (need_start && !s->started) {
-        set_error("%s: chains have no starting values (carma_mpt_start / carma_mpt_set_chains)", who);
-        return nullptr;
-    }
-    return s;
-}
-
-// Iterations per chunk: the K1 of an iteration runs as long as its longest series (>= ~0.45 us per datum, as chunk_iters of the
-// single-series lane sampler), 2-3 launches each; around a quarter of a second, at most 4096 iterations, are in flight at a time.
-static long mpt_chunk_iters(const MptState* s)
-{
-    const double est_us = std::max(1.0, 0.45 * s->nmax);
-    return (long)std::max(1.0, std::min(4096.0, 250000.0 / est_us));
-}
-
-// niter iterations, a chunk in flight at a time.  thin > 0: save the coldest chains every thin iterations from sample *save_offset on
-static int mpt_iterate(Mctx* c, long niter, int do_exchange, int thin, long* save_offset)
-{
+    PtFront f;
+    f.name = "carma_mpt";
+    if (!h) return f;
+    Mctx* c = reinterpret_cast<Mctx*>(h);
     MptState* s = c->mpt.get();
-    const long chunk0 = mpt_chunk_iters(s);
-    const PtLaneK1 k1 = [c, s](const double* thn, long nc, double* ll, hipStream_t st) {
-        return launch_logdens_chains_ms(c, s, thn, nc, ll, st);
+    f.has_ctx = true;
+    f.device = c->device;
+    f.stream = c->stream;
+    f.p = c->p;
+    f.q = c->q;
+    f.dim = c->d;
+    f.s = s;
+    f.guard = &c->k_res;
+    if (!s) return f;
+    const size_t per_run = (size_t)s->reps * s->T;
+    f.M = (size_t)s->M;
+    f.per_run = per_run;
+    f.n = s->nmax;
+    f.chunk0 = s->chunk0;
+    f.k1 = [c, s](const double* thn, long nc, double* ll, hipStream_t st) { return launch_logdens_chains_ms(c, s, thn, nc, ll, st); };
+    f.eval = [h, s, per_run](const double* rows, const size_t* chain, size_t m, double* out) {
+        std::vector<int> which(m);
+        for (size_t i = 0; i < m; i++) which[i] = s->series[(chain ? chain[i] : i) / per_run];
+        return carma_mlogdensity_batch(h, rows, which.data(), (int)m, 0, out);
     };
-    long left = niter;
-    while (left > 0) {
-        const long ch = pt_next_chunk(left, chunk0, thin);
-        const PtLaunch L = pt_ens_launch(s, c->d, c->q, s->nmax, ch, do_exchange, thin, save_offset ? *save_offset : 0);
-        hipError_t e = launch_pt_lane_k1(c->p, L, s->d_scratch, k1, pt_ens_buffers(s), !s->factor_loaded, c->stream);
-        if (e == hipSuccess) {
-            s->factor_loaded = true;
-            s->chol_stale = true;
-            e = hipStreamSynchronize(c->stream);
-        }
-        if (e != hipSuccess) return hip_fail(e, "carma_mpt: sampler launch");
-        pt_ens_advance(s, ch, thin, save_offset);
-        left -= ch;
-    }
-    return CARMA_OK;
+    f.draw = [c, s, per_run](size_t k, int round, double* out) {
+        const int sj = s->series[k / per_run];
+        std::mt19937_64 rng = start_rng(s->seed, (uint64_t)k, round);
+        draw_start(c->t.data() + c->hoff[sj], c->y.data() + c->hoff[sj], c->n[sj], c->pr[sj], c->p, c->q, rng, out);
+    };
+    f.which = [s, per_run](size_t k) {
+        char buf[96];
+        snprintf(buf, sizeof(buf), "chain %zu of run %zu (series %d)", k % per_run, k / per_run, s->series[k / per_run]);
+        return std::string(buf);
+    };
+    return f;
 }
 
 }  // namespace carma
@@ -203,6 +191,7 @@ int carma_mpt_create(carma_mctx* h, const int* series, int M, int ntemps, int nr
             std::memcpy(&chol[k * d * d], R0.data(), sizeof(double) * d * d);
         for (int r = 0; r < nreplicas; r++) lser[(size_t)j * nreplicas + r] = sj;
     }
+    s->chunk0 = mpt_chunk_iters(s->nmax);
     e = pt_ens_create(s, ntemps, nlad, d, temps, chol.data());
     if (e == hipSuccess) e = s->d_lser.alloc(lser.size());
     if (e == hipSuccess) e = s->d_rep.alloc((size_t)c->S);
@@ -218,204 +207,32 @@ int carma_mpt_create(carma_mctx* h, const int* series, int M, int ntemps, int nr
 
 int carma_mpt_set_chains(carma_mctx* h, const double* theta, const double* logpost)
 {
-    MptState* s = mpt_state(h, "carma_mpt_set_chains", false);
-    if (!s) return CARMA_EINVAL;
-    if (!theta) {
-        set_error("carma_mpt_set_chains: null theta");
-        return CARMA_EINVAL;
-    }
-    Mctx* c = reinterpret_cast<Mctx*>(h);
-    const size_t nchain = s->nchain();
-    std::vector<double> lp(nchain);
-    if (logpost) {
-        std::memcpy(lp.data(), logpost, sizeof(double) * nchain);
-    } else {
-        std::vector<int> which(nchain);
-        for (size_t k = 0; k < nchain; k++) which[k] = s->series[k / ((size_t)s->reps * s->T)];
-        const int rc = carma_mlogdensity_batch(h, theta, which.data(), (int)nchain, 0, lp.data());
-        if (rc != CARMA_OK) return rc;
-    }
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = pt_ens_set_chains(s, c->d, theta, lp.data());
-    if (e != hipSuccess) return hip_fail(e, "carma_mpt_set_chains");
-    s->started = true;
-    return CARMA_OK;
+    return pt_front_set_chains(mpt_front(h), theta, logpost);
 }
 
-int carma_mpt_get_chains(carma_mctx* h, double* theta, double* logpost)
-{
-    MptState* s = mpt_state(h, "carma_mpt_get_chains", false);
-    if (!s) return CARMA_EINVAL;
-    Mctx* c = reinterpret_cast<Mctx*>(h);
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = pt_ens_get_chains(s, c->d, theta, logpost);
-    if (e != hipSuccess) return hip_fail(e, "carma_mpt_get_chains");
-    return CARMA_OK;
-}
+int carma_mpt_get_chains(carma_mctx* h, double* theta, double* logpost) { return pt_front_get_chains(mpt_front(h), theta, logpost); }
 
-int carma_mpt_start(carma_mctx* h, const double* init)
-{
-    MptState* s = mpt_state(h, "carma_mpt_start", false);
-    if (!s) return CARMA_EINVAL;
-    Mctx* c = reinterpret_cast<Mctx*>(h);
-    const int d = c->d, M = s->M;
-    const size_t per_run = (size_t)s->reps * s->T, nchain = s->nchain();
-    std::vector<double> theta(nchain * d), lp(nchain, -std::numeric_limits<double>::infinity());
-    std::vector<char> done(nchain, 0);
-    // a run's init row is honoured when its log-density on the run's series is finite (src/samplers.cpp:75-93): all M rows in one
-    // launch
-    if (init) {
-        std::vector<double> l0(M);
-        const int rc = carma_mlogdensity_batch(h, init, s->series.data(), M, 0, l0.data());
-        if (rc != CARMA_OK) return rc;
-        for (int j = 0; j < M; j++) {
-            if (!std::isfinite(l0[j])) continue;
-            for (size_t k = j * per_run; k < (j + 1) * per_run; k++) {
-                std::memcpy(&theta[k * d], init + (size_t)j * d, sizeof(double) * d);
-                lp[k] = l0[j];
-                done[k] = 1;
-            }
-        }
-    }
-    // Drawn starts: chain k = ladder T + temperature of the ENSEMBLE keys its generator, so run j draws what a single-series sampler
-    // sharded to replica0 = j R draws; the candidates still pending of ALL runs are evaluated in one launch per round.
-    std::vector<int> which;
-    const int rc = find_starts(
-        nchain, d, theta.data(), lp.data(), done.data(),
-        [&](size_t k, int round, double* out) {
-            const int sj = s->series[k / per_run];
-            std::mt19937_64 rng = start_rng(s->seed, (uint64_t)k, round);
-            draw_start(c->t.data() + c->hoff[sj], c->y.data() + c->hoff[sj], c->n[sj], c->pr[sj], c->p, c->q, rng, out);
-        },
-        [&](const double* cand, const size_t* idx, size_t m, double* out) {
-            which.resize(m);
-            for (size_t i = 0; i < m; i++) which[i] = s->series[idx[i] / per_run];
-            return carma_mlogdensity_batch(h, cand, which.data(), (int)m, 0, out);
-        });
-    if (rc != CARMA_OK) return rc;
-    for (size_t k = 0; k < nchain; k++)
-        if (!done[k]) {
-            set_error("carma_mpt_start: no finite starting value found for chain %zu of run %zu (series %d)", k % per_run, k / per_run,
-                      s->series[k / per_run]);
-            return CARMA_EINVAL;
-        }
-    return carma_mpt_set_chains(h, theta.data(), lp.data());
-}
+int carma_mpt_start(carma_mctx* h, const double* init) { return pt_front_start(mpt_front(h), init); }
 
-int carma_mpt_get_factor(carma_mctx* h, double* chol)
-{
-    MptState* s = mpt_state(h, "carma_mpt_get_factor", false);
-    if (!s || !chol) return CARMA_EINVAL;
-    Mctx* c = reinterpret_cast<Mctx*>(h);
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = pt_ens_get_factor(s, c->d, c->stream, chol);
-    if (e != hipSuccess) return hip_fail(e, "carma_mpt_get_factor");
-    return CARMA_OK;
-}
+int carma_mpt_get_factor(carma_mctx* h, double* chol) { return pt_front_get_factor(mpt_front(h), chol); }
 
-int carma_mpt_set_factor(carma_mctx* h, const double* chol)
-{
-    MptState* s = mpt_state(h, "carma_mpt_set_factor", false);
-    if (!s || !chol) return CARMA_EINVAL;
-    Mctx* c = reinterpret_cast<Mctx*>(h);
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = pt_ens_set_factor(s, c->d, c->stream, chol);
-    if (e != hipSuccess) return hip_fail(e, "carma_mpt_set_factor");
-    return CARMA_OK;
-}
+int carma_mpt_set_factor(carma_mctx* h, const double* chol) { return pt_front_set_factor(mpt_front(h), chol); }
 
-int carma_mpt_iterate(carma_mctx* h, long niter, int do_exchange)
-{
-    MptState* s = mpt_state(h, "carma_mpt_iterate", true);
-    if (!s) return CARMA_EINVAL;
-    if (niter < 0) {
-        set_error("carma_mpt_iterate: niter < 0");
-        return CARMA_EINVAL;
-    }
-    Mctx* c = reinterpret_cast<Mctx*>(h);
-    const hipError_t e = hipSetDevice(c->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    return mpt_iterate(c, niter, do_exchange, 0, nullptr);
-}
+int carma_mpt_iterate(carma_mctx* h, long niter, int do_exchange) { return pt_front_iterate(mpt_front(h), niter, do_exchange); }
 
 int carma_mpt_sample(carma_mctx* h, int nsamples, int thin, double* samples, double* logposts)
 {
-    MptState* s = mpt_state(h, "carma_mpt_sample", true);
-    if (!s) return CARMA_EINVAL;
-    if (nsamples < 1 || thin < 1 || !samples || !logposts) {
-        set_error("carma_mpt_sample: bad argument (nsamples >= 1, thin >= 1, non-null outputs)");
-        return CARMA_EINVAL;
-    }
-    Mctx* c = reinterpret_cast<Mctx*>(h);
-    hipError_t e = hipSetDevice(c->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    long capacity = 0;
-    e = s->reserve_samples(c->d, nsamples, &capacity);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("carma_mpt_sample: no device memory for the sample buffer: %zu bytes asked for (%ld ladders x %d samples x %d)",
-                  sizeof(double) * (size_t)s->R * nsamples * (c->d + 1), (long)s->R, nsamples, c->d);
-        return CARMA_ENOMEM;
-    }
-    long off = 0;
-    int rc = mpt_iterate(c, (long)nsamples * thin, 1, thin, &off);
-    if (rc == CARMA_OK) {
-        e = pt_ens_fetch_samples(s, c->d, nsamples, samples, logposts);
-        if (e != hipSuccess) rc = hip_fail(e, "carma_mpt_sample: D2H");
-    }
-    s->cap = capacity;
-    return rc;
+    return pt_front_sample(mpt_front(h), nsamples, thin, samples, logposts);
 }
 
 int carma_mpt_stats(carma_mctx* h, double* accept_rate, double* swap_rate, int reset)
 {
-    MptState* s = mpt_state(h, "carma_mpt_stats", false);
-    if (!s) return CARMA_EINVAL;
-    Mctx* c = reinterpret_cast<Mctx*>(h);
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = pt_ens_stats(s, accept_rate, swap_rate, reset);
-    if (e != hipSuccess) return hip_fail(e, "carma_mpt_stats");
-    return CARMA_OK;
+    return pt_front_stats(mpt_front(h), accept_rate, swap_rate, reset);
 }
 
-long carma_mpt_iterations_done(const carma_mctx* h)
-{
-    if (!h || !reinterpret_cast<const Mctx*>(h)->mpt) return CARMA_EINVAL;
-    return (long)reinterpret_cast<const Mctx*>(h)->mpt->iter;
-}
+long carma_mpt_iterations_done(const carma_mctx* h) { return pt_front_iterations_done(mpt_front(const_cast<carma_mctx*>(h))); }
 
-int carma_mpt_logdensity(carma_mctx* h, const double* theta, double* out)
-{
-    MptState* s = mpt_state(h, "carma_mpt_logdensity", false);
-    if (!s) return CARMA_EINVAL;
-    if (!theta || !out) {
-        set_error("carma_mpt_logdensity: null theta or out");
-        return CARMA_EINVAL;
-    }
-    Mctx* c = reinterpret_cast<Mctx*>(h);
-    const size_t nchain = s->nchain(), GUARD = 64;
-    // [nc][d] proposals, [nc] results, then GUARD words nobody may write: a kernel whose idle lanes stored would show here
-    std::vector<double> res(nchain + GUARD, 0.0);
-    const double mark = -12345.678;
-    std::fill(res.begin() + nchain, res.end(), mark);
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = c->k_res.need(sizeof(double) * (nchain * c->d + nchain + GUARD));
-    double *d_th = c->k_res.as<double>(), *d_ll = d_th + nchain * c->d;
-    if (e == hipSuccess) e = hipMemcpyAsync(d_th, theta, sizeof(double) * nchain * c->d, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_ll, res.data(), sizeof(double) * res.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_logdens_chains_ms(c, s, d_th, (long)nchain, d_ll, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(res.data(), d_ll, sizeof(double) * res.size(), hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return hip_fail(e, "carma_mpt_logdensity");
-    for (size_t k = nchain; k < res.size(); k++)
-        if (res[k] != mark) {
-            set_error("carma_mpt_logdensity: the kernel wrote past its %zu results", nchain);
-            return CARMA_EHIP;
-        }
-    std::memcpy(out, res.data(), sizeof(double) * nchain);
-    return CARMA_OK;
-}
+int carma_mpt_logdensity(carma_mctx* h, const double* theta, double* out) { return pt_front_logdensity(mpt_front(h), theta, out); }
 
 int carma_mpt_kernel_name(const carma_mctx* h, char* buf, int len)
 {
@@ -428,11 +245,8 @@ int carma_mpt_kernel_name(const carma_mctx* h, char* buf, int len)
 int carma_mpt_run(carma_mctx* h, const int* series, int M, int ntemps, int nreplicas, int sample_size, int burnin, int thin,
                   const double* init, uint64_t seed, double* samples, double* logposts)
 {
-    int rc = carma_mpt_create(h, series, M, ntemps, nreplicas, nullptr, burnin, seed);
-    if (rc == CARMA_OK) rc = carma_mpt_start(h, init);
-    if (rc == CARMA_OK) rc = carma_mpt_iterate(h, burnin, 1);                     // Sampler::Run burn-in (samplers.cpp:97)
-    if (rc == CARMA_OK) rc = carma_mpt_sample(h, sample_size, thin, samples, logposts);   // :101-108
-    return rc;
+    const int rc = carma_mpt_create(h, series, M, ntemps, nreplicas, nullptr, burnin, seed);
+    return rc == CARMA_OK ? pt_front_run(mpt_front(h), init, burnin, sample_size, thin, samples, logposts) : rc;
 }
 
 }  // extern "C"

@@ -48,6 +48,16 @@ inline long check_toff(const long* toff, int M)
     return TOFF_OK;
 }
 
+// ---- carma_mpt_* --------------------------------------------------------------------------------------------------------
+// Iterations per chunk of the sampler whose longest series has nmax data: the K1 of an iteration runs as long as that series
+// (>= ~0.45 us per datum, as chunk_iters of the single-series lane sampler), 2-3 launches each; around a quarter of a second, at
+// most 4096 iterations, are in flight at a time.
+inline long mpt_chunk_iters(int nmax)
+{
+    const double est_us = std::max(1.0, 0.45 * nmax);
+    return (long)std::max(1.0, std::min(4096.0, 250000.0 / est_us));
+}
+
 // ---- carma_mlogdensity_batch --------------------------------------------------------------------------------------------
 // B evaluations, evaluation i on series[i]: waves of 64 evaluations of ONE series each, W = sum over the series of
 // ceil(cnt / 64).  The series that have evaluations come with the irregular-cadence ones (repdt = 0) first -- the waves

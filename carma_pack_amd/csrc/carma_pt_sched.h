@@ -1,5 +1,6 @@
 // carma_pt_sched.h -- what the parallel-tempering samplers decide on the host, host C++ only: no HIP, nothing but the standard
-// library and carma_types.h.  One copy for carma_pt_* (carma_pt_host.hip: one series) and carma_mpt_* (carma_mpt.hip: many):
+// library and carma_types.h.  One copy for carma_pt_* (carma_pt_host.hip: one series) and the handle-based lane samplers
+// (carma_pt_front.hip: carma_mpt_* on many series, carma_bands_pt_*, carma_bandset_pt_*):
 // the default ladder, the initial proposal factor, the length of the next launch, the starting-value draws and the search for
 // finite starting values.  tests/ptsched/ compiles it with a plain C++ compiler.
 #ifndef CARMA_PT_SCHED_H

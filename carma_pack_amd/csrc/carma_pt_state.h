@@ -1,7 +1,7 @@
 // carma_pt_state.h -- the state of the parallel-tempering samplers and the part of them that only requests, regrows and releases
 // device buffers: which buffers a state holds, how many elements each, in which order they are asked for, and what is left after a
 // request failed.  Every buffer has an owner (carma_devbuf.h), so deleting a state releases all of it; the copies, memsets and
-// launches are in carma_pt_host.hip, carma_shard.hip and carma_mpt.hip.  Host C++ without the HIP runtime:
+// launches are in carma_pt_host.hip, carma_shard.hip and carma_pt_front.hip.  Host C++ without the HIP runtime:
 // tests/hostmem/hostmem_main.cpp runs these methods over an allocator of its own.
 #pragma once
 #include <cstdint>
@@ -11,9 +11,10 @@
 
 namespace carma {
 
-// What both parallel-tempering samplers hold: an ensemble of R ladders of T chains (chain = ladder * T + temperature) with its
-// buffers.  carma_pt_* (PtState below): the R replicas of one series; carma_mpt_* (MptState): the ladders of all runs of a call.
-// The pt_ens_* functions (carma_host.h, carma_pt_host.hip) work on this part alone.
+// What every parallel-tempering sampler holds: an ensemble of R ladders of T chains (chain = ladder * T + temperature) with its
+// buffers.  carma_pt_* (PtState below): the R replicas of one series; the handle-based lane samplers behind carma_pt_front.h --
+// carma_mpt_* (MptState), carma_bands_pt_* (BptState, carma_mband_ctx.h), carma_bandset_pt_* (BSptState, carma_mband_set_ctx.h):
+// the ladders of all runs of a call.  The pt_ens_* functions (carma_host.h, carma_pt_host.hip) work on this part alone.
 struct PtEnsemble {
     int T = 0, R = 0;                  // temperatures of a ladder, ladders (what PtLaunch::T and ::R receive)
     int maxiter = 0;
@@ -131,6 +132,7 @@ struct MptState : PtEnsemble {
     int M = 0, reps = 0;              // runs, replicas per run
     std::vector<int> series;          // [M] series of run j
     int nmax = 0;                     // the longest series of the call
+    long chunk0 = 1;                  // iterations per chunk (mpt_chunk_iters, carma_mseries_plan.h)
     bool any_plain = false, any_rep = false;   // the call holds irregular / regular-cadence series
     DevBuf<int> d_lser;               // [R] series of every ladder, uploaded once
     DevBuf<char> d_rep;               // [S] SERIES_REPEATED_DT of every series

@@ -6,6 +6,7 @@
 //   plan_main smooth    G S M forced, nser[S], the data times of all series, series[M], toff[M + 1], tout[toff[M]]
 //                                                                   -> E W J pts_max chunk0 tint tlong grids
 //   plan_main toff      M, toff[M + 1]                              -> toff r      (r as check_toff returns it)
+//   plan_main chunk     nmax                                        -> chunk c     (c = mpt_chunk_iters(nmax))
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -38,7 +39,7 @@ int main(int argc, char** argv)
 {
     using namespace carma;
     if (argc != 2) {
-        fprintf(stderr, "usage: plan_main logdens | filter | predict | smooth | toff   (the case on stdin)\n");
+        fprintf(stderr, "usage: plan_main logdens | filter | predict | smooth | toff | chunk   (the case on stdin)\n");
         return 1;
     }
     const char* mode = argv[1];
@@ -48,6 +49,12 @@ int main(int argc, char** argv)
         std::vector<long> toff((size_t)M + 1);
         if (!rd(toff)) return 2;
         put1("toff", check_toff(toff.data(), M));
+        return 0;
+    }
+    if (!strcmp(mode, "chunk")) {
+        int nmax = 0;
+        if (scanf("%d", &nmax) != 1) return 2;
+        put1("chunk", mpt_chunk_iters(nmax));
         return 0;
     }
     if (!strcmp(mode, "logdens")) {

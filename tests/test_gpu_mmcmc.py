@@ -350,6 +350,8 @@ def test_error_paths(cpa, sset):
         mc.pt_create([0, 7], 3, 1, 5)
     # before start
     mc.pt_create(runs, 3, 2, 5, seed=4)
+    err(lib.carma_mpt_get_factor(h, None), "carma_mpt_get_factor: null chol")
+    err(lib.carma_mpt_set_factor(h, None), "carma_mpt_set_factor: null chol")
     err(lib.carma_mpt_iterate(h, 1, 1), "no starting values")
     err(lib.carma_mpt_sample(h, 1, 1, dp(x), dp(x)), "no starting values")
     mc.pt_start()

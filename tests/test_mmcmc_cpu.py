@@ -20,26 +20,47 @@ def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
-def test_entry_points_reject_a_null_context(cpa):
+# The three handle-based lane samplers share one front (carma_pt_front.h): every entry point of each returns EINVAL on a null
+# handle, and every one that sets a message has ITS OWN name at the start of last_error().
+@pytest.mark.parametrize("prefix", ["carma_mpt", "carma_bands_pt", "carma_bandset_pt"])
+def test_entry_points_reject_a_null_context(cpa, prefix):
     lib = cpa._lib.lib
     x = np.zeros(64)
     w = np.zeros(4, dtype=np.int32)
     wp = w.ctypes.data_as(C.POINTER(C.c_int))
     buf = C.create_string_buffer(64)
-    assert lib.carma_mpt_create(None, wp, 1, 10, 1, None, 5, C.c_uint64(1)) == EINVAL
-    assert "carma_mpt_create" in cpa._lib.last_error()
-    assert lib.carma_mpt_start(None, None) == EINVAL
-    assert lib.carma_mpt_set_chains(None, _dp(x), None) == EINVAL
-    assert lib.carma_mpt_get_chains(None, _dp(x), _dp(x)) == EINVAL
-    assert lib.carma_mpt_get_factor(None, _dp(x)) == EINVAL
-    assert lib.carma_mpt_set_factor(None, _dp(x)) == EINVAL
-    assert lib.carma_mpt_iterate(None, 1, 1) == EINVAL
-    assert lib.carma_mpt_sample(None, 1, 1, _dp(x), _dp(x)) == EINVAL
-    assert lib.carma_mpt_stats(None, _dp(x), _dp(x), 0) == EINVAL
-    assert lib.carma_mpt_iterations_done(None) == EINVAL
-    assert lib.carma_mpt_logdensity(None, _dp(x), _dp(x)) == EINVAL
-    assert lib.carma_mpt_kernel_name(None, buf, 64) == EINVAL
-    assert lib.carma_mpt_run(None, wp, 1, 10, 1, 5, 5, 1, None, C.c_uint64(1), _dp(x), _dp(x)) == EINVAL
+    seed = C.c_uint64(1)
+    fn = lambda name: getattr(lib, prefix + "_" + name)
+
+    # (consecutive calls below expect different names, so a message left by the call before does not pass)
+    def rejected(name, *args, named=None):
+        assert fn(name)(None, *args) == EINVAL, name
+        if named is not None:
+            assert cpa._lib.last_error().startswith(prefix + "_" + named + ":"), (name, cpa._lib.last_error())
+
+    create = {"carma_mpt": (wp, 1, 10, 1, None, 5, seed),
+              "carma_bands_pt": (10, 1, None, 5, seed, None, None),
+              "carma_bandset_pt": (wp, 1, 10, 1, None, 5, seed, None, None)}[prefix]
+    run = {"carma_mpt": (wp, 1, 10, 1, 5, 5, 1, None, seed, _dp(x), _dp(x)),
+           "carma_bands_pt": (10, 1, 5, 5, 1, None, seed, None, None, _dp(x), _dp(x)),
+           "carma_bandset_pt": (wp, 1, 10, 1, 5, 5, 1, None, seed, None, None, _dp(x), _dp(x))}[prefix]
+    rejected("create", *create, named="create")
+    rejected("start", None, named="start")
+    rejected("set_chains", _dp(x), None, named="set_chains")
+    rejected("get_chains", _dp(x), _dp(x), named="get_chains")
+    rejected("get_factor", _dp(x), named="get_factor")
+    rejected("set_factor", _dp(x), named="set_factor")
+    rejected("iterate", 1, 1, named="iterate")
+    rejected("sample", 1, 1, _dp(x), _dp(x), named="sample")
+    rejected("stats", _dp(x), _dp(x), 0, named="stats")
+    rejected("iterations_done")
+    rejected("logdensity", _dp(x), _dp(x), named="logdensity")
+    rejected("kernel_name", buf, 64)
+    rejected("run", *run, named="create")                    # (run's first step is create, which words the refusal)
+    if prefix == "carma_bands_pt":
+        rejected("default_box", _dp(x), _dp(x), named="default_box")
+    if prefix == "carma_bandset_pt":
+        rejected("default_box", 0, _dp(x), _dp(x), named="default_box")
 
 
 def _set(cpa, p=3, q=1):

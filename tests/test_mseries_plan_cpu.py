@@ -66,6 +66,13 @@ def test_check_toff(toff, want):
     assert int(got["toff"][0]) == want == ref.check_toff(toff)
 
 
+# ---- the sampler's chunk (carma_mpt_*) -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nmax, want", [(1, 4096), (1000, int(250000.0 / 450.0)), (10 ** 6, 1)])
+def test_mpt_chunk_iters(nmax, want):
+    """min(4096, 250000 / max(1, 0.45 nmax)), at least 1: the upper clamp, a value between (555), the lower clamp"""
+    assert int(run("chunk", [nmax])["chunk"][0]) == want == max(1, int(min(4096.0, 250000.0 / max(1.0, 0.45 * nmax))))
+
+
 # ---- log-density plan -----------------------------------------------------------------------------------------------------
 # S = 5 series; series 2 never has evaluations; both cadence classes; series 0 and 4 tie in length within the plain class
 LD_NSER = np.array([120, 300, 77, 45, 120])
