@@ -387,6 +387,40 @@ def _theta_rows(thetas, d):
     return thetas.reshape(-1, d), thetas.ndim == 1
 
 
+def _bounds_lohi(bounds):
+    """[(lo, hi)] with None for unbounded -> (lo, hi) float64 arrays with -inf / +inf there, as the optimiser entries take a box."""
+    return (np.array([-np.inf if b[0] is None else b[0] for b in bounds], dtype=np.float64),
+            np.array([np.inf if b[1] is None else b[1] for b in bounds], dtype=np.float64))
+
+
+def _which(which, B, n=None, noun=None):
+    """which (one index per row, or one for all B rows) -> int32 [B] as the library takes it.  n: every index must lie in
+    [0, n), a ValueError that names `noun` otherwise; None: the range is the library's check."""
+    w = np.ascontiguousarray(np.broadcast_to(np.asarray(which, dtype=np.int64), (B,)))
+    if n is not None and B and (w.min() < 0 or w.max() >= n):
+        raise ValueError("%s index out of range [0, %d)" % (noun, n))
+    return np.ascontiguousarray(w, dtype=np.int32)
+
+
+def _times_per_row(times, B):
+    """One array of times for all B rows, or one per row -- a list or tuple of arrays, or an array of more than one axis -> a
+    list: B times the one, or the caller's entries (whose count _pack_times or the caller checks).  Nothing is converted here."""
+    if np.ndim(times if isinstance(times, np.ndarray) else 0) > 1 or (isinstance(times, (list, tuple)) and len(times)
+                                                                       and np.ndim(times[0]) > 0):
+        return list(times)
+    return [times] * B
+
+
+def _pack_times(times, B, who, noun):
+    """A list of B arrays of times -> (the arrays, their offsets [B + 1], all of them back to back).  All empty: one dummy time,
+    so that the pointers the library gets are valid; outputs are then sized max(offsets[-1], 1)."""
+    times = [as_f64(np.atleast_1d(t)).ravel() for t in times]
+    if len(times) != B:
+        raise ValueError("%s: times must hold one array per %s (%d), got %d" % (who, noun, B, len(times)))
+    toff = _offsets([t.size for t in times])
+    return times, toff, as_f64(np.concatenate(times)) if toff[-1] else np.zeros(1)
+
+
 def _pack_models(who, noun, sigsqr, omega, ma=None):
     """The K models of a batched stateless call -> (K, p, sigsqr [K], roots, ma).  With ma: omega [K][p] complex ->
     roots [K][p][2], ma [K][nma]; without (CAR(1)): omega [K] = 1 / tau -> roots [K]."""
@@ -456,10 +490,19 @@ class _Handle:
 
 
 class _Sampler:
-    """The parallel-tempering calls Context (carma_pt_*, chains [R][T]) and MultiContext (carma_mpt_*, chains [M][R][T]) share:
-    `_pt` is the prefix of the C functions, `_pt_lead()` the leading shape (..., R, T) that pt_create / pt_run left.  BandsContext (carma_bands_pt_*, chains [R][T] of dx
-    entries) and BandsSetContext (carma_bandset_pt_*, chains [M][R][T] of dx entries) take them too."""
+    """The parallel-tempering calls of the four contexts.  `_pt` is the prefix of the C functions, `_pt_lead()` the leading shape
+    (..., R, T) that pt_create / pt_run left, `_pt_dim()` the entries of a chain's vector.  Everything from pt_set_chains down
+    serves all four: Context (carma_pt_*, chains [R][T] of d entries), MultiContext (carma_mpt_*, [M][R][T] of d), BandsContext
+    (carma_bands_pt_*, [R][T] of dx) and BandsSetContext (carma_bandset_pt_*, [M][R][T] of dx).
+
+    The three handle-based lane samplers (all but Context) also share ONE create, start and run -- _pt_create, pt_start, _pt_run --
+    as the C side shares one front.  Two class attributes say what a class's C calls look like: `_pt_runs`, the arguments lead
+    with a run list (w, M) and every shape with M; `_pt_box`, they carry a band box (lo, hi) behind the seed.  A class keeps its
+    public pt_create / pt_run, which name the run list as the class does and hand everything on.  A failed create or run leaves
+    no sampler behind (`_pt_shape` None: "call pt_create first").  Context has its own three: its init is a list of values with
+    a length, and it has the sharding members."""
     _pt = None
+    _pt_runs = _pt_box = False
 
     def _pt_dim(self):
         """Entries of a chain's vector: d of a series; a context whose chains carry more (BandsContext: dx) says so here."""
@@ -473,20 +516,66 @@ class _Sampler:
     def _pt_call(self, name, *args):
         check(getattr(lib, self._pt + name)(self._h, *args), self._pt + name)
 
-    # the samplers of many runs per call (MultiContext, BandsSetContext): the run list and the init rows as the C calls take them
+    # ---- create, start and run of the lane samplers: the arguments as the C calls take them ----
     def _runs(self, index):
+        """The run list (None without one) and what it puts in front of the C arguments and of every shape."""
+        if not self._pt_runs:
+            return None, (), ()
         w = np.asarray(index, dtype=np.int64).ravel()
         if w.size < 1:
             raise ValueError("need at least one run")
-        return np.ascontiguousarray(w, dtype=np.int32)
+        w = np.ascontiguousarray(w, dtype=np.int32)
+        return w, (_iptr(w), w.size), (int(w.size),)              # (w itself: the caller holds it while the C call reads the pointer)
 
-    def _init_rows(self, init, M):
+    def _init(self, init, lead):
+        """init of start / run: None, or one vector -- with a run list one row per run."""
         if init is None:
             return None
         a = as_f64(init)
-        if a.shape != (M, self._pt_dim()):
-            raise ValueError("init must be [%d, %d] (one row per run), got %r" % (M, self._pt_dim(), a.shape))
+        if a.shape != lead + (self._pt_dim(),):
+            raise ValueError(("init must be [%d, %d] (one row per run), got %r" if lead else "init must be [%d], got %r")
+                             % (lead + (self._pt_dim(), a.shape)))
         return a
+
+    def _band_box(self, band_box, lead):
+        """None, or (lo, hi) [K - 1, 2] each, columns (log a_b, mu_b) -- with a run list [M, K - 1, 2], a box per run, or
+        [K - 1, 2] for every run -> the two arrays the C calls take (or None, None); nothing for a sampler without a box."""
+        if not self._pt_box:
+            return ()
+        if band_box is None:
+            return None, None
+        shape = lead + (self.nbands - 1, 2)
+        return tuple(as_f64(np.broadcast_to(as_f64(v), shape) if lead and np.ndim(v) == 2 else as_f64(v).reshape(shape))
+                     for v in band_box)
+
+    def _pt_create(self, runs, ntemps, nreplicas, adapt_iters, seed, temperatures, band_box=None):
+        w, cargs, lead = self._runs(runs)
+        tt = as_f64(temperatures) if temperatures is not None else None
+        if tt is not None and tt.size != int(ntemps):
+            raise ValueError("temperatures must hold ntemps = %d values" % int(ntemps))
+        box = self._band_box(band_box, lead)
+        self._pt_shape = None
+        self._pt_call("create", *cargs, int(ntemps), int(nreplicas), _optr(tt), int(adapt_iters), _seed(seed),
+                      *(_optr(v) for v in box))
+        self._pt_shape = lead + (int(nreplicas), int(ntemps))
+
+    def pt_start(self, init=None):
+        """Starting values (carma_*pt_start); init: None, or a vector of the chains' entries -- with a run list [M, ...], row j for
+        run j -- taken by every chain where its log-density there is finite."""
+        a = self._init(init, self._pt_lead()[:1] if self._pt_runs else ())
+        self._pt_call("start", _optr(a))
+
+    def _pt_run(self, runs, ntemps, nreplicas, sample_size, burnin, thin, init, seed, band_box=None):
+        w, cargs, lead = self._runs(runs)
+        a = self._init(init, lead)
+        box = self._band_box(band_box, lead)
+        head = lead + (int(nreplicas), int(sample_size))
+        samples, logposts = np.empty(head + (self._pt_dim(),)), np.empty(head)
+        self._pt_shape = None
+        self._pt_call("run", *cargs, int(ntemps), int(nreplicas), int(sample_size), int(burnin), int(thin), _optr(a), _seed(seed),
+                      *(_optr(v) for v in box), ptr(samples), ptr(logposts))
+        self._pt_shape = lead + (int(nreplicas), int(ntemps))
+        return samples, logposts
 
     def pt_set_chains(self, theta, logpost=None):
         lead = self._pt_lead()
@@ -595,8 +684,7 @@ class Context(_Handle, _Sampler):
         """carma_mle_batched: lock-step bounded L-BFGS from every row of x0 on -LogDensity, host loop in the library.
         bounds = [(lo, hi)] with None for unbounded.  Returns (x [B, d], fun [B], nit [B], nfev [B], status [B])."""
         x0, B = _mle_x0(x0, self.d)
-        lo = np.array([-np.inf if b[0] is None else b[0] for b in bounds], dtype=np.float64)
-        hi = np.array([np.inf if b[1] is None else b[1] for b in bounds], dtype=np.float64)
+        lo, hi = _bounds_lohi(bounds)
         out, tail = _mle_tail(B, self.d, maxiter, mem, ftol, gtol, fd_step, ignore_prior)
         check(lib.carma_mle_batched(self._h, ptr(x0), B, ptr(lo), ptr(hi), *tail), "carma_mle_batched")
         return out
@@ -800,7 +888,7 @@ class MultiContext(_Handle, _Sampler):
 
     series: a list of (t, y, yerr); each is prepared as Context prepares one (sort, dedup, prior bounds).  max_stdev: None
     (10 sqrt(var(y, ddof=1)) per series, as Context), a number for all series, or one value per series."""
-    _destroy, _pt = "carma_mctx_destroy", "carma_mpt_"
+    _destroy, _pt, _pt_runs = "carma_mctx_destroy", "carma_mpt_", True
 
     def __init__(self, series, p, q=0, max_stdev=None, device=None):
         ys, offsets, t_all, y_all, e_all = _concat_series(series, "MultiContext", "series")
@@ -828,17 +916,11 @@ class MultiContext(_Handle, _Sampler):
         check(lib.carma_mctx_get_prior(self._h, int(s), ptr(out)), "carma_mctx_get_prior")
         return tuple(out)
 
-    def _which(self, which, B):
-        w = np.ascontiguousarray(np.broadcast_to(np.asarray(which, dtype=np.int64), (B,)))
-        if B and (w.min() < 0 or w.max() >= self.nseries):
-            raise ValueError("series index out of range [0, %d)" % self.nseries)
-        return np.ascontiguousarray(w, dtype=np.int32)
-
     def logdensity(self, thetas, which, ignore_prior=False):
         """Log-density of thetas[i] on series which[i] (which: one index per row, or one for all), one launch."""
         thetas, one = _theta_rows(thetas, self.d)
         B = thetas.shape[0]
-        w = self._which(which, B)
+        w = _which(which, B, self.nseries, "series")
         out = np.empty(B)
         check(lib.carma_mlogdensity_batch(self._h, ptr(thetas), _iptr(w), B, int(bool(ignore_prior)), ptr(out)),
               "carma_mlogdensity_batch")
@@ -853,7 +935,7 @@ class MultiContext(_Handle, _Sampler):
         M = sig.size
         if M < 1:
             raise ValueError("%s: need at least one item" % who)
-        w = self._which(which, M)
+        w = _which(which, M, self.nseries, "series")
         roots = np.asarray(roots, dtype=complex)
         if self.p == 1:
             roots = roots.reshape(-1)
@@ -886,11 +968,7 @@ class MultiContext(_Handle, _Sampler):
     def _at_times(self, what, who, which, sigsqr, roots, ma, times, mu, return_singular):
         """carma_mpredict / carma_msmooth (`what`): M items, item i at times[i]."""
         M, w, sig, om, ma_, nma, mu_ = self._items(which, sigsqr, roots, ma, mu, who)
-        times = [as_f64(np.atleast_1d(t)).ravel() for t in times]
-        if len(times) != M:
-            raise ValueError("%s: times must hold one array per item (%d), got %d" % (who, M, len(times)))
-        toff = _offsets([t.size for t in times])
-        tp = as_f64(np.concatenate(times)) if toff[-1] else np.zeros(1)       # all empty: one dummy time, outputs of length 1
+        times, toff, tp = _pack_times(times, M, who, "item")
         pm, pv = np.empty(max(int(toff[-1]), 1)), np.empty(max(int(toff[-1]), 1))
         sing = np.zeros(M, dtype=np.int32)
         check(getattr(lib, what)(self._h, _iptr(w), M, ptr(sig), ptr(om), ptr(ma_), nma, _optr(mu_), ptr(tp), _lptr(toff), ptr(pm),
@@ -919,7 +997,7 @@ class MultiContext(_Handle, _Sampler):
         """carma_mle_batched_ms: Context.mle_batched with start i on series which[i] and its own box lo[i], hi[i] ([B, d],
         non-finite = unbounded; or [d] for every start).  Returns (x [B, d], fun [B], nit [B], nfev [B], status [B])."""
         x0, B = _mle_x0(x0, self.d)
-        w = self._which(which, B)
+        w = _which(which, B, self.nseries, "series")
         lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.float64), x0.shape))
         hi = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.float64), x0.shape))
         out, tail = _mle_tail(B, self.d, maxiter, mem, ftol, gtol, fd_step, ignore_prior)
@@ -931,31 +1009,11 @@ class MultiContext(_Handle, _Sampler):
     def pt_create(self, series, ntemps, nreplicas, adapt_iters, seed=0, temperatures=None):
         """One sampler run (nreplicas ladders of ntemps chains) per entry of `series` (indices into this context, any order,
         repeats allowed), all advancing in the same launches (carma_mpt_create)."""
-        w = self._runs(series)
-        tt = as_f64(temperatures) if temperatures is not None else None
-        if tt is not None and tt.size != int(ntemps):
-            raise ValueError("temperatures must hold ntemps = %d values" % int(ntemps))
-        check(lib.carma_mpt_create(self._h, _iptr(w), w.size, int(ntemps), int(nreplicas), _optr(tt), int(adapt_iters),
-                                   _seed(seed)), "carma_mpt_create")
-        self._pt_shape = (int(w.size), int(nreplicas), int(ntemps))
-        self._mpt_series = w
-
-    def pt_start(self, init=None):
-        """Starting values (carma_mpt_start); init: None or [M, d], row j for every chain of run j where it is finite."""
-        a = self._init_rows(init, self._pt_lead()[0])
-        check(lib.carma_mpt_start(self._h, _optr(a)), "carma_mpt_start")
+        self._pt_create(series, ntemps, nreplicas, adapt_iters, seed, temperatures)
 
     def pt_run(self, series, ntemps, nreplicas, sample_size, burnin, thin=1, init=None, seed=0):
         """Whole Sampler::Run of every run: (samples [M][R][S][d], logposts [M][R][S]) of the coldest chains (carma_mpt_run)."""
-        w = self._runs(series)
-        a = self._init_rows(init, w.size)
-        samples = np.empty((w.size, int(nreplicas), int(sample_size), self.d))
-        logposts = np.empty((w.size, int(nreplicas), int(sample_size)))
-        check(lib.carma_mpt_run(self._h, _iptr(w), w.size, int(ntemps), int(nreplicas), int(sample_size), int(burnin), int(thin),
-                                _optr(a), _seed(seed), ptr(samples), ptr(logposts)), "carma_mpt_run")
-        self._pt_shape = (int(w.size), int(nreplicas), int(ntemps))
-        self._mpt_series = w
-        return samples, logposts
+        return self._pt_run(series, ntemps, nreplicas, sample_size, burnin, thin, init, seed)
 
 
 class BandsContext(_Handle, _Sampler):
@@ -964,59 +1022,7 @@ class BandsContext(_Handle, _Sampler):
     bands: a list of (t, y, yerr), band 0 the reference band; lag_bounds: [K - 1] pairs (lo, hi), the box of every lag.  The
     parameter vector is Context's (d entries) followed by (lag_b, log a_b, mu_b) for b = 1 ... K - 1: dx entries.
     The sampler (carma_bands_pt_*): pt_create / pt_start, then _Sampler's calls on chains [R][T] of dx entries."""
-    _destroy, _pt = "carma_bands_destroy", "carma_bands_pt_"
-
-    def _pt_dim(self):
-        return self.dx
-
-    def _band_box(self, band_box):
-        """None, or (lo, hi) [K - 1, 2] each, columns (log a_b, mu_b) -> the two arrays the C calls take (or None, None)."""
-        if band_box is None:
-            return None, None
-        lo, hi = (as_f64(v).reshape(self.nbands - 1, 2) for v in band_box)
-        return lo, hi
-
-    def pt_default_box(self):
-        """(lo, hi) [K - 1, 2] each: the default box of (log a_b, mu_b) (carma_bands_pt_default_box)."""
-        lo, hi = np.empty((self.nbands - 1, 2)), np.empty((self.nbands - 1, 2))
-        check(lib.carma_bands_pt_default_box(self._h, ptr(lo), ptr(hi)), "carma_bands_pt_default_box")
-        return lo, hi
-
-    def pt_create(self, ntemps, nreplicas, adapt_iters, seed=0, temperatures=None, band_box=None):
-        """nreplicas ladders of ntemps chains on the extended vector (carma_bands_pt_create).  band_box: None (no box) or (lo, hi),
-        [K - 1, 2] each for (log a_b, mu_b): outside it a chain's log-density is -inf."""
-        tt = as_f64(temperatures) if temperatures is not None else None
-        if tt is not None and tt.size != int(ntemps):
-            raise ValueError("temperatures must hold ntemps = %d values" % int(ntemps))
-        lo, hi = self._band_box(band_box)
-        self._pt_shape = None
-        check(lib.carma_bands_pt_create(self._h, int(ntemps), int(nreplicas), _optr(tt), int(adapt_iters), _seed(seed), _optr(lo),
-                                        _optr(hi)), "carma_bands_pt_create")
-        self._pt_shape = (int(nreplicas), int(ntemps))
-
-    def _init_row(self, init):
-        if init is None:
-            return None
-        a = as_f64(init)
-        if a.shape != (self.dx,):
-            raise ValueError("init must be [%d], got %r" % (self.dx, a.shape))
-        return a
-
-    def pt_start(self, init=None):
-        """Starting values (carma_bands_pt_start); init: None or [dx], every chain's value where its log-density is finite."""
-        check(lib.carma_bands_pt_start(self._h, _optr(self._init_row(init))), "carma_bands_pt_start")
-
-    def pt_run(self, ntemps, nreplicas, sample_size, burnin, thin=1, init=None, seed=0, band_box=None):
-        """Whole Sampler::Run: (samples [R][S][dx], logposts [R][S]) of the coldest chains (carma_bands_pt_run)."""
-        a = self._init_row(init)
-        lo, hi = self._band_box(band_box)
-        samples = np.empty((int(nreplicas), int(sample_size), self.dx))
-        logposts = np.empty((int(nreplicas), int(sample_size)))
-        self._pt_shape = None
-        check(lib.carma_bands_pt_run(self._h, int(ntemps), int(nreplicas), int(sample_size), int(burnin), int(thin), _optr(a),
-                                     _seed(seed), _optr(lo), _optr(hi), ptr(samples), ptr(logposts)), "carma_bands_pt_run")
-        self._pt_shape = (int(nreplicas), int(ntemps))
-        return samples, logposts
+    _destroy, _pt, _pt_box = "carma_bands_destroy", "carma_bands_pt_", True
 
     def __init__(self, bands, p, q=0, lag_bounds=None, max_stdev=None, device=None):
         ys, offsets, t_all, y_all, e_all = _concat_series(bands, "BandsContext", "band")
@@ -1088,6 +1094,25 @@ class BandsContext(_Handle, _Sampler):
             mean, var, inv = mean[0], var[0], bool(inv[0])
         return (mean, var, bm, bv, inv) if moments else (mean, var, inv)
 
+    # ---- parallel-tempering sampler on the extended vector (carma_bands_pt_*); the rest is _Sampler's --------
+    def _pt_dim(self):
+        return self.dx
+
+    def pt_default_box(self):
+        """(lo, hi) [K - 1, 2] each: the default box of (log a_b, mu_b) (carma_bands_pt_default_box)."""
+        lo, hi = np.empty((self.nbands - 1, 2)), np.empty((self.nbands - 1, 2))
+        check(lib.carma_bands_pt_default_box(self._h, ptr(lo), ptr(hi)), "carma_bands_pt_default_box")
+        return lo, hi
+
+    def pt_create(self, ntemps, nreplicas, adapt_iters, seed=0, temperatures=None, band_box=None):
+        """nreplicas ladders of ntemps chains on the extended vector (carma_bands_pt_create).  band_box: None (no box) or (lo, hi),
+        [K - 1, 2] each for (log a_b, mu_b): outside it a chain's log-density is -inf."""
+        self._pt_create(None, ntemps, nreplicas, adapt_iters, seed, temperatures, band_box)
+
+    def pt_run(self, ntemps, nreplicas, sample_size, burnin, thin=1, init=None, seed=0, band_box=None):
+        """Whole Sampler::Run: (samples [R][S][dx], logposts [R][S]) of the coldest chains (carma_bands_pt_run)."""
+        return self._pt_run(None, ntemps, nreplicas, sample_size, burnin, thin, init, seed, band_box)
+
 
 class BandsSetContext(_Handle, _Sampler):
     """Owns one carma_bandset: S multi-band objects of the same K bands and order resident in HBM, each prepared as BandsContext
@@ -1098,62 +1123,7 @@ class BandsSetContext(_Handle, _Sampler):
     belongs to another set.
     The sampler (carma_bandset_pt_*): pt_create / pt_start, then _Sampler's calls on chains [M][R][T] of dx entries, run j of
     the M on object objects[j]."""
-    _destroy, _pt = "carma_bandset_destroy", "carma_bandset_pt_"
-
-    # ---- parallel-tempering sampler over many objects (carma_bandset_pt_*); the rest is _Sampler's --------
-    def _pt_dim(self):
-        return self.dx
-
-    def _band_boxes(self, band_box, M):
-        """None, or (lo, hi) [M, K - 1, 2] each ([K - 1, 2]: for every run), columns (log a_b, mu_b) -> the two arrays the C calls
-        take (or None, None)."""
-        if band_box is None:
-            return None, None
-        shape = (M, self.nbands - 1, 2)
-        lo, hi = (as_f64(np.broadcast_to(as_f64(v), shape) if np.ndim(v) == 2 else as_f64(v).reshape(shape)) for v in band_box)
-        return lo, hi
-
-    def pt_default_box(self, s):
-        """(lo, hi) [K - 1, 2] each: the default box of (log a_b, mu_b) of object s (carma_bandset_pt_default_box)."""
-        lo, hi = np.empty((self.nbands - 1, 2)), np.empty((self.nbands - 1, 2))
-        check(lib.carma_bandset_pt_default_box(self._h, int(s), ptr(lo), ptr(hi)), "carma_bandset_pt_default_box")
-        return lo, hi
-
-    def pt_create(self, objects, ntemps, nreplicas, adapt_iters, seed=0, temperatures=None, band_box=None):
-        """One sampler run (nreplicas ladders of ntemps chains on the extended vector) per entry of `objects` (indices into this
-        set, any order, repeats allowed), all advancing in the same launches (carma_bandset_pt_create).  band_box: None (no box)
-        or (lo, hi), [M, K - 1, 2] each -- a box per run -- or [K - 1, 2] each for every run."""
-        w = self._runs(objects)
-        tt = as_f64(temperatures) if temperatures is not None else None
-        if tt is not None and tt.size != int(ntemps):
-            raise ValueError("temperatures must hold ntemps = %d values" % int(ntemps))
-        lo, hi = self._band_boxes(band_box, w.size)
-        self._pt_shape = None
-        check(lib.carma_bandset_pt_create(self._h, _iptr(w), w.size, int(ntemps), int(nreplicas), _optr(tt), int(adapt_iters),
-                                          _seed(seed), _optr(lo), _optr(hi)), "carma_bandset_pt_create")
-        self._pt_shape = (int(w.size), int(nreplicas), int(ntemps))
-        self._bspt_objects = w
-
-    def pt_start(self, init=None):
-        """Starting values (carma_bandset_pt_start); init: None or [M, dx], row j for every chain of run j where it is finite."""
-        a = self._init_rows(init, self._pt_lead()[0])
-        check(lib.carma_bandset_pt_start(self._h, _optr(a)), "carma_bandset_pt_start")
-
-    def pt_run(self, objects, ntemps, nreplicas, sample_size, burnin, thin=1, init=None, seed=0, band_box=None):
-        """Whole Sampler::Run of every run: (samples [M][R][S][dx], logposts [M][R][S]) of the coldest chains
-        (carma_bandset_pt_run)."""
-        w = self._runs(objects)
-        a = self._init_rows(init, w.size)
-        lo, hi = self._band_boxes(band_box, w.size)
-        samples = np.empty((w.size, int(nreplicas), int(sample_size), self.dx))
-        logposts = np.empty((w.size, int(nreplicas), int(sample_size)))
-        self._pt_shape = None
-        check(lib.carma_bandset_pt_run(self._h, _iptr(w), w.size, int(ntemps), int(nreplicas), int(sample_size), int(burnin),
-                                       int(thin), _optr(a), _seed(seed), _optr(lo), _optr(hi), ptr(samples), ptr(logposts)),
-              "carma_bandset_pt_run")
-        self._pt_shape = (int(w.size), int(nreplicas), int(ntemps))
-        self._bspt_objects = w
-        return samples, logposts
+    _destroy, _pt, _pt_runs, _pt_box = "carma_bandset_destroy", "carma_bandset_pt_", True, True
 
     def __init__(self, objects, p, q=0, lag_bounds=None, max_stdev=None, device=None):
         objects = [list(o) for o in objects]
@@ -1192,16 +1162,12 @@ class BandsSetContext(_Handle, _Sampler):
         check(lib.carma_bandset_get_prior(self._h, int(s), ptr(out)), "carma_bandset_get_prior")
         return tuple(out)
 
-    def _which(self, which, B):
-        """which (one index per row, or one for all) as the library takes it; the range is the library's check."""
-        return np.ascontiguousarray(np.broadcast_to(np.asarray(which, dtype=np.int64), (B,)), dtype=np.int32)
-
     def logdensity(self, thetas, which, ignore_prior=False, out=None):
         """Log-density of thetas[i] on object which[i], one launch (carma_bandset_logdensity_batch).  out: a float64 array of at
         least B entries to write the results to (the first B)."""
         thetas, one = _theta_rows(thetas, self.dx)
         B = thetas.shape[0]
-        w = self._which(which, B)
+        w = _which(which, B)
         if out is None:
             out = np.empty(B)
         elif out.dtype != np.float64 or not out.flags.c_contiguous or out.size < B:
@@ -1219,7 +1185,7 @@ class BandsSetContext(_Handle, _Sampler):
         ([B, dx], or [dx] for every start; None or non-finite = unbounded; lags stay in the boxes of their object).  fixed_lag
         [B, K - 1] as BandsContext.mle_batched.  Returns (x [B, dx], fun [B], nit [B], nfev [B], status [B])."""
         x0, B = _mle_x0(x0, self.dx)
-        w = self._which(which, B)
+        w = _which(which, B)
         lo = np.ascontiguousarray(np.broadcast_to(as_f64(-np.inf if lo is None else lo), x0.shape))
         hi = np.ascontiguousarray(np.broadcast_to(as_f64(np.inf if hi is None else hi), x0.shape))
         fl = None if fixed_lag is None else as_f64(fixed_lag).reshape(B, self.nbands - 1)
@@ -1237,16 +1203,8 @@ class BandsSetContext(_Handle, _Sampler):
         CarmaError -- or, with return_invalid, is flagged in a third return value, a bool array [B]."""
         thetas, _ = _theta_rows(thetas, self.dx)
         B = thetas.shape[0]
-        w, bo = self._which(which, B), self._which(band, B)
-        if np.ndim(times if isinstance(times, np.ndarray) else 0) > 1 or (isinstance(times, (list, tuple)) and len(times)
-                                                                           and np.ndim(times[0]) > 0):
-            times = [as_f64(np.atleast_1d(t)).ravel() for t in times]
-            if len(times) != B:
-                raise ValueError("BandsSetContext.smooth: times must hold one array per row (%d), got %d" % (B, len(times)))
-        else:
-            times = [as_f64(np.atleast_1d(times)).ravel()] * B
-        toff = _offsets([t.size for t in times])
-        tp = as_f64(np.concatenate(times)) if toff[-1] else np.zeros(1)
+        w, bo = _which(which, B), _which(band, B)
+        times, toff, tp = _pack_times(_times_per_row(times, B), B, "BandsSetContext.smooth", "row")
         mean, var = np.empty(max(int(toff[-1]), 1)), np.empty(max(int(toff[-1]), 1))
         inv = np.zeros(B, dtype=np.int32)
         check(lib.carma_bandset_smooth(self._h, ptr(thetas), _iptr(w), _iptr(bo), B, ptr(tp), _lptr(toff), ptr(mean), ptr(var),
@@ -1257,6 +1215,27 @@ class BandsSetContext(_Handle, _Sampler):
             raise CarmaError("BandsSetContext.smooth: a repeated AR root or a non-finite lag, scale or offset for row(s) %s"
                              % np.flatnonzero(inv)[:8].tolist())
         return _split(mean, toff), _split(var, toff)
+
+    # ---- parallel-tempering sampler over many objects (carma_bandset_pt_*); the rest is _Sampler's --------
+    def _pt_dim(self):
+        return self.dx
+
+    def pt_default_box(self, s):
+        """(lo, hi) [K - 1, 2] each: the default box of (log a_b, mu_b) of object s (carma_bandset_pt_default_box)."""
+        lo, hi = np.empty((self.nbands - 1, 2)), np.empty((self.nbands - 1, 2))
+        check(lib.carma_bandset_pt_default_box(self._h, int(s), ptr(lo), ptr(hi)), "carma_bandset_pt_default_box")
+        return lo, hi
+
+    def pt_create(self, objects, ntemps, nreplicas, adapt_iters, seed=0, temperatures=None, band_box=None):
+        """One sampler run (nreplicas ladders of ntemps chains on the extended vector) per entry of `objects` (indices into this
+        set, any order, repeats allowed), all advancing in the same launches (carma_bandset_pt_create).  band_box: None (no box)
+        or (lo, hi), [M, K - 1, 2] each -- a box per run -- or [K - 1, 2] each for every run."""
+        self._pt_create(objects, ntemps, nreplicas, adapt_iters, seed, temperatures, band_box)
+
+    def pt_run(self, objects, ntemps, nreplicas, sample_size, burnin, thin=1, init=None, seed=0, band_box=None):
+        """Whole Sampler::Run of every run: (samples [M][R][S][dx], logposts [M][R][S]) of the coldest chains
+        (carma_bandset_pt_run)."""
+        return self._pt_run(objects, ntemps, nreplicas, sample_size, burnin, thin, init, seed, band_box)
 
 
 def kfilter_car1(time, y, yerr, sigsqr, omega, device=None):

@@ -9,11 +9,13 @@ replicas at once (``nreplicas``).  ``predict``/``simulate``/``assess_fit`` use t
 Predict kernel (one launch for all requested times); plotting bodies are not part of the hot path.
 """
 import os
+from time import perf_counter
 
 import numpy as np
 from scipy.optimize import minimize
 
 from . import _carmcmc as carmcmcLib
+from ._lib import _bounds_lohi, _times_per_row, _which
 
 __all__ = ["CarmaModel", "CarmaModelSet", "CarmaBandsModel", "CarmaBandsSample", "CarmaBandsSet", "CarmaSample", "Car1Sample", "MCMCSample", "get_ar_roots", "power_spectrum",
            "carma_variance", "car1_process", "carma_process", "carma_process_batch", "car1_process_batch", "mle_to_model"]
@@ -161,6 +163,174 @@ class BatchResult(object):
 # status codes of carma_mle_batched (include/carma_mi355.h) in words
 STATUS_TEXT = ("converged: projected gradient <= gtol", "converged: relative reduction of f <= ftol",
                "maximum number of iterations reached", "line search failed", "no finite value at the start")
+
+
+# ---- what the model classes share: no object state, so plain functions -----------------------------------
+def mle_bounds(time, y, p, q):
+    """L-BFGS-B box of the reference (:219-240) for a CARMA(p,q) fit of the series (time sorted, at least two distinct)."""
+    ysigma = y.std()
+    dt = np.diff(time)
+    max_freq, min_freq = 0.9 / dt.min(), 1.0 / (time.max() - time.min())
+    bnds = [(ysigma / 10.0, 10.0 * ysigma), (0.9, 1.1), (None, None)]
+    if p == 1:
+        bnds.append((np.log(min_freq), np.log(max_freq)))
+    else:
+        lo = np.log(min(min_freq ** 2, 2.0 * min_freq))
+        hi = np.log(max(max_freq ** 2, 2.0 * max_freq))
+        bnds += [(lo, hi)] * p + [(None, None)] * q
+    return bnds
+
+
+def _clamp_starts(starts, bnds, seed):
+    """A short sampler run's draws [ntrials, d] -> the starts of get_mle, in place (reference :195-240): the error scale set to
+    1 (:217), an entry outside its box `bnds` drawn anew, uniform in the box, from np.random.default_rng(seed)."""
+    rng = np.random.default_rng(seed)
+    starts[:, 1] = 1.0
+    for j, (lo, hi) in enumerate(bnds):
+        if lo is not None:
+            out = (starts[:, j] < lo) | (starts[:, j] > hi)
+            starts[out, j] = rng.uniform(lo, hi, int(out.sum()))
+    return starts
+
+
+def _batch_results(xs, fs, nits, nfevs, sts):
+    """What a context's mle_batched returns -> one BatchResult per start."""
+    return [BatchResult(xs[i].copy(), float(fs[i]), int(nits[i]), int(nfevs[i]), int(sts[i]) < 2, STATUS_TEXT[int(sts[i])])
+            for i in range(xs.shape[0])]
+
+
+def _best_result(results):
+    """The best finite result, else the best."""
+    return min([r for r in results if np.isfinite(r.fun) and r.fun < 1e299] or results, key=lambda r: r.fun)
+
+
+def _results_per_member(res, S, nt, return_all):
+    """mle_batched's answer for S members of a set with nt starts each, back to back -> S best results (return_all: S lists)."""
+    results = _batch_results(*res)
+    groups = [results[s * nt:(s + 1) * nt] for s in range(S)]
+    return groups if return_all else [_best_result(g) for g in groups]
+
+
+def _pq_grid(pmax, qmax, pqlist):
+    """The orders choose_order tries (reference :131-192): pqlist, or every (p, q) with p <= pmax, q < p, q <= qmax."""
+    if pmax < 1:
+        raise ValueError("Order of AR polynomial must be at least 1.")
+    if qmax is None:
+        qmax = pmax - 1
+    if pqlist is None:
+        pqlist = [(p, q) for p in range(1, pmax + 1) for q in range(min(p, qmax + 1))]
+    return pqlist
+
+
+def aicc(fun, p, q, n):
+    """AICc of a CARMA(p,q) fit with objective value fun = -loglik to n data (reference :131-192)."""
+    k = 2 + p + q
+    return 2.0 * k + 2.0 * fun + 2.0 * k * (k + 1.0) / (n - k - 1.0)
+
+
+def _choose_order(mles, pqlist, n):
+    """(best fit, AICc of every order, the order of the best -- None when no AICc is below 1e300) of one series of n data."""
+    AICc = [aicc(mle.fun, p, q, n) for mle, (p, q) in zip(mles, pqlist)]
+    best, order, best_aicc = mles[0], None, 1e300
+    for mle, pq, a in zip(mles, pqlist, AICc):
+        if a < best_aicc:
+            best, order, best_aicc = mle, pq, a
+    return best, AICc, order
+
+
+def _series_item(item, noun, k, least=0):
+    """One (time, y, ysig) of a constructor's list -> three flat float arrays of one length (`least`: at least that many)."""
+    if len(item) != 3:
+        raise ValueError("%s %d: expected (time, y, ysig)" % (noun, k))
+    t, y, e = (np.asarray(a, dtype=float).ravel() for a in item)
+    if not (t.size == y.size == e.size) or t.size < least:
+        raise ValueError("%s %d: time, y, ysig must have the same length%s" % (noun, k, ", at least %d" % least if least else ""))
+    return t, y, e
+
+
+def _resolve_samples(samples, kept, S):
+    """samples= of the set's post-processing calls: the caller's list of S sample objects, by default what run_mcmc kept."""
+    if samples is None:
+        samples = kept
+        if samples is None:
+            raise ValueError("no samples: call run_mcmc first, or pass samples=")
+    samples = list(samples)
+    if len(samples) != S:
+        raise ValueError("samples must hold one sample object per series (%d), got %d" % (S, len(samples)))
+    return samples
+
+
+def _lag_grid(lags, K, lag_bounds, obj=None):
+    """lags of lag_profile ([L] for two bands, else [L, K - 1]) -> [L, K - 1], every lag inside its box.  obj: the object of a
+    set the grid is for, as the messages name it."""
+    g = np.asarray(lags, dtype=float)
+    g = g.reshape(-1, 1) if K == 2 and g.ndim == 1 else np.atleast_2d(g)
+    if g.shape[1] != K - 1:
+        raise ValueError("lags must be [L] for two bands or [L, %d]%s"
+                         % (K - 1, "" if obj is None else ", for all objects or a list of one per object"))
+    if not np.all((g >= lag_bounds[:, 0]) & (g <= lag_bounds[:, 1])):
+        raise ValueError("%severy lag must lie inside its box (lag_bounds)" % ("" if obj is None else "object %d: " % obj))
+    return g
+
+
+def _profile_best(fs, xs, L, nt):
+    """The objective values fs [L x nt] and optima xs of a lag profile, nt starts per lag -> (loglik [L], x [L, dx]): the best
+    start of every lag; a start without a finite value never wins."""
+    fs = np.where(np.isfinite(fs), fs, 1e300).reshape(L, nt)
+    best = fs.argmin(axis=1)
+    return -fs[np.arange(L), best], xs.reshape(L, nt, xs.shape[1])[np.arange(L), best]
+
+
+def _timing(t0, t1, t2):
+    """perf_counter() before the starts, after them and after the optimiser -> what get_mle / lag_profile keep as self.timing."""
+    return {"starts_s": t1 - t0, "optimise_s": t2 - t1}
+
+
+def _mcmc_defaults(nsamples, nburnin, ntemperatures, p, q):
+    """(nburnin, ntemperatures) with run_mcmc's defaults as the reference has them (:53-89): nsamples / 2 and max(10, p + q)."""
+    return nsamples // 2 if nburnin is None else nburnin, max(10, p + q) if ntemperatures is None else ntemperatures
+
+
+def _mcmc_args(nsamples, nburnin, ntemperatures, nthin, nreplicas, p, q):
+    """The sampler arguments of a run_mcmc on a lane sampler, defaults filled in, as ints, refused here before any library call
+    -> (nsamples, nburnin, ntemperatures, nthin, nreplicas)."""
+    nsamples, nthin, nreplicas = int(nsamples), int(nthin), int(nreplicas)
+    if nsamples < 1:
+        raise ValueError("nsamples must be at least 1")
+    if nthin < 1:
+        raise ValueError("nthin must be at least 1")
+    if nreplicas < 1:
+        raise ValueError("nreplicas must be at least 1")
+    nburnin, ntemperatures = (int(v) for v in _mcmc_defaults(nsamples, nburnin, ntemperatures, p, q))
+    if not 1 <= ntemperatures <= 64:
+        raise ValueError("ntemperatures must be 1 ... 64 (a ladder is the lanes of one wave), got %d" % ntemperatures)
+    if nburnin < 0:
+        raise ValueError("nburnin must not be negative")
+    return nsamples, nburnin, ntemperatures, nthin, nreplicas
+
+
+def _band_bounds(name, v, K, positive=False):
+    """run_mcmc's scale_bounds ((lo, hi) of a_b, `positive`) or offset_bounds ((lo, hi) of mu_b) -- `name` for the messages --
+    one pair per band after the first, checked -> [K - 1, 2]; None stays None (the default box)."""
+    if v is None:
+        return None
+    a = np.asarray(v, dtype=float)
+    if a.shape != (K - 1, 2):
+        raise ValueError("%s must hold one (lo, hi) pair for each of the %d bands after the first, got shape %r" % (name, K - 1, a.shape))
+    if not np.all(a[:, 0] <= a[:, 1]) or (positive and not np.all(a[:, 0] > 0)):
+        raise ValueError("%s: need %slo <= hi in every pair" % (name, "0 < " if positive else ""))
+    return a
+
+
+def _sampler_box(default, scale_bounds, offset_bounds):
+    """A context's default box (lo, hi) [K - 1, 2], columns (log a_b, mu_b), with the checked scale_bounds / offset_bounds of
+    run_mcmc put in where given -> the (lo, hi) the context's sampler takes."""
+    lo, hi = default
+    if scale_bounds is not None:
+        lo[:, 0], hi[:, 0] = np.log(scale_bounds[:, 0]), np.log(scale_bounds[:, 1])
+    if offset_bounds is not None:
+        lo[:, 1], hi[:, 1] = offset_bounds[:, 0], offset_bounds[:, 1]
+    return lo, hi
 
 
 class MCMCSample(object):
@@ -700,10 +870,7 @@ class CarmaModel(object):
         process per GPU, every rank makes the same call): the `nreplicas` independent ladders are split over the ranks
         and every rank returns the gathered samples of all of them (parallel.sharded_pt_run) -- the same arrays as the
         single-process call with the same seed."""
-        if ntemperatures is None:
-            ntemperatures = max(10, self.p + self.q)
-        if nburnin is None:
-            nburnin = nsamples // 2
+        nburnin, ntemperatures = _mcmc_defaults(nsamples, nburnin, ntemperatures, self.p, self.q)
         init = carmcmcLib.vecD() if init is None else _vec(init)
         if self.p == 1:
             cpp = carmcmcLib.run_mcmc_car1(nsamples, int(nburnin), self._time, self._y, self._ysig, nthin, init,
@@ -719,17 +886,7 @@ class CarmaModel(object):
     # -- maximum likelihood ---------------------------------------------------------------------
     def _mle_bounds(self, p, q):
         """L-BFGS-B box of the reference (:219-240)."""
-        ysigma = self.y.std()
-        dt = np.diff(self.time)
-        max_freq, min_freq = 0.9 / dt.min(), 1.0 / (self.time.max() - self.time.min())
-        bnds = [(ysigma / 10.0, 10.0 * ysigma), (0.9, 1.1), (None, None)]
-        if p == 1:
-            bnds.append((np.log(min_freq), np.log(max_freq)))
-        else:
-            lo = np.log(min(min_freq ** 2, 2.0 * min_freq))
-            hi = np.log(max(max_freq ** 2, 2.0 * max_freq))
-            bnds += [(lo, hi)] * p + [(None, None)] * q
-        return bnds
+        return mle_bounds(self.time, self.y, p, q)
 
     def _mle_problem(self, p, q, ntrials, seed):
         """(model object, [ntrials, d] starting points, L-BFGS-B box) of a get_mle call (reference :195-240)."""
@@ -739,15 +896,8 @@ class CarmaModel(object):
             proc = carmcmcLib.run_mcmc_carma(1, 25, self._time, self._y, self._ysig, p, q, 10, False, 1,
                                              nreplicas=ntrials, seed=seed)
             proc.SetMLE(True)
-        starts = proc.getAllSamples()[0][:, 0, :].copy()
         bnds = self._mle_bounds(p, q)
-        rng = np.random.default_rng(seed)
-        starts[:, 1] = 1.0                                   # initial guess for the error scale (:217)
-        for j, (lo, hi) in enumerate(bnds):
-            if lo is not None:
-                out = (starts[:, j] < lo) | (starts[:, j] > hi)
-                starts[out, j] = rng.uniform(lo, hi, int(out.sum()))
-        return proc, starts, bnds
+        return proc, _clamp_starts(proc.getAllSamples()[0][:, 0, :].copy(), bnds, seed), bnds
 
     def get_mle(self, p, q, ntrials=100, njobs=1, seed=None, method="batched", return_all=False):
         """Best of `ntrials` bounded quasi-Newton fits started from short tempered MCMC runs
@@ -764,13 +914,8 @@ class CarmaModel(object):
 
         if method == "batched":
             # the lock-step optimiser inside the library (carma_mle.hip): no interpreter between the launches
-            xs, fs, nits, nfevs, sts = proc.minimizeBatch(starts, bnds)
-            results = [BatchResult(xs[i].copy(), float(fs[i]), int(nits[i]), int(nfevs[i]), int(sts[i]) < 2, STATUS_TEXT[int(sts[i])])
-                       for i in range(xs.shape[0])]
-            if return_all:
-                return results
-            results = [r for r in results if np.isfinite(r.fun) and r.fun < 1e299] or results
-            return min(results, key=lambda r: r.fun)
+            results = _batch_results(*proc.minimizeBatch(starts, bnds))
+            return results if return_all else _best_result(results)
         if method != "scipy":
             raise ValueError("method must be 'batched' or 'scipy'")
 
@@ -790,12 +935,7 @@ class CarmaModel(object):
 
     def choose_order(self, pmax, qmax=None, pqlist=None, njobs=1, ntrials=100, seed=None, method="batched"):
         """Minimise AICc over a (p,q) grid (reference :131-192); sets self.p, self.q."""
-        if pmax < 1:
-            raise ValueError("Order of AR polynomial must be at least 1.")
-        if qmax is None:
-            qmax = pmax - 1
-        if pqlist is None:
-            pqlist = [(p, q) for p in range(1, pmax + 1) for q in range(min(p, qmax + 1))]
+        pqlist = _pq_grid(pmax, qmax, pqlist)
         # njobs (reference :131: processes of a multiprocessing pool, -1 = all cores): here THREADS, each driving its own
         # orders -- every order has its own context and stream, the library calls release the interpreter lock, and the
         # launches of one order (a few thousand evaluations) leave most of the chip to the others
@@ -806,14 +946,9 @@ class CarmaModel(object):
                 MLEs = list(pool.map(lambda pq: self.get_mle(pq[0], pq[1], ntrials=ntrials, seed=seed, method=method), pqlist))
         else:
             MLEs = [self.get_mle(p, q, ntrials=ntrials, njobs=njobs, seed=seed, method=method) for p, q in pqlist]
-        AICc, best, best_aicc = [], MLEs[0], 1e300
-        n = self.time.size
-        for mle, (p, q) in zip(MLEs, pqlist):
-            k = 2 + p + q
-            a = 2.0 * k + 2.0 * mle.fun + 2.0 * k * (k + 1.0) / (n - k - 1.0)
-            AICc.append(a)
-            if a < best_aicc:
-                best, best_aicc, self.p, self.q = mle, a, p, q
+        best, AICc, order = _choose_order(MLEs, pqlist, self.time.size)
+        if order is not None:
+            self.p, self.q = order
         return best, pqlist, AICc
 
 
@@ -832,11 +967,7 @@ class CarmaModelSet(object):
             raise ValueError("Order of AR polynomial, p, must be larger than order of MA polynomial, q.")
         self.models = []
         for s, item in enumerate(series):
-            if len(item) != 3:
-                raise ValueError("series %d: expected (time, y, ysig)" % s)
-            t, y, e = (np.asarray(a, dtype=float).ravel() for a in item)
-            if not (t.size == y.size == e.size):
-                raise ValueError("series %d: time, y, ysig must have the same length" % s)
+            t, y, e = _series_item(item, "series", s)
             if np.unique(t).size < 2:
                 raise ValueError("series %d has fewer than 2 distinct times" % s)
             self.models.append(CarmaModel(t, y, e, p=p, q=q))
@@ -856,18 +987,12 @@ class CarmaModelSet(object):
                                            max_stdev=[carmcmcLib._pop_max_stdev(m.y) for m in self.models])
         return self._mctx[key]
 
-    def _which(self, which, B):
-        w = np.broadcast_to(np.asarray(which, dtype=np.int64), (B,))
-        if B and (w.min() < 0 or w.max() >= self.nseries):
-            raise ValueError("series index out of range [0, %d)" % self.nseries)
-        return w
-
     def loglik(self, theta, which):
         """-f of get_mle's objective: the log-density with the prior bounds of the MLE (SetMLE(true) for p > 1) of theta[i]
         on series which[i], every row in one launch."""
         theta = np.asarray(theta, dtype=float)
         rows = np.atleast_2d(theta)
-        w = self._which(which, rows.shape[0])
+        w = _which(which, rows.shape[0], self.nseries, "series")
         out = self.context(self.p, self.q).logdensity(rows, w, ignore_prior=self.p > 1)
         return float(out[0]) if theta.ndim == 1 else out
 
@@ -878,22 +1003,9 @@ class CarmaModelSet(object):
         CarmaSample (p = 1: Car1Sample) in the caller's order, also kept as self.mcmc_samples and models[s].mcmc_sample."""
         p, q, S = self.p, self.q, self.nseries
         d = 4 if p == 1 else 3 + p + q
-        if int(nsamples) < 1:
-            raise ValueError("nsamples must be at least 1")
-        if int(nthin) < 1:
-            raise ValueError("nthin must be at least 1")
-        if int(nreplicas) < 1:
-            raise ValueError("nreplicas must be at least 1")
-        if ntemperatures is None:
-            ntemperatures = max(10, p + q)
-        if not 1 <= int(ntemperatures) <= 64:
-            raise ValueError("ntemperatures must be 1 ... 64 (a ladder is the lanes of one wave), got %d" % int(ntemperatures))
+        nsamples, nburnin, ntemperatures, nthin, nreplicas = _mcmc_args(nsamples, nburnin, ntemperatures, nthin, nreplicas, p, q)
         if p == 1:
             ntemperatures = 1
-        if nburnin is None:
-            nburnin = int(nsamples) // 2
-        if int(nburnin) < 0:
-            raise ValueError("nburnin must not be negative")
         if init is not None:
             init = np.asarray(init, dtype=float)
             if init.shape != (S, d):
@@ -901,7 +1013,7 @@ class CarmaModelSet(object):
         mc = self.context(p, q)
         # longest series first: the ladders that share a wave then have similar lengths
         order = np.argsort(-np.asarray(mc.n), kind="stable")
-        samples, logposts = mc.pt_run(order, int(ntemperatures), int(nreplicas), int(nsamples), int(nburnin), int(nthin),
+        samples, logposts = mc.pt_run(order, ntemperatures, nreplicas, nsamples, nburnin, nthin,
                                       init=None if init is None else init[order], seed=carmcmcLib._seed(seed))
         acc, swp = mc.pt_stats()
         # the "loglik" column (prior bounds ignored) of all series' traces: one launch
@@ -932,13 +1044,7 @@ class CarmaModelSet(object):
         [S, nf].  nsamples: the evenly spaced subsample of each series that the single-series call takes.  Returns
         (lower, upper, median, frequencies), each [S, nf]."""
         S = self.nseries
-        if samples is None:
-            samples = self.mcmc_samples
-            if samples is None:
-                raise ValueError("no samples: call run_mcmc first, or pass samples=")
-        samples = list(samples)
-        if len(samples) != S:
-            raise ValueError("samples must hold one sample object per series (%d), got %d" % (S, len(samples)))
+        samples = _resolve_samples(samples, self.mcmc_samples, S)
         if freq is None:
             freq = np.stack([smp._psd_frequencies() for smp in samples])
         else:
@@ -967,13 +1073,7 @@ class CarmaModelSet(object):
         CarmaSample / Car1Sample, by default self.mcmc_samples of run_mcmc; all must hold the same number of replicas, of
         samples and of parameters."""
         S = self.nseries
-        if samples is None:
-            samples = self.mcmc_samples
-            if samples is None:
-                raise ValueError("no samples: call run_mcmc first, or pass samples=")
-        samples = list(samples)
-        if len(samples) != S:
-            raise ValueError("samples must hold one sample object per series (%d), got %d" % (S, len(samples)))
+        samples = _resolve_samples(samples, self.mcmc_samples, S)
         runs = [smp._sampler.getAllSamples() for smp in samples]
         if any(par is None or lp is None for par, lp in runs):
             raise ValueError("a sample object's sampler holds no samples")
@@ -998,12 +1098,7 @@ class CarmaModelSet(object):
         starts = np.empty((self.nseries, int(ntrials), mc.d))
         starts[order] = samples[:, :, 0, :]
         for s, m in enumerate(self.models):
-            rng = np.random.default_rng(seed)
-            starts[s, :, 1] = 1.0                            # initial guess for the error scale
-            for j, (lo, hi) in enumerate(m._mle_bounds(p, q)):
-                if lo is not None:
-                    out = (starts[s, :, j] < lo) | (starts[s, :, j] > hi)
-                    starts[s, out, j] = rng.uniform(lo, hi, int(out.sum()))
+            _clamp_starts(starts[s], m._mle_bounds(p, q), seed)
         return starts
 
     def get_mle(self, p, q, ntrials=100, seed=None, starts=None, return_all=False):
@@ -1013,13 +1108,12 @@ class CarmaModelSet(object):
         the set's ensemble); else an array [S, ntrials, d].  All S x ntrials starts are then optimised in ONE lock-step run.
         Returns a list of S BatchResult (return_all: S lists of ntrials).  self.timing holds the seconds spent drawing
         starts and optimising."""
-        import time as _time
         if not p > q:
             raise ValueError("Order of AR polynomial, p, must be larger than order of MA polynomial, q.")
         if isinstance(starts, str) and starts != "set":
             raise ValueError("starts must be None, 'set' or an array [S, ntrials, d], got %r" % starts)
         S = self.nseries
-        t0 = _time.perf_counter()
+        t0 = perf_counter()
         if starts is None:
             starts = np.stack([m._mle_problem(p, q, ntrials, seed)[1] for m in self.models])
         elif isinstance(starts, str):
@@ -1029,51 +1123,24 @@ class CarmaModelSet(object):
             d = 4 if p == 1 else 3 + p + q
             if starts.ndim != 3 or starts.shape[0] != S or starts.shape[2] != d:
                 raise ValueError("starts must be [%d, ntrials, %d], got %r" % (S, d, starts.shape))
-        t1 = _time.perf_counter()
+        t1 = perf_counter()
         nt, d = starts.shape[1], starts.shape[2]
-        lo, hi = np.empty((S, d)), np.empty((S, d))
-        for s, m in enumerate(self.models):
-            bnds = m._mle_bounds(p, q)
-            lo[s] = [-np.inf if b[0] is None else b[0] for b in bnds]
-            hi[s] = [np.inf if b[1] is None else b[1] for b in bnds]
+        lo, hi = (np.stack(a) for a in zip(*[_bounds_lohi(m._mle_bounds(p, q)) for m in self.models]))
         which = np.repeat(np.arange(S), nt)
-        xs, fs, nits, nfevs, sts = self.context(p, q).mle_batched(starts.reshape(S * nt, d), which, lo[which], hi[which],
-                                                                  ignore_prior=p > 1)
-        t2 = _time.perf_counter()
-        self.timing = {"starts_s": t1 - t0, "optimise_s": t2 - t1}
-        out = []
-        for s in range(S):
-            res = [BatchResult(xs[i].copy(), float(fs[i]), int(nits[i]), int(nfevs[i]), int(sts[i]) < 2, STATUS_TEXT[int(sts[i])])
-                   for i in range(s * nt, (s + 1) * nt)]
-            if return_all:
-                out.append(res)
-            else:
-                res = [r for r in res if np.isfinite(r.fun) and r.fun < 1e299] or res
-                out.append(min(res, key=lambda r: r.fun))
-        return out
+        res = self.context(p, q).mle_batched(starts.reshape(S * nt, d), which, lo[which], hi[which], ignore_prior=p > 1)
+        self.timing = _timing(t0, t1, perf_counter())
+        return _results_per_member(res, S, nt, return_all)
 
     def choose_order(self, pmax, qmax=None, pqlist=None, ntrials=100, seed=None):
         """CarmaModel.choose_order of every series: one get_mle over the whole set per order, AICc with each series' own n.
         Returns a list of S (best, pqlist, AICc) triples; self.orders holds each series' chosen (p, q)."""
-        if pmax < 1:
-            raise ValueError("Order of AR polynomial must be at least 1.")
-        if qmax is None:
-            qmax = pmax - 1
-        if pqlist is None:
-            pqlist = [(p, q) for p in range(1, pmax + 1) for q in range(min(p, qmax + 1))]
+        pqlist = _pq_grid(pmax, qmax, pqlist)
         MLEs = [self.get_mle(p, q, ntrials=ntrials, seed=seed) for p, q in pqlist]
         out, self.orders = [], []
         for s, m in enumerate(self.models):
-            n = m.time.size
-            AICc, best, best_aicc, order = [], MLEs[0][s], 1e300, pqlist[0]
-            for mles, (p, q) in zip(MLEs, pqlist):
-                k = 2 + p + q
-                a = 2.0 * k + 2.0 * mles[s].fun + 2.0 * k * (k + 1.0) / (n - k - 1.0)
-                AICc.append(a)
-                if a < best_aicc:
-                    best, best_aicc, order = mles[s], a, (p, q)
+            best, AICc, order = _choose_order([mles[s] for mles in MLEs], pqlist, m.time.size)
             out.append((best, pqlist, AICc))
-            self.orders.append(order)
+            self.orders.append(order or pqlist[0])
         return out
 
     def _fit_items(self, fits, orders):
@@ -1107,39 +1174,29 @@ class CarmaModelSet(object):
                              np.array([m[3] for m in mods]))
         return items
 
-    def predict(self, times, fits, orders=None):
-        """CarmaSample.predict of every series at its fitted model: expected value and variance at `times` -- one array for
-        every series, or a list of S arrays -- given the series' data.  fits: S results as get_mle returns them (or the best of
-        each choose_order triple); orders: see _fit_items.  The series are grouped by order, one launch per order present.
-        Returns two lists of S arrays."""
-        if isinstance(times, (list, tuple)) and len(times) and not np.isscalar(times[0]):
-            tlist = [np.atleast_1d(np.asarray(t, dtype=float)).ravel() for t in times]
-            if len(tlist) != self.nseries:
-                raise ValueError("times must be one array, or one per series (%d), got %d" % (self.nseries, len(tlist)))
-        else:
-            tlist = [np.atleast_1d(np.asarray(times, dtype=float)).ravel()] * self.nseries
+    def _at_times(self, method, times, fits, orders):
+        """predict / smooth: `method` of every order's context at its series' times."""
+        tlist = _times_per_row(times, self.nseries)
+        if len(tlist) != self.nseries:
+            raise ValueError("times must be one array, or one per series (%d), got %d" % (self.nseries, len(tlist)))
         mean, var = [None] * self.nseries, [None] * self.nseries
         for (p, q), (idx, sig, roots, ma, mu) in self._fit_items(fits, orders).items():
-            pm, pv = self.context(p, q).predict(idx, sig, roots, ma, [tlist[s] for s in idx], mu=mu)
+            pm, pv = getattr(self.context(p, q), method)(idx, sig, roots, ma, [tlist[s] for s in idx], mu=mu)
             for k, s in enumerate(idx):
                 mean[s], var[s] = pm[k], pv[k]
         return mean, var
 
+    def predict(self, times, fits, orders=None):
+        """CarmaSample.predict of every series at its fitted model: expected value and variance at `times` -- one array for
+        every series, or one per series (a list of S arrays, or an array [S, M]) -- given the series' data.  fits: S results as
+        get_mle returns them (or the best of each choose_order triple); orders: see _fit_items.  The series are grouped by order,
+        one launch per order present.  Returns two lists of S arrays."""
+        return self._at_times("predict", times, fits, orders)
+
     def smooth(self, times, fits, orders=None):
         """predict(times, fits, orders) by the one-pass smoother (CarmaSample.smooth of every series at its fitted model;
         MultiContext.smooth): arguments and return values as predict, one call per order present."""
-        if isinstance(times, (list, tuple)) and len(times) and not np.isscalar(times[0]):
-            tlist = [np.atleast_1d(np.asarray(t, dtype=float)).ravel() for t in times]
-            if len(tlist) != self.nseries:
-                raise ValueError("times must be one array, or one per series (%d), got %d" % (self.nseries, len(tlist)))
-        else:
-            tlist = [np.atleast_1d(np.asarray(times, dtype=float)).ravel()] * self.nseries
-        mean, var = [None] * self.nseries, [None] * self.nseries
-        for (p, q), (idx, sig, roots, ma, mu) in self._fit_items(fits, orders).items():
-            pm, pv = self.context(p, q).smooth(idx, sig, roots, ma, [tlist[s] for s in idx], mu=mu)
-            for k, s in enumerate(idx):
-                mean[s], var[s] = pm[k], pv[k]
-        return mean, var
+        return self._at_times("smooth", times, fits, orders)
 
     def assess_fit(self, fits, orders=None, nplot=256):
         """CarmaSample.assess_fit of every series at its fitted model: a list of S dicts with the interpolated path on `nplot`
@@ -1183,11 +1240,7 @@ class CarmaBandsModel(object):
             raise ValueError("Order of AR polynomial, p, must be larger than order of MA polynomial, q.")
         self.bands = []
         for b, item in enumerate(bands):
-            if len(item) != 3:
-                raise ValueError("band %d: expected (time, y, ysig)" % b)
-            t, y, e = (np.asarray(a, dtype=float).ravel() for a in item)
-            if not (t.size == y.size == e.size) or t.size < 1:
-                raise ValueError("band %d: time, y, ysig must have the same length, at least 1" % b)
+            t, y, e = _series_item(item, "band", b, least=1)
             _, idx = np.unique(t, return_index=True)         # sorted, first occurrence of each time
             self.bands.append((t[idx], y[idx], e[idx]))
         self.K = len(self.bands)
@@ -1228,10 +1281,15 @@ class CarmaBandsModel(object):
         uniform in their boxes, log a_b = log(std y_b / std y_0), mu_b = mean y_b."""
         t0, y0, e0 = self.bands[0]
         _, st, bnds = CarmaModel(t0, y0, e0, p=self.p, q=self.q)._mle_problem(self.p, self.q, ntrials, seed)
-        return self._extend_starts(st, bnds, seed)
+        return (self._extend_starts(st, seed),) + self._box(bnds)
 
-    def _extend_starts(self, st, bnds, seed):
-        """_starts behind its CARMA part: st [ntrials, d] and the box bnds of band 0's CarmaModel."""
+    def _box(self, bnds):
+        """(lo [dx], hi [dx]) of the optimiser: the box bnds of band 0's CarmaModel, the band columns unbounded (the lags stay in
+        their boxes inside the library)."""
+        return _bounds_lohi(bnds + [(None, None)] * (3 * (self.K - 1)))
+
+    def _extend_starts(self, st, seed):
+        """_starts behind its CARMA part st [ntrials, d]: the band columns."""
         y0 = self.bands[0][1]
         rng = np.random.default_rng(seed)
         x0 = np.empty((st.shape[0], self.dx))
@@ -1243,25 +1301,15 @@ class CarmaBandsModel(object):
             x0[:, c] = rng.uniform(self.lag_bounds[b - 1, 0], self.lag_bounds[b - 1, 1], st.shape[0])
             x0[:, c + 1] = np.log(yb.std() / s0) if yb.std() > 0 and s0 > 0 else 0.0
             x0[:, c + 2] = yb.mean()
-        lo = np.array([-np.inf if b[0] is None else b[0] for b in bnds] + [-np.inf] * (3 * (self.K - 1)))
-        hi = np.array([np.inf if b[1] is None else b[1] for b in bnds] + [np.inf] * (3 * (self.K - 1)))
-        return x0, lo, hi
-
-    @staticmethod
-    def _results(xs, fs, nits, nfevs, sts):
-        return [BatchResult(xs[i].copy(), float(fs[i]), int(nits[i]), int(nfevs[i]), int(sts[i]) < 2, STATUS_TEXT[int(sts[i])])
-                for i in range(xs.shape[0])]
+        return x0
 
     def get_mle(self, ntrials=100, seed=None, return_all=False):
         """Best of `ntrials` bounded quasi-Newton fits of the extended vector, all advanced in lock-step
         (carma_bands_mle_batched); the lags stay inside their boxes.  Returns an object with .x, .fun (= -loglik), .message
         (return_all: the list of all ntrials results, in the order of the starts)."""
         x0, lo, hi = self._starts(ntrials, seed)
-        results = self._results(*self.context().mle_batched(x0, lo, hi, ignore_prior=self.p > 1))
-        if return_all:
-            return results
-        results = [r for r in results if np.isfinite(r.fun) and r.fun < 1e299] or results
-        return min(results, key=lambda r: r.fun)
+        results = _batch_results(*self.context().mle_batched(x0, lo, hi, ignore_prior=self.p > 1))
+        return results if return_all else _best_result(results)
 
     def lag_profile(self, lags, ntrials=8, seed=None):
         """The profile log-likelihood over the lags: at each of the L rows of `lags` ([L] for two bands, else [L, K - 1]) the
@@ -1270,21 +1318,14 @@ class CarmaBandsModel(object):
         whose lag entries are the given lags unchanged."""
         if self.K < 2:
             raise ValueError("lag_profile needs at least two bands")
-        lags = np.asarray(lags, dtype=float)
-        lags = lags.reshape(-1, 1) if self.K == 2 and lags.ndim == 1 else np.atleast_2d(lags)
-        if lags.shape[1] != self.K - 1:
-            raise ValueError("lags must be [L] for two bands or [L, %d]" % (self.K - 1))
-        if not np.all((lags >= self.lag_bounds[:, 0]) & (lags <= self.lag_bounds[:, 1])):
-            raise ValueError("every lag must lie inside its box (lag_bounds)")
+        lags = _lag_grid(lags, self.K, self.lag_bounds)
         L = lags.shape[0]
         x0, lo, hi = self._starts(ntrials, seed)
         nt = x0.shape[0]
         fixed = np.repeat(lags, nt, axis=0)
         xs, fs, nits, nfevs, sts = self.context().mle_batched(np.tile(x0, (L, 1)), lo, hi, fixed_lag=fixed,
                                                               ignore_prior=self.p > 1)
-        fs = np.where(np.isfinite(fs), fs, 1e300).reshape(L, nt)
-        best = fs.argmin(axis=1)
-        return -fs[np.arange(L), best], xs.reshape(L, nt, self.dx)[np.arange(L), best]
+        return _profile_best(fs, xs, L, nt)
 
     def _smooth_rows(self, theta, time, band, moments):
         out = self.context().smooth(theta, band, time, moments=moments)
@@ -1306,23 +1347,6 @@ class CarmaBandsModel(object):
         the optima of a lag_profile, of get_mle(return_all=True), or whatever vectors the caller holds.  Mixed on the device."""
         return self._smooth_rows(thetas, time, band, True)[2:]
 
-    def _band_box(self, scale_bounds, offset_bounds):
-        """The (K - 1, 2) arrays run_mcmc was given, checked: scale_bounds = (lo, hi) of a_b > 0, offset_bounds = (lo, hi) of
-        mu_b, one pair per band after the first; None stays None (the default box)."""
-        out = []
-        for name, v in (("scale_bounds", scale_bounds), ("offset_bounds", offset_bounds)):
-            if v is None:
-                out.append(None)
-                continue
-            a = np.asarray(v, dtype=float)
-            if a.shape != (self.K - 1, 2):
-                raise ValueError("%s must hold one (lo, hi) pair for each of the %d bands after the first, got shape %r"
-                                 % (name, self.K - 1, a.shape))
-            if not np.all(a[:, 0] <= a[:, 1]) or (name == "scale_bounds" and not np.all(a[:, 0] > 0)):
-                raise ValueError("%s: need %slo <= hi in every pair" % (name, "0 < " if name == "scale_bounds" else ""))
-            out.append(a)
-        return out
-
     def run_mcmc(self, nsamples, nburnin=None, ntemperatures=None, nthin=1, init=None, nreplicas=1, seed=None, scale_bounds=None,
                  offset_bounds=None):
         """Parallel-tempered RAM sampler on the extended vector (carma_bands_pt_run): the posterior of the lags, scales and
@@ -1335,27 +1359,17 @@ class CarmaBandsModel(object):
         Returns a CarmaBandsSample (all replicas' cold-chain draws), kept as mcmc_sample."""
         if self.K < 1:
             raise ValueError("run_mcmc needs at least one band")
-        if int(nsamples) < 1:
-            raise ValueError("nsamples must be at least 1")
-        if int(nthin) < 1 or int(nreplicas) < 1:
-            raise ValueError("nthin and nreplicas must be at least 1")
+        nsamples, nburnin, ntemperatures, nthin, nreplicas = _mcmc_args(nsamples, nburnin, ntemperatures, nthin, nreplicas,
+                                                                        self.p, self.q)
         if init is not None:
             init = np.asarray(init, dtype=float)
             if init.shape != (self.dx,):
                 raise ValueError("init must be [%d], got %r" % (self.dx, init.shape))
-        sb, ob = self._band_box(scale_bounds, offset_bounds)
-        if ntemperatures is None:
-            ntemperatures = max(10, self.p + self.q)
-        if nburnin is None:
-            nburnin = int(nsamples) // 2
+        sb = _band_bounds("scale_bounds", scale_bounds, self.K, positive=True)
+        ob = _band_bounds("offset_bounds", offset_bounds, self.K)
         ctx = self.context()
-        lo, hi = ctx.pt_default_box()
-        if sb is not None:
-            lo[:, 0], hi[:, 0] = np.log(sb[:, 0]), np.log(sb[:, 1])
-        if ob is not None:
-            lo[:, 1], hi[:, 1] = ob[:, 0], ob[:, 1]
-        samples, logposts = ctx.pt_run(int(ntemperatures), int(nreplicas), int(nsamples), int(nburnin), int(nthin), init,
-                                       carmcmcLib._seed(seed), band_box=(lo, hi))
+        samples, logposts = ctx.pt_run(ntemperatures, nreplicas, nsamples, nburnin, nthin, init, carmcmcLib._seed(seed),
+                                       band_box=_sampler_box(ctx.pt_default_box(), sb, ob))
         self.mcmc_sample = CarmaBandsSample(self, samples, logposts)
         return self.mcmc_sample
 
@@ -1434,16 +1448,10 @@ class CarmaBandsSet(object):
                                         max_stdev=[carmcmcLib._pop_max_stdev(m.bands[0][1]) for m in self.models])
         return self._ctx
 
-    def _which(self, which, B):
-        w = np.broadcast_to(np.asarray(which, dtype=np.int64), (B,))
-        if B and (w.min() < 0 or w.max() >= self.nobjects):
-            raise ValueError("object index out of range [0, %d)" % self.nobjects)
-        return w
-
     def _logdensity(self, theta, which, ignore_prior):
         theta = np.asarray(theta, dtype=float)
         rows = np.atleast_2d(theta)
-        w = self._which(which, rows.shape[0])
+        w = _which(which, rows.shape[0], self.nobjects, "object")
         out = self.context().logdensity(rows, w, ignore_prior=ignore_prior)
         return float(out[0]) if theta.ndim == 1 else out
 
@@ -1457,13 +1465,8 @@ class CarmaBandsSet(object):
 
     def _boxes(self):
         """(lo, hi) [S, dx]: each object's optimiser box, as CarmaBandsModel._starts gives it."""
-        lo, hi = np.empty((self.nobjects, self.dx)), np.empty((self.nobjects, self.dx))
-        for s, m in enumerate(self.models):
-            t0, y0, e0 = m.bands[0]
-            b = CarmaModel.__new__(CarmaModel)
-            b.time, b.y = t0, y0
-            _, lo[s], hi[s] = m._extend_starts(np.empty((0, self.d)), b._mle_bounds(self.p, self.q), None)
-        return lo, hi
+        boxes = [m._box(mle_bounds(m.bands[0][0], m.bands[0][1], self.p, self.q)) for m in self.models]
+        return tuple(np.stack(a) for a in zip(*boxes))
 
     def get_mle(self, ntrials=100, seed=None, starts=None, return_all=False):
         """CarmaBandsModel.get_mle of every object.  starts None: each object's starts drawn exactly as its CarmaBandsModel
@@ -1472,65 +1475,42 @@ class CarmaBandsSet(object):
         an array [S, ntrials, dx].  All S x ntrials starts are then optimised in ONE lock-step run.  Returns a list of S results
         (return_all: S lists of ntrials).  self.timing holds the seconds spent drawing starts and optimising.  smooth() takes
         the list this returns and draws every object's interpolated light curves in its K bands, in one call."""
-        import time as _time
         if isinstance(starts, str) and starts != "set":
             raise ValueError("starts must be None, 'set' or an array [S, ntrials, dx], got %r" % starts)
         S = self.nobjects
-        t0 = _time.perf_counter()
+        t0 = perf_counter()
         if starts is None:
             starts = np.stack([m._starts(ntrials, seed)[0] for m in self.models])
         elif isinstance(starts, str):
             band0 = CarmaModelSet([m.bands[0] for m in self.models], p=self.p, q=self.q)
             carma = band0._set_starts(self.p, self.q, ntrials, seed)
-            starts = np.stack([m._extend_starts(carma[s], b0._mle_bounds(self.p, self.q), seed)[0]
-                               for s, (m, b0) in enumerate(zip(self.models, band0.models))])
+            starts = np.stack([m._extend_starts(carma[s], seed) for s, m in enumerate(self.models)])
         else:
             starts = np.asarray(starts, dtype=float)
             if starts.ndim != 3 or starts.shape[0] != S or starts.shape[2] != self.dx:
                 raise ValueError("starts must be [%d, ntrials, %d], got %r" % (S, self.dx, starts.shape))
         lo, hi = self._boxes()
-        t1 = _time.perf_counter()
+        t1 = perf_counter()
         nt = starts.shape[1]
         which = np.repeat(np.arange(S), nt)
-        xs, fs, nits, nfevs, sts = self.context().mle_batched(starts.reshape(S * nt, self.dx), which, lo[which], hi[which],
-                                                              ignore_prior=self.p > 1)
-        t2 = _time.perf_counter()
-        self.timing = {"starts_s": t1 - t0, "optimise_s": t2 - t1}
-        out = []
-        for s in range(S):
-            k = slice(s * nt, (s + 1) * nt)
-            res = CarmaBandsModel._results(xs[k], fs[k], nits[k], nfevs[k], sts[k])
-            if not return_all:
-                res = [r for r in res if np.isfinite(r.fun) and r.fun < 1e299] or res
-                res = min(res, key=lambda r: r.fun)
-            out.append(res)
-        return out
+        res = self.context().mle_batched(starts.reshape(S * nt, self.dx), which, lo[which], hi[which], ignore_prior=self.p > 1)
+        self.timing = _timing(t0, t1, perf_counter())
+        return _results_per_member(res, S, nt, return_all)
 
     def _lag_grids(self, lags):
         """lags of lag_profile -> S arrays [L_s, K - 1], each checked against its object's boxes.  One grid for all objects
         ([L] for two bands, else [L, K - 1]), or a list (not an array) of S grids."""
         K, S = self.K, self.nobjects
         per = isinstance(lags, (list, tuple)) and len(lags) == S and all(np.ndim(g) >= (1 if K == 2 else 2) for g in lags)
-        grids = []
-        for s, g in enumerate(lags if per else [lags] * S):
-            g = np.asarray(g, dtype=float)
-            g = g.reshape(-1, 1) if K == 2 and g.ndim == 1 else np.atleast_2d(g)
-            if g.shape[1] != K - 1:
-                raise ValueError("lags must be [L] for two bands or [L, %d], for all objects or a list of one per object" % (K - 1))
-            lb = self.models[s].lag_bounds
-            if not np.all((g >= lb[:, 0]) & (g <= lb[:, 1])):
-                raise ValueError("object %d: every lag must lie inside its box (lag_bounds)" % s)
-            grids.append(g)
-        return grids
+        return [_lag_grid(g, K, self.models[s].lag_bounds, obj=s) for s, g in enumerate(lags if per else [lags] * S)]
 
     def lag_profile(self, lags, ntrials=8, seed=None):
         """CarmaBandsModel.lag_profile of every object: `lags` is one grid for all objects or a list of one grid per object;
         all S x L x ntrials starts run in ONE lock-step call.  Returns a list of S (loglik [L], x [L, dx])."""
-        import time as _time
         if self.K < 2:
             raise ValueError("lag_profile needs at least two bands")
         grids = self._lag_grids(lags)
-        t0 = _time.perf_counter()
+        t0 = perf_counter()
         x0s, los, his, fixed, which = [], [], [], [], []
         for s, (m, g) in enumerate(zip(self.models, grids)):
             x0, lo, hi = m._starts(ntrials, seed)
@@ -1540,26 +1520,22 @@ class CarmaBandsSet(object):
             his.append(np.tile(hi, (L * nt, 1)))
             fixed.append(np.repeat(g, nt, axis=0))
             which.append(np.full(L * nt, s))
-        t1 = _time.perf_counter()
+        t1 = perf_counter()
         xs, fs, nits, nfevs, sts = self.context().mle_batched(np.concatenate(x0s), np.concatenate(which), np.concatenate(los),
                                                               np.concatenate(his), fixed_lag=np.concatenate(fixed),
                                                               ignore_prior=self.p > 1)
-        t2 = _time.perf_counter()
-        self.timing = {"starts_s": t1 - t0, "optimise_s": t2 - t1}
+        self.timing = _timing(t0, t1, perf_counter())
         out, k = [], 0
         for g in grids:
             L, nt = g.shape[0], x0s[len(out)].shape[0] // g.shape[0]
-            f = fs[k:k + L * nt]
-            f = np.where(np.isfinite(f), f, 1e300).reshape(L, nt)
-            best = f.argmin(axis=1)
-            out.append((-f[np.arange(L), best], xs[k:k + L * nt].reshape(L, nt, self.dx)[np.arange(L), best]))
+            out.append(_profile_best(fs[k:k + L * nt], xs[k:k + L * nt], L, nt))
             k += L * nt
         return out
 
     def smooth(self, thetas, time, band=None):
         """CarmaBandsModel.smooth of every object, in ONE call for all objects, bands and rows (carma_bandset_smooth).  thetas: a
         list of S entries, one per object: a vector [dx], an array [B_s, dx] or an object with .x (what get_mle returns); time:
-        one array for all objects or a list of S arrays; band: None (all K bands), an int or a list of bands.  Returns a list of
+        one array for all objects, or one per object -- a list of S arrays or an array [S, M]; any other count is a ValueError; band: None (all K bands), an int or a list of bands.  Returns a list of
         S (mean, var), arrays [nbands, B_s, M_s] -- without the row axis where the entry was a single vector, without the band
         axis where band is an int; every entry has the bits of models[s].smooth(theta, time, band=b).  ValueError on an invalid
         row, named by object and row."""
@@ -1567,8 +1543,9 @@ class CarmaBandsSet(object):
         thetas = list(thetas)
         if len(thetas) != S:
             raise ValueError("thetas must hold one entry per object (%d), got %d" % (S, len(thetas)))
-        per = isinstance(time, (list, tuple)) and len(time) == S and all(np.ndim(t) > 0 for t in time)
-        times = [np.asarray(t, dtype=float).ravel() for t in (time if per else [time] * S)]
+        times = [np.atleast_1d(np.asarray(t, dtype=float)).ravel() for t in _times_per_row(time, S)]
+        if len(times) != S:
+            raise ValueError("time must be one array, or one per object (%d), got %d" % (S, len(times)))
         bands = list(range(self.K)) if band is None else [int(b) for b in np.atleast_1d(band)]
         rows, which, bo, tl, ones = [], [], [], [], []
         for s, th in enumerate(thetas):
@@ -1601,9 +1578,9 @@ class CarmaBandsSet(object):
             out.append(tuple(pair))
         return out
 
-    def _run_boxes(self, which, name, bounds):
-        """scale_bounds / offset_bounds of run_mcmc -> a list of len(which) entries, None or [K - 1, 2], each checked by its
-        model's _band_box: None, one [K - 1, 2] for all objects, or [len(which), K - 1, 2]."""
+    def _run_bounds(self, which, name, bounds, positive=False):
+        """scale_bounds / offset_bounds of run_mcmc -> a list of len(which) entries, None or [K - 1, 2], each checked
+        (_band_bounds): None, one [K - 1, 2] for all objects, or [len(which), K - 1, 2]."""
         if bounds is None:
             return [None] * len(which)
         a = np.asarray(bounds, dtype=float)
@@ -1615,10 +1592,9 @@ class CarmaBandsSet(object):
         out = []
         for i, s in enumerate(which):
             try:
-                pair = self.models[s]._band_box(a[i] if name == "scale_bounds" else None, a[i] if name == "offset_bounds" else None)
+                out.append(_band_bounds(name, a[i], self.K, positive))
             except ValueError as ex:
                 raise ValueError("object %d: %s" % (s, ex))
-            out.append(pair[0] if name == "scale_bounds" else pair[1])
         return out
 
     def run_mcmc(self, nsamples, nburnin=None, ntemperatures=None, nthin=1, init=None, nreplicas=1, seed=None, scale_bounds=None,
@@ -1630,10 +1606,8 @@ class CarmaBandsSet(object):
         [len(which), K - 1, 2].  The default ladder fills 10 of a wave's 64 lanes: nreplicas fills the rest at no cost in time.
         Returns a list of CarmaBandsSample, one per entry of `which` in the caller's order, each also kept as that model's
         mcmc_sample."""
-        if int(nsamples) < 1:
-            raise ValueError("nsamples must be at least 1")
-        if int(nthin) < 1 or int(nreplicas) < 1:
-            raise ValueError("nthin and nreplicas must be at least 1")
+        nsamples, nburnin, ntemperatures, nthin, nreplicas = _mcmc_args(nsamples, nburnin, ntemperatures, nthin, nreplicas,
+                                                                        self.p, self.q)
         if which is None:
             which = np.arange(self.nobjects)
         which = np.asarray(which)
@@ -1649,28 +1623,16 @@ class CarmaBandsSet(object):
                 init = np.broadcast_to(init, (M, self.dx))
             if init.shape != (M, self.dx):
                 raise ValueError("init must be [%d] or [%d, %d] (one row per object of which), got %r" % (self.dx, M, self.dx, init.shape))
-        sbs = self._run_boxes(which, "scale_bounds", scale_bounds)
-        obs = self._run_boxes(which, "offset_bounds", offset_bounds)
-        if ntemperatures is None:
-            ntemperatures = max(10, self.p + self.q)
-        if not 1 <= int(ntemperatures) <= 64:
-            raise ValueError("ntemperatures must be 1 ... 64 (a ladder is the lanes of one wave), got %d" % int(ntemperatures))
-        if nburnin is None:
-            nburnin = int(nsamples) // 2
-        if int(nburnin) < 0:
-            raise ValueError("nburnin must not be negative")
+        sbs = self._run_bounds(which, "scale_bounds", scale_bounds, positive=True)
+        obs = self._run_bounds(which, "offset_bounds", offset_bounds)
         ctx = self.context()
         lo, hi = np.empty((M, self.K - 1, 2)), np.empty((M, self.K - 1, 2))
         for i, s in enumerate(which):
-            lo[i], hi[i] = ctx.pt_default_box(s)
-            if sbs[i] is not None:
-                lo[i, :, 0], hi[i, :, 0] = np.log(sbs[i][:, 0]), np.log(sbs[i][:, 1])
-            if obs[i] is not None:
-                lo[i, :, 1], hi[i, :, 1] = obs[i][:, 0], obs[i][:, 1]
+            lo[i], hi[i] = _sampler_box(ctx.pt_default_box(s), sbs[i], obs[i])
         # longest object first: the waves in flight together then have similar trip counts
         order = np.argsort(-ctx.n.sum(axis=1)[which], kind="stable")
         runs = which[order]
-        samples, logposts = ctx.pt_run(runs, int(ntemperatures), int(nreplicas), int(nsamples), int(nburnin), int(nthin),
+        samples, logposts = ctx.pt_run(runs, ntemperatures, nreplicas, nsamples, nburnin, nthin,
                                        init=None if init is None else init[order], seed=carmcmcLib._seed(seed),
                                        band_box=(lo[order], hi[order]))
         # the "loglik" column (prior bounds ignored) of all objects' draws: one launch; the "sigma" column: one more

@@ -11,10 +11,8 @@ import numpy as np
 import pytest
 
 import carma_pack_amd._lib as L
+from fakelib import H, FakeLib, fill, null, rd, setref, val, wr
 
-H = 0x5000                                                    # the handle every scripted create function returns
-CREATORS = ("carma_ctx_create", "carma_mctx_create", "carma_bands_create", "carma_kf_create_car1", "carma_kf_create_carma",
-            "carma_comm_create")
 N, P, Q, D, R, T = 5, 3, 1, 6, 2, 3
 T5, Y5, E5 = np.arange(5.0), np.array([1.0, 3.0, 2.0, 5.0, 4.0]), np.full(5, 0.1)
 SERIES = [(T5[:3], Y5[:3], E5[:3]), (T5[3:], Y5[3:], E5[3:])]
@@ -23,66 +21,6 @@ ROOTS3 = np.stack([ROOTS, 2 * ROOTS, 3 * ROOTS])
 MA3 = np.array([[1.0, 0.5], [1.0, 0.25], [1.0, 0.125]])
 SIG3 = np.array([1.0, 2.0, 3.0])
 REIM3 = np.stack([ROOTS3.real, ROOTS3.imag], axis=-1)
-CTYPES = {float: C.c_double, np.int32: C.c_int, np.int64: C.c_long}
-
-
-def _view(p, shape, dtype=float):
-    n = int(np.prod(shape))
-    addr = C.cast(p, C.c_void_p).value
-    assert addr, "NULL where an array was expected"
-    return np.ctypeslib.as_array((CTYPES[dtype] * n).from_address(addr)).reshape(shape)
-
-
-def rd(p, shape, dtype=float):
-    """A copy of the array behind a pointer argument."""
-    return _view(p, shape, dtype).copy()
-
-
-def wr(p, values, dtype=float):
-    """Write `values` (any shape, C order) through an output pointer."""
-    values = np.asarray(values)
-    _view(p, values.shape, dtype)[...] = values
-
-
-def fill(p, shape, start=0, dtype=float):
-    wr(p, np.arange(start, start + int(np.prod(shape))).reshape(shape), dtype)
-
-
-def val(x):
-    """A scalar argument as a Python number, whether it came as one or as a ctypes object; None stays None (NULL)."""
-    return x.value if hasattr(x, "value") else x
-
-
-def null(p):
-    return p is None or not C.cast(p, C.c_void_p).value
-
-
-def setref(ref, v):
-    ref._obj.value = v                                         # (the object behind a byref())
-
-
-class FakeLib:
-    def __init__(self):
-        self.calls, self.on, self.error = [], {}, b"scripted failure"
-
-    def __getattr__(self, name):
-        if not name.startswith("carma_"):
-            raise AttributeError(name)
-
-        def fn(*a):
-            self.calls.append((name, a))
-            if name in self.on:
-                return self.on[name](*a)
-            if name == "carma_last_error":
-                return self.error
-            return H if name in CREATORS else None if name.endswith("_destroy") else 0
-        return fn
-
-    def args(self, name, k=-1):
-        return [a for n, a in self.calls if n == name][k]
-
-    def count(self, name):
-        return sum(n == name for n, _ in self.calls)
 
 
 @pytest.fixture
@@ -96,7 +34,7 @@ def fake(monkeypatch):
     yield f
     # an object a traceback still holds is released after the real library is back: it must not hand that one a scripted handle
     for o in gc.get_objects():
-        if type(o) in (L.Context, L.MultiContext, L.BandsContext, L.KalmanHandle, L.Comm) and getattr(o, "_h", None) in (H, H + 8, H + 16):
+        if type(o) in (L.Context, L.MultiContext, L.BandsContext, L.BandsSetContext, L.KalmanHandle, L.Comm) and getattr(o, "_h", None) in (H, H + 8, H + 16):
             o._h = None
 
 
@@ -730,6 +668,291 @@ def test_bandscontext_mle_batched(fake):
         bc.mle_batched(np.zeros((3, D)))
     with pytest.raises(ValueError):
         bc.mle_batched(x0, fixed_lag=[0.5, 1.5])
+
+
+def test_bandscontext_sampler_band_box_and_failed_calls(fake):
+    bc = make_bands(fake, K=2)
+    dx, S = bc.dx, 4
+    for call in (lambda: bc.pt_set_chains(np.zeros(R * T * dx)), bc.pt_get_chains, bc.pt_stats, lambda: bc.pt_logdensity(np.zeros(1))):
+        with pytest.raises(ValueError) as e:
+            call()
+        assert str(e.value) == "call pt_create first"
+    bc.pt_start()                                              # (one object has no run count to look up: the library's check)
+    assert fake.count("carma_bands_pt_start") == 1
+    with pytest.raises(ValueError, match="temperatures must hold ntemps = 3 values"):
+        bc.pt_create(T, R, 10, temperatures=[1.0, 2.0])
+    bc.pt_create(T, R, 40, seed=-1, temperatures=[1.0, 2.0, 4.0])
+    a = fake.args("carma_bands_pt_create")
+    assert a[0] == H and [val(v) for v in a[1:3]] == [T, R] and rd(a[3], (T,)).tolist() == [1.0, 2.0, 4.0]
+    assert [val(v) for v in a[4:6]] == [40, 2 ** 64 - 1] and null(a[6]) and null(a[7]) and bc._pt_shape == (R, T)
+    box = (np.array([[-1.0, -2.0]]), [3.0, 4.0])               # [K - 1, 2], or anything of its size
+    bc.pt_create(T, R, 40, band_box=box)
+    a = fake.args("carma_bands_pt_create")
+    assert null(a[3]) and rd(a[6], (1, 2)).tolist() == [[-1.0, -2.0]] and rd(a[7], (1, 2)).tolist() == [[3.0, 4.0]]
+    with pytest.raises(ValueError):
+        bc.pt_create(T, R, 40, band_box=(np.zeros((2, 2)), np.zeros((2, 2))))
+    bc.pt_start()
+    assert fake.args("carma_bands_pt_start")[0] == H and null(fake.args("carma_bands_pt_start")[1])
+    init = np.arange(1.0 * dx)
+    bc.pt_start(init)
+    assert rd(fake.args("carma_bands_pt_start")[1], (dx,)).tolist() == init.tolist()
+    with pytest.raises(ValueError, match=r"init must be \[9\], got \(1, 9\)"):
+        bc.pt_start(init[None])
+    fake.on["carma_bands_pt_run"] = lambda *a: (fill(a[10], (R, S, dx)), fill(a[11], (R, S), 5), 0)[2]
+    s, lp = bc.pt_run(T, R, S, 30, thin=2, init=init, seed=7, band_box=box)
+    a = fake.args("carma_bands_pt_run")
+    assert a[0] == H and [val(v) for v in a[1:6]] == [T, R, S, 30, 2] and rd(a[6], (dx,)).tolist() == init.tolist() and val(a[7]) == 7
+    assert rd(a[8], (1, 2)).tolist() == [[-1.0, -2.0]] and rd(a[9], (1, 2)).tolist() == [[3.0, 4.0]]
+    assert np.array_equal(s, np.arange(1.0 * R * S * dx).reshape(R, S, dx)) and np.array_equal(lp, 5 + np.arange(8.0).reshape(R, S))
+    bc.pt_run(T, R, S, 30)
+    a = fake.args("carma_bands_pt_run")
+    assert null(a[6]) and null(a[8]) and null(a[9]) and bc.pt_stats()[0].shape == (R, T)
+    # a failed create or run leaves no sampler behind
+    for name, call in (("carma_bands_pt_create", lambda: bc.pt_create(T, R, 40)), ("carma_bands_pt_run", lambda: bc.pt_run(T, R, S, 30))):
+        bc.pt_create(T, R, 40)
+        assert bc._pt_shape == (R, T)
+        fake.on[name] = lambda *a: -22
+        with pytest.raises(ValueError, match=r"%s failed \(-22\)" % name):
+            call()
+        assert bc._pt_shape is None
+        with pytest.raises(ValueError) as e:
+            bc.pt_get_chains()
+        assert str(e.value) == "call pt_create first"
+        del fake.on[name]
+
+
+def test_multicontext_sampler_failed_calls(fake):
+    mc = make_mctx(fake)
+    for name, call in (("carma_mpt_create", lambda: mc.pt_create([0], T, R, 40)), ("carma_mpt_run", lambda: mc.pt_run([0], T, R, 4, 30))):
+        mc.pt_create([1, 0, 1], T, R, 40)
+        assert mc._pt_shape == (3, R, T)
+        fake.on[name] = lambda *a: -22
+        with pytest.raises(ValueError, match=r"%s failed \(-22\)" % name):
+            call()
+        assert mc._pt_shape is None                            # a failed create or run leaves no sampler behind
+        del fake.on[name]
+
+
+# ---- BandsSetContext ----------------------------------------------------------------------------------
+OBJECTS = [SERIES, [(T5[:3] + 10.0, 2.0 * Y5[:3], E5[:3]), (T5[3:] + 10.0, 3.0 * Y5[3:], E5[3:])]]
+DX = D + 3
+
+
+def make_bandset(fake, K=2, **kw):
+    fake.on.update(carma_bandset_nobjects=lambda h: 2, carma_bandset_nbands=lambda h: K, carma_bandset_dim=lambda h: D + 3 * (K - 1),
+                   carma_bandset_n=lambda h, s, b: (3, 2)[b])
+    if K == 2:
+        kw.setdefault("lag_bounds", [(-1.0, 1.5)])
+    return L.BandsSetContext([o[:K] for o in OBJECTS], P, Q, **kw)
+
+
+def test_bandsetcontext_create(fake):
+    bs = make_bandset(fake, device=1)
+    a = fake.args("carma_bandset_create")
+    cat = [np.concatenate([b[i] for o in OBJECTS for b in o]) for i in range(3)]
+    assert [rd(a[i], (2 * N,)).tolist() for i in range(3)] == [c.tolist() for c in cat]
+    assert rd(a[3], (5,), np.int64).tolist() == [0, 3, 5, 8, 10] and [val(v) for v in a[4:8]] == [2, 2, P, Q]
+    assert rd(a[8], (2, 1)).tolist() == [[-1.0], [-1.0]] and rd(a[9], (2, 1)).tolist() == [[1.5], [1.5]]       # one box for all objects
+    # band 0 of each object sets its default max_stdev
+    assert rd(a[10], (2,)).tolist() == [10.0 * np.sqrt(np.var(Y5[:3], ddof=1)), 10.0 * np.sqrt(np.var(2.0 * Y5[:3], ddof=1))]
+    assert val(a[11]) == 1 and len(a) == 12
+    assert (bs.nobjects, bs.nbands, bs.dx, bs.d, bs.p, bs.q, bs.handle, bs.device) == (2, 2, DX, D, P, Q, H, 1)
+    assert bs.n.tolist() == [[3, 2], [3, 2]] and bs.n.dtype == np.int64 and bs.lag_bounds.tolist() == [[[-1.0, 1.5]], [[-1.0, 1.5]]]
+    assert [fake.args("carma_bandset_n", k)[1:] for k in range(4)] == [(0, 0), (0, 1), (1, 0), (1, 1)]
+    bs = make_bandset(fake, lag_bounds=[[(-1.0, 1.5)], [(-2.0, 2.5)]], max_stdev=2)                              # a box per object
+    a = fake.args("carma_bandset_create")
+    assert rd(a[8], (2, 1)).tolist() == [[-1.0], [-2.0]] and rd(a[9], (2, 1)).tolist() == [[1.5], [2.5]]
+    assert rd(a[10], (2,)).tolist() == [2.0, 2.0] and val(a[11]) == 0 and bs.lag_bounds.tolist() == [[[-1.0, 1.5]], [[-2.0, 2.5]]]
+    make_bandset(fake, max_stdev=[1, 2])
+    assert rd(fake.args("carma_bandset_create")[10], (2,)).tolist() == [1.0, 2.0]
+    b1 = make_bandset(fake, K=1)
+    a = fake.args("carma_bandset_create")
+    assert null(a[8]) and null(a[9]) and val(a[5]) == 1 and rd(a[3], (3,), np.int64).tolist() == [0, 3, 6]
+    assert (b1.dx, b1.d) == (D, D) and b1.lag_bounds.shape == (2, 0, 2)
+    for lb in (None, [(-1, 1), (-2, 2), (-3, 3)]):
+        with pytest.raises(ValueError, match=r"lag_bounds must hold one \(lo, hi\) pair for each of the 1 bands after the first, for all "
+                                             "objects or for each of the 2 objects"):
+            L.BandsSetContext(OBJECTS, P, Q, lag_bounds=lb)
+    for objects, msg in (([], "BandsSetContext needs at least one object"),
+                         ([OBJECTS[0], OBJECTS[1][:1]], "object 1 has 1 bands, object 0 has 2: the objects of a set share their bands"),
+                         ([OBJECTS[0], [OBJECTS[1][0], OBJECTS[1][1][:2]]], r"band 3: expected \(t, y, yerr\)"),
+                         ([[(T5[:3], Y5[:2], E5[:3])]], "band 0: time, y, yerr must have the same length")):
+        with pytest.raises(ValueError, match=msg):
+            L.BandsSetContext(objects, P, Q, lag_bounds=[(-1.0, 1.5)])
+    with pytest.raises(ValueError, match="operands could not be broadcast|broadcast"):
+        make_bandset(fake, max_stdev=[1, 2, 3])
+
+
+def test_bandsetcontext_prior_logdensity(fake):
+    bs = make_bandset(fake)
+    fake.on["carma_bandset_get_prior"] = lambda h, s, o: (fill(o, (3,), 1 + 10 * s), 0)[1]
+    assert bs.prior(1) == (11.0, 12.0, 13.0) and [val(v) for v in fake.args("carma_bandset_get_prior")[:2]] == [H, 1]
+    seen = {}
+
+    def logdens(h, th, w, B, ip, out):
+        seen.update(th=rd(th, (B, DX)), w=rd(w, (B,), np.int32).tolist(), B=B, ip=ip, out=C.cast(out, C.c_void_p).value)
+        fill(out, (B,), 100)
+        return 0
+    fake.on["carma_bandset_logdensity_batch"] = logdens
+    th = np.arange(3.0 * DX).reshape(3, DX)
+    out = bs.logdensity(th, [1, 0, 1])
+    assert out.tolist() == [100.0, 101.0, 102.0] and np.array_equal(seen["th"], th) and (seen["w"], seen["B"], seen["ip"]) == ([1, 0, 1], 3, 0)
+    assert bs.logdensity(th, 1, ignore_prior=True).shape == (3,) and (seen["w"], seen["ip"]) == ([1, 1, 1], 1)
+    one = bs.logdensity(th[2], 0)
+    assert isinstance(one, float) and one == 100.0 and np.array_equal(seen["th"], th[2:]) and seen["w"] == [0]
+    assert bs.logdensity(th, 7).shape == (3,) and seen["w"] == [7, 7, 7]          # the range is the library's check
+    buf = np.full((2, 2), -1.0)
+    out = bs.logdensity(th, [0, 1, 0], out=buf)                                  # the first B entries of a caller's array
+    assert seen["out"] == buf.ctypes.data and buf.ravel().tolist() == [100.0, 101.0, 102.0, -1.0] and out.tolist() == [100.0, 101.0, 102.0]
+    assert out.base is not None and np.shares_memory(out, buf)
+    for bad in (np.zeros(2), np.zeros(3, dtype=np.float32), np.zeros((3, 2))[:, 0]):
+        with pytest.raises(ValueError, match="out must be a contiguous float64 array of at least 3 entries"):
+            bs.logdensity(th, 0, out=bad)
+    with pytest.raises(ValueError):
+        bs.logdensity(th, [0, 1])
+    fake.on["carma_bandset_kernel_name"] = lambda h, buf, n: (setattr(buf, "value", b"k_set_%d" % n), 0)[1]
+    assert bs.kernel_name() == "k_set_128"
+
+
+def test_bandsetcontext_mle_batched(fake):
+    bs = make_bandset(fake)
+    seen = {}
+    _script_mle(fake, "carma_bandset_mle_batched", 7, 3, DX, seen)
+    x0 = np.arange(3.0 * DX).reshape(3, DX)
+    _check_mle_out(bs.mle_batched(x0, [1, 0, 1]), 3, DX)
+    a = seen["a"]
+    assert a[0] == H and np.array_equal(rd(a[1], (3, DX)), x0) and rd(a[2], (3,), np.int32).tolist() == [1, 0, 1] and val(a[3]) == 3
+    assert np.all(rd(a[4], (3, DX)) == -np.inf) and np.all(rd(a[5], (3, DX)) == np.inf) and null(a[6])
+    assert [val(v) for v in a[7:13]] == [2000, 8, 2.220446049250313e-09, 1e-5, 1e-6, 1] and len(a) == 18
+    lo, hi = -np.arange(1.0, DX + 1), np.arange(3.0 * DX).reshape(3, DX) + 1    # [dx] for every start, [B, dx] a box per start
+    _check_mle_out(bs.mle_batched(x0, 0, lo, hi, fixed_lag=[0.5, 1.5, 2.5], maxiter=9, mem=3, ignore_prior=False), 3, DX)
+    a = seen["a"]
+    assert rd(a[2], (3,), np.int32).tolist() == [0, 0, 0]
+    assert np.array_equal(rd(a[4], (3, DX)), np.tile(lo, (3, 1))) and np.array_equal(rd(a[5], (3, DX)), hi)
+    assert rd(a[6], (3, 1)).tolist() == [[0.5], [1.5], [2.5]] and [val(v) for v in a[7:13]] == [9, 3, 2.220446049250313e-09, 1e-5, 1e-6, 0]
+    with pytest.raises(ValueError, match=r"x0 must be \[B, 9\]"):
+        bs.mle_batched(np.zeros((3, D)), 0)
+    with pytest.raises(ValueError):
+        bs.mle_batched(x0, 0, fixed_lag=[0.5, 1.5])
+
+
+def test_bandsetcontext_smooth(fake):
+    bs = make_bandset(fake)
+    seen, flags = {}, [0, 0, 0]
+
+    def smooth(h, th, w, bo, B, tp, toff, mean, var, inv):
+        off = rd(toff, (B + 1,), np.int64)
+        ntot = max(int(off[-1]), 1)
+        seen.update(th=rd(th, (B, DX)), w=rd(w, (B,), np.int32).tolist(), bo=rd(bo, (B,), np.int32).tolist(), B=B, off=off.tolist(),
+                    tp=rd(tp, (ntot,)).tolist())
+        fill(mean, (ntot,)), fill(var, (ntot,), 10), wr(inv, flags, np.int32)
+        return 0
+    fake.on["carma_bandset_smooth"] = smooth
+    th = np.arange(3.0 * DX).reshape(3, DX)
+    m, v = bs.smooth(th, [1, 0, 1], 1, [9.0, 8.0])                               # one time array and one band for all rows
+    assert fake.args("carma_bandset_smooth")[0] == H and np.array_equal(seen["th"], th)
+    assert (seen["w"], seen["bo"], seen["B"], seen["off"], seen["tp"]) == ([1, 0, 1], [1, 1, 1], 3, [0, 2, 4, 6], [9.0, 8.0] * 3)
+    assert [a.tolist() for a in m] == [[0.0, 1.0], [2.0, 3.0], [4.0, 5.0]] and [a.tolist() for a in v] == [[10.0, 11.0], [12.0, 13.0], [14.0, 15.0]]
+    m, v = bs.smooth(th, 0, [0, 1, 0], np.array([9.0, 8.0]))
+    assert (seen["w"], seen["bo"], seen["off"]) == ([0, 0, 0], [0, 1, 0], [0, 2, 4, 6])
+    m, v = bs.smooth(th, 0, 0, [[9.0, 8.0, 7.0], [], [6.0]])                     # an array per row; an empty one is allowed
+    assert (seen["off"], seen["tp"]) == ([0, 3, 3, 4], [9.0, 8.0, 7.0, 6.0]) and [a.tolist() for a in m] == [[0.0, 1.0, 2.0], [], [3.0]]
+    assert [a.tolist() for a in v] == [[10.0, 11.0, 12.0], [], [13.0]]
+    m, v = bs.smooth(th, 0, 0, np.array([[1.0, 2.0], [3.0, 4.0], [5.0, 6.0]]))   # [B, M]: a row of times per row
+    assert (seen["off"], seen["tp"]) == ([0, 2, 4, 6], [1.0, 2.0, 3.0, 4.0, 5.0, 6.0])
+    m, v = bs.smooth(th[0], 1, 0, 4.5)                                           # one vector is one row; one time is one time
+    assert (seen["B"], seen["off"], seen["tp"]) == (1, [0, 1], [4.5]) and [a.tolist() for a in m] == [[0.0]]
+    m, v = bs.smooth(th, 0, 0, [[], [], []])                                     # all empty: one dummy time, outputs of length 1
+    assert (seen["off"], seen["tp"]) == ([0, 0, 0, 0], [0.0]) and [a.size for a in m] == [0, 0, 0]
+    with pytest.raises(ValueError, match=r"BandsSetContext.smooth: times must hold one array per row \(3\), got 2"):
+        bs.smooth(th, 0, 0, [[9.0], [8.0]])
+    flags[:] = [0, 1, 1]
+    m, v, inv = bs.smooth(th, 0, 0, [9.0, 8.0], return_invalid=True)
+    assert inv.dtype == bool and inv.tolist() == [False, True, True] and len(m) == len(v) == 3
+    with pytest.raises(L.CarmaError) as e:
+        bs.smooth(th, 0, 0, [9.0, 8.0])
+    assert str(e.value) == "BandsSetContext.smooth: a repeated AR root or a non-finite lag, scale or offset for row(s) [1, 2]"
+    fake.on["carma_bandset_smooth"] = lambda *a: -22
+    with pytest.raises(ValueError, match=r"carma_bandset_smooth failed \(-22\)"):
+        bs.smooth(th, 0, 0, [9.0])
+
+
+def test_bandsetcontext_sampler(fake):
+    bs = make_bandset(fake)
+    M, S = 3, 4
+    fake.on["carma_bandset_pt_default_box"] = lambda h, s, lo, hi: (fill(lo, (1, 2), 10 * s), fill(hi, (1, 2), 10 * s + 5), 0)[2]
+    lo, hi = bs.pt_default_box(1)
+    assert [val(v) for v in fake.args("carma_bandset_pt_default_box")[:2]] == [H, 1] and lo.tolist() == [[10.0, 11.0]] and hi.tolist() == [[15.0, 16.0]]
+    for call in (bs.pt_start, lambda: bs.pt_set_chains(np.zeros(M * R * T * DX)), bs.pt_get_chains, bs.pt_get_factor,
+                 lambda: bs.pt_sample(2), bs.pt_stats, lambda: bs.pt_logdensity(np.zeros(1))):
+        with pytest.raises(ValueError) as e:
+            call()
+        assert str(e.value) == "call pt_create first"
+    with pytest.raises(ValueError, match="need at least one run"):
+        bs.pt_create([], T, R, 10)
+    with pytest.raises(ValueError, match="temperatures must hold ntemps = 3 values"):
+        bs.pt_create([0], T, R, 10, temperatures=[1.0, 2.0])
+    bs.pt_create([1, 0, 1], T, R, 40, seed=2 ** 64 + 5)                          # band_box None: no box
+    a = fake.args("carma_bandset_pt_create")
+    assert a[0] == H and rd(a[1], (M,), np.int32).tolist() == [1, 0, 1] and [val(v) for v in a[2:5]] == [M, T, R] and null(a[5])
+    assert [val(v) for v in a[6:8]] == [40, 5] and null(a[8]) and null(a[9]) and len(a) == 10 and bs._pt_shape == (M, R, T)
+    one = (np.array([[-1.0, -2.0]]), np.array([[3.0, 4.0]]))                     # [K - 1, 2]: for every run
+    bs.pt_create([1, 0, 1], T, R, 40, seed=-1, temperatures=[1.0, 2.0, 4.0], band_box=one)
+    a = fake.args("carma_bandset_pt_create")
+    assert rd(a[5], (T,)).tolist() == [1.0, 2.0, 4.0] and val(a[7]) == 2 ** 64 - 1
+    assert rd(a[8], (M, 1, 2)).tolist() == [[[-1.0, -2.0]]] * M and rd(a[9], (M, 1, 2)).tolist() == [[[3.0, 4.0]]] * M
+    per = (-np.arange(1.0, 2 * M + 1).reshape(M, 1, 2), np.arange(1.0, 2 * M + 1).reshape(M, 1, 2))      # [M, K - 1, 2]: a box per run
+    bs.pt_create([1, 0, 1], T, R, 40, band_box=per)
+    a = fake.args("carma_bandset_pt_create")
+    assert np.array_equal(rd(a[8], (M, 1, 2)), per[0]) and np.array_equal(rd(a[9], (M, 1, 2)), per[1])
+    with pytest.raises(ValueError):
+        bs.pt_create([1, 0], T, R, 40, band_box=per)
+    bs.pt_create([1, 0, 1], T, R, 40)
+    bs.pt_start()
+    assert fake.args("carma_bandset_pt_start")[0] == H and null(fake.args("carma_bandset_pt_start")[1])
+    init = np.arange(1.0 * M * DX).reshape(M, DX)
+    bs.pt_start(init)
+    assert np.array_equal(rd(fake.args("carma_bandset_pt_start")[1], (M, DX)), init)
+    with pytest.raises(ValueError, match=r"init must be \[3, 9\] \(one row per run\), got \(2, 9\)"):
+        bs.pt_start(init[:2])
+    lead = (M, R, T)
+    fake.on["carma_bandset_pt_get_chains"] = lambda h, th, lp: (fill(th, lead + (DX,)), fill(lp, lead, 100), 0)[2]
+    th, lp = bs.pt_get_chains()
+    assert np.array_equal(th, np.arange(18.0 * DX).reshape(lead + (DX,))) and np.array_equal(lp, 100 + np.arange(18.0).reshape(lead))
+    fake.on["carma_bandset_pt_sample"] = lambda h, n, thin, s, lp: (fill(s, (M, R, n, DX)), fill(lp, (M, R, n), 7), 0)[2]
+    s, lp = bs.pt_sample(4, thin=3)
+    assert np.array_equal(s, np.arange(1.0 * M * R * 4 * DX).reshape(M, R, 4, DX)) and lp.shape == (M, R, 4)
+    fake.on["carma_bandset_pt_kernel_name"] = lambda h, buf, n: (setattr(buf, "value", b"k_bspt"), 0)[1]
+    assert bs.pt_kernel_name() == "k_bspt"
+    fake.on["carma_bandset_pt_run"] = lambda *a: (fill(a[12], (a[2], R, S, DX)), fill(a[13], (a[2], R, S), 5), 0)[2]
+    s, lp = bs.pt_run([1, 0, 1], T, R, S, 30, thin=2, init=init, seed=-1, band_box=per)
+    a = fake.args("carma_bandset_pt_run")
+    assert a[0] == H and rd(a[1], (M,), np.int32).tolist() == [1, 0, 1] and [val(v) for v in a[2:8]] == [M, T, R, S, 30, 2]
+    assert np.array_equal(rd(a[8], (M, DX)), init) and val(a[9]) == 2 ** 64 - 1 and len(a) == 14
+    assert np.array_equal(rd(a[10], (M, 1, 2)), per[0]) and np.array_equal(rd(a[11], (M, 1, 2)), per[1])
+    assert np.array_equal(s, np.arange(1.0 * M * R * S * DX).reshape(M, R, S, DX)) and np.array_equal(lp, 5 + np.arange(24.0).reshape(M, R, S))
+    bs.pt_run([0, 1], T, R, S, 30, band_box=one)
+    a = fake.args("carma_bandset_pt_run")
+    assert null(a[8]) and rd(a[10], (2, 1, 2)).tolist() == [[[-1.0, -2.0]]] * 2 and rd(a[11], (2, 1, 2)).tolist() == [[[3.0, 4.0]]] * 2
+    assert bs.pt_stats()[0].shape == (2, R, T)
+    bs.pt_run([0], T, R, S, 30)
+    a = fake.args("carma_bandset_pt_run")
+    assert null(a[8]) and null(a[10]) and null(a[11]) and bs.pt_stats()[0].shape == (1, R, T)
+    with pytest.raises(ValueError, match=r"init must be \[1, 9\]"):
+        bs.pt_run([0], T, R, S, 30, init=init)
+    # a failed create or run leaves no sampler behind
+    for name, call in (("carma_bandset_pt_create", lambda: bs.pt_create([0], T, R, 40)),
+                       ("carma_bandset_pt_run", lambda: bs.pt_run([0], T, R, S, 30))):
+        bs.pt_create([1, 0, 1], T, R, 40)
+        assert bs._pt_shape == (M, R, T)
+        fake.on[name] = lambda *a: -22
+        with pytest.raises(ValueError, match=r"%s failed \(-22\)" % name):
+            call()
+        assert bs._pt_shape is None
+        with pytest.raises(ValueError) as e:
+            bs.pt_stats()
+        assert str(e.value) == "call pt_create first"
+        del fake.on[name]
 
 
 # ---- stateless calls -----------------------------------------------------------------------------------
